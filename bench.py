@@ -10,7 +10,19 @@ frames/s, from an un-instrumented loop (HIP events around each batch only) with 
 batches in flight on their own extractor handles and HIP streams; the per-stage split and the
 roofline come from a second, profiled pass of one handle alone.
 
-Legs after the headline loop:
+A plain run (no --full) does only what the headline figure needs: set-up, warm-up, the timed
+loop, --dump-outputs if given, and the result line (metric, value, unit, ms_per_step, the per-batch
+latencies, the keypoint / match counts and the run's configuration).  Everything below -- the
+profiled pass with its rooflines, the CPU baselines and the other legs -- runs only with --full.
+
+--dump-outputs DIR writes what the last timed step returned to its caller (rank 0, after the timed
+loop) as DIR/<name>.npy, float32: counts [2B] and nmatches [B] whole, and keypoints [n,2,cap,7]
+(cv::KeyPoint fields in order), descriptors [n,2,cap,32], uright / depth [n,cap] of the n frames
+listed in frames [n] (a fixed seeded sample of the batch, at most 64 MB in all); rows past an
+image's keypoint count are written as zeros (the library leaves them untouched).  The inputs are
+seeded, so two builds run with the same arguments can be compared file for file.
+
+Legs after the headline loop (--full):
   config3   EuRoC-shaped stereo + PnP RANSAC per frame (configs[2]): extract+match of a frame batch
             (one frame per synthetic sequence) and one batched orbx_pnp_iterate_many over their solvers.
   localba   Optimizer::LocalBundleAdjustment (orbx_ba_run) on the config-4 problem
@@ -22,7 +34,7 @@ Legs after the headline loop:
             all-gather of the records + LocalBA summaries (RCCL over xGMI); the
             sequence, its parts alone and the all-gather timed separately.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
 
 Ranks: one process per GPU.  Under torch.distributed.run (WORLD_SIZE set) every rank checks
 WORLD_SIZE == --gpus and fails otherwise.  Started plainly with --gpus N > 1 (no WORLD_SIZE), the
@@ -61,6 +73,11 @@ def parse():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=256, help="stereo frames per step per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the profiled pass (per-stage times, rooflines), the CPU baselines and the "
+                         "other legs (single-frame, LocalBA, tracking, config 5 / 1 / 3)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (float32, seeded sample of frames)")
     ap.add_argument("--inflight", type=int, default=4, help="batches in flight (extractor handles / HIP streams)")
     ap.add_argument("--unique", type=int, default=16, help="seeded synthetic stereo scenes per rank (slots are distinct rolls of them)")
     ap.add_argument("--profile-steps", type=int, default=5, help="steps of the second, per-stage profiled pass")
@@ -941,89 +958,47 @@ def config5_leg(args, rank, world, dev, odist, exs, batch_images, pairs):
                      "(earlier batches are consumed in place) and every LocalBA summary")
 
 
-def main():
-    args = parse()
-    kind, n = rank_plan(args)
-    if kind == "launch":
-        sys.exit(launch_ranks(args, sys.argv[1:]))
+# ------------------------------------------------------------------ --dump-outputs
+DUMP_FRAMES = 16       # frames of the batch whose per-keypoint outputs are written
+DUMP_BYTES = 48 << 20  # ceiling of the sampled arrays together (the whole dump stays under 64 MB)
+
+
+def dump_outputs(path, slot, B):
+    """Write what the step that last ran on `slot` returned (orbx_stereo_frames_device's output buffers)
+    to path/<name>.npy as float32: counts and nmatches of the whole batch, and keypoints, descriptors,
+    uright and depth of a fixed seeded sample of its frames.  Rows at or past an image's keypoint count
+    are zeroed: the library does not write them, so they hold whatever the allocation held."""
     import torch
+    from orb_slam2_commit_amd._lib import KEYPOINT_DTYPE
+    os.makedirs(path, exist_ok=True)
+    cap = slot["kps"].shape[1]
+    per_frame = cap * (2 * 7 + 2 * 32 + 2) * 4  # float32 bytes of one frame's sampled arrays
+    n = max(1, min(B, DUMP_FRAMES, DUMP_BYTES // per_frame))
+    frames = np.sort(np.random.default_rng(0).choice(B, n, replace=False))
+    idx = torch.from_numpy(frames).to(slot["kps"].device)
+    counts = slot["counts"].cpu().numpy()
+    cnt = counts.reshape(B, 2)[frames]  # [n, (L, R)]
+    live = np.arange(cap)[None, None, :] < cnt[:, :, None]  # [n, 2, cap]
+    kps = slot["kps"].view(B, 2, cap, 28).index_select(0, idx).cpu().numpy().view(KEYPOINT_DTYPE)[..., 0]
+    kf = np.stack([kps[f].astype(np.float32) for f in KEYPOINT_DTYPE.names], axis=-1)  # [n, 2, cap, 7]
+    desc = slot["desc"].view(B, 2, cap, 32).index_select(0, idx).cpu().numpy().astype(np.float32)
+    arrays = dict(frames=frames, counts=counts, nmatches=slot["nmatch"].cpu().numpy(),
+                  keypoints=np.where(live[..., None], kf, 0), descriptors=np.where(live[..., None], desc, 0))
+    for name in ("uR", "depth"):
+        a = slot[name].index_select(0, idx).cpu().numpy()
+        arrays["uright" if name == "uR" else name] = np.where(live[:, 0], a, 0)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, np.float32))
 
-    from orb_slam2_commit_amd import dist as odist
-    rank, local, world = odist.env_rank()
-    assert world == n
-    backend = os.environ.get("ORBX_DIST_BACKEND", "nccl")
-    ndev = torch.cuda.device_count()
-    if backend == "gloo":
-        # one-GPU rehearsal of the multi-rank flow: ranks wrap onto the available devices
-        local = local % max(ndev, 1)
-    elif local >= ndev:
-        raise SystemExit("LOCAL_RANK %d but only %d GPU(s): one rank per GPU under RCCL" % (local, ndev))
-    torch.cuda.set_device(local)  # before the process group, so RCCL binds this rank's GPU
-    odist.init(backend, rank, world)
-    dev = torch.device("cuda", local)
-    devices_used = odist.distinct_devices(local, dev)  # distinct GPUs the ranks actually use
 
-    from orb_slam2_commit_amd import ORBextractor, synth
+# ------------------------------------------------------------------ --full: profiled pass + rooflines
+def profiled_pass(args, rank, dev, ex, step, B, elapsed, kps_per_img, acc_per_frame):
+    """The second, per-stage profiled pass of one handle alone and the rooflines derived from it and
+    from the timed loop's `elapsed`.  Returns the result-line entries they fill."""
+    import torch
     from orb_slam2_commit_amd import _lib
-
-    W, H, B = KITTI["width"], KITTI["height"], args.batch
-    # synthetic frames: sequence = rank (distinct seeds per rank: frame shards); every frame of every
-    # in-flight batch distinct (batch k holds frames k*B .. k*B+B-1 of the rank's sequence)
-    pairs = [synth.stereo_pair(s, W, H) for s in synth.sequence_seeds(rank, args.unique)]
-    # S = --inflight extractor handles, each with its own HIP stream, input batch and output buffers:
-    # step i runs on slot i % S, so consecutive batches overlap (one batch's latency-bound stages --
-    # octree, small pyramid levels, stereo finalize -- fill in beside the next batch's bandwidth-bound ones)
-    S = max(1, args.inflight)
-    batch_images = [torch.from_numpy(synth.stereo_batch(rank, B, pairs=pairs, first=k * B)).to(dev) for k in range(S)]
-    images = batch_images[0]
-    exs = [ORBextractor(KITTI["nfeatures"], 1.2, 8, 20, 7, device=local) for _ in range(S)]
-    ex = exs[0]
-    cap = ex.max_keypoints(W, H)
-    slots = []
-    for _ in range(S):
-        slots.append(dict(kps=torch.empty((2 * B, cap, 28), dtype=torch.uint8, device=dev),
-                          desc=torch.empty((2 * B, cap, 32), dtype=torch.uint8, device=dev),
-                          counts=torch.zeros(2 * B, dtype=torch.int32, device=dev),
-                          uR=torch.empty((B, cap), dtype=torch.float32, device=dev),
-                          depth=torch.empty((B, cap), dtype=torch.float32, device=dev),
-                          nmatch=torch.zeros(B, dtype=torch.int32, device=dev),
-                          stream=torch.cuda.Stream(dev)))
-    kps, desc, counts = slots[0]["kps"], slots[0]["desc"], slots[0]["counts"]
-    uR, depth, nmatch = slots[0]["uR"], slots[0]["depth"], slots[0]["nmatch"]
-    # dedicated streams for the whole run: the library launches on them (the legacy null stream would be
-    # replaced by the handle's own stream), and the step events / torch ops are ordered with the kernels
-    stream = slots[0]["stream"]
-    torch.cuda.set_stream(stream)
-    torch.cuda.synchronize(dev)
-    bf, baseline = KITTI["bf"], KITTI["bf"] / KITTI["fx"]
-
-    def step(i=0):
-        k = i % S
-        sl = slots[k]
-        exs[k].stereo_frames_device(batch_images[k], sl["kps"], sl["desc"], sl["counts"], bf, baseline, sl["uR"],
-                                    sl["depth"], sl["nmatch"], sl["stream"])
-
-    for i in range(max(args.warmup, S)):
-        step(i)
-    torch.cuda.synchronize(dev)
+    W, H = KITTI["width"], KITTI["height"]
     L = _lib.lib()
-
-    # ---- headline: un-instrumented timed loop (events around each step on its slot's stream)
-    ev0 = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps)]
-    ev1 = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps)]
-    odist.barrier()
-    torch.cuda.synchronize(dev)
-    t0 = time.perf_counter()
-    for i in range(args.steps):
-        st_i = slots[i % S]["stream"]
-        ev0[i].record(st_i)
-        step(i)
-        ev1[i].record(st_i)
-    torch.cuda.synchronize(dev)
-    odist.barrier()
-    elapsed = odist.max_over_ranks(time.perf_counter() - t0, dev)
-    step_ms = [ev0[i].elapsed_time(ev1[i]) for i in range(args.steps)]  # per-batch latency on its stream
-
     # ---- second pass: per-stage HIP events (orbx_profile_*, recorded on the kernels' stream)
     L.orbx_profile_reset(ex._h)
     L.orbx_profile_enable(ex._h, 1)
@@ -1038,10 +1013,6 @@ def main():
         L.orbx_profile_read(ex._h, s, C.byref(ms), C.byref(n), C.byref(name))
         if n.value:
             stages[name.value.decode()] = (ms.value, n.value)
-    cnt = counts.cpu().numpy()
-    nm = nmatch.cpu().numpy()
-    kps_per_img = float(cnt.mean())
-    acc_per_frame = float(nm.mean())  # surviving matches (lower bound of SAD refinements)
     ncand = L.orbx_debug_copy(ex._h, 2, 0, 0, None, 0) // 4  # FAST survivors per cell of the last batch
     cc = np.zeros(ncand, np.int32)
     L.orbx_debug_copy(ex._h, 2, 0, 0, _lib.ptr(cc), cc.nbytes)
@@ -1147,6 +1118,98 @@ def main():
                       note="SURVEY 8(d): 2*B_ext + B_st per stereo frame x frames/s of this rank (timed loop); "
                            "N_acc = surviving stereo matches per frame (a lower bound of the keypoints that reach "
                            "the SAD, so the figure is conservative)")
+    return {"roofline": roofline, "whole_step_roofline": whole_step,
+            "stage_ms_per_step": {k: round(v[0] / args.profile_steps, 4) for k, v in stages.items()},
+            "stage_hbm": stage_hbm, "fast_candidates_per_image": round(cand_per_img, 1), "level_pixels": P}
+
+
+def main():
+    args = parse()
+    kind, n = rank_plan(args)
+    if kind == "launch":
+        sys.exit(launch_ranks(args, sys.argv[1:]))
+    import torch
+
+    from orb_slam2_commit_amd import dist as odist
+    rank, local, world = odist.env_rank()
+    assert world == n
+    backend = os.environ.get("ORBX_DIST_BACKEND", "nccl")
+    ndev = torch.cuda.device_count()
+    if backend == "gloo":
+        # one-GPU rehearsal of the multi-rank flow: ranks wrap onto the available devices
+        local = local % max(ndev, 1)
+    elif local >= ndev:
+        raise SystemExit("LOCAL_RANK %d but only %d GPU(s): one rank per GPU under RCCL" % (local, ndev))
+    torch.cuda.set_device(local)  # before the process group, so RCCL binds this rank's GPU
+    odist.init(backend, rank, world)
+    dev = torch.device("cuda", local)
+    devices_used = odist.distinct_devices(local, dev)  # distinct GPUs the ranks actually use
+
+    from orb_slam2_commit_amd import ORBextractor, synth
+
+    W, H, B = KITTI["width"], KITTI["height"], args.batch
+    # synthetic frames: sequence = rank (distinct seeds per rank: frame shards); every frame of every
+    # in-flight batch distinct (batch k holds frames k*B .. k*B+B-1 of the rank's sequence)
+    pairs = [synth.stereo_pair(s, W, H) for s in synth.sequence_seeds(rank, args.unique)]
+    # S = --inflight extractor handles, each with its own HIP stream, input batch and output buffers:
+    # step i runs on slot i % S, so consecutive batches overlap (one batch's latency-bound stages --
+    # octree, small pyramid levels, stereo finalize -- fill in beside the next batch's bandwidth-bound ones)
+    S = max(1, args.inflight)
+    batch_images = [torch.from_numpy(synth.stereo_batch(rank, B, pairs=pairs, first=k * B)).to(dev) for k in range(S)]
+    images = batch_images[0]
+    exs = [ORBextractor(KITTI["nfeatures"], 1.2, 8, 20, 7, device=local) for _ in range(S)]
+    ex = exs[0]
+    cap = ex.max_keypoints(W, H)
+    slots = []
+    for _ in range(S):
+        slots.append(dict(kps=torch.empty((2 * B, cap, 28), dtype=torch.uint8, device=dev),
+                          desc=torch.empty((2 * B, cap, 32), dtype=torch.uint8, device=dev),
+                          counts=torch.zeros(2 * B, dtype=torch.int32, device=dev),
+                          uR=torch.empty((B, cap), dtype=torch.float32, device=dev),
+                          depth=torch.empty((B, cap), dtype=torch.float32, device=dev),
+                          nmatch=torch.zeros(B, dtype=torch.int32, device=dev),
+                          stream=torch.cuda.Stream(dev)))
+    kps, desc, counts = slots[0]["kps"], slots[0]["desc"], slots[0]["counts"]
+    uR, depth, nmatch = slots[0]["uR"], slots[0]["depth"], slots[0]["nmatch"]
+    # dedicated streams for the whole run: the library launches on them (the legacy null stream would be
+    # replaced by the handle's own stream), and the step events / torch ops are ordered with the kernels
+    stream = slots[0]["stream"]
+    torch.cuda.set_stream(stream)
+    torch.cuda.synchronize(dev)
+    bf, baseline = KITTI["bf"], KITTI["bf"] / KITTI["fx"]
+
+    def step(i=0):
+        k = i % S
+        sl = slots[k]
+        exs[k].stereo_frames_device(batch_images[k], sl["kps"], sl["desc"], sl["counts"], bf, baseline, sl["uR"],
+                                    sl["depth"], sl["nmatch"], sl["stream"])
+
+    for i in range(max(args.warmup, S)):
+        step(i)
+    torch.cuda.synchronize(dev)
+
+    # ---- headline: un-instrumented timed loop (events around each step on its slot's stream)
+    ev0 = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps)]
+    ev1 = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps)]
+    odist.barrier()
+    torch.cuda.synchronize(dev)
+    t0 = time.perf_counter()
+    for i in range(args.steps):
+        st_i = slots[i % S]["stream"]
+        ev0[i].record(st_i)
+        step(i)
+        ev1[i].record(st_i)
+    torch.cuda.synchronize(dev)
+    odist.barrier()
+    elapsed = odist.max_over_ranks(time.perf_counter() - t0, dev)
+    step_ms = [ev0[i].elapsed_time(ev1[i]) for i in range(args.steps)]  # per-batch latency on its stream
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, slots[(args.steps - 1) % S], B)
+    cnt = counts.cpu().numpy()
+    nm = nmatch.cpu().numpy()
+    kps_per_img = float(cnt.mean())
+    acc_per_frame = float(nm.mean())  # surviving matches (lower bound of SAD refinements)
     value = odist.job_throughput(B, args.steps, world, elapsed)
     info, cpus = host_info()
     out = {
@@ -1172,35 +1235,32 @@ def main():
                    "scale_factor": 1.2, "fast_th": [20, 7], "parallelism": "frame-sharded x%d" % world,
                    "devices_used": devices_used, "dist_backend": odist.backend(),
                    "batches_in_flight": S},
-        "roofline": roofline,
-        "whole_step_roofline": whole_step,
-        "stage_ms_per_step": {k: round(v[0] / args.profile_steps, 4) for k, v in stages.items()},
-        "stage_hbm": stage_hbm,
         "keypoints_per_image": round(kps_per_img, 1),
         "stereo_matches_per_frame": round(acc_per_frame, 1),
-        "fast_candidates_per_image": round(cand_per_img, 1),
-        "level_pixels": P,
         "localba_iters_per_s": None,
         "host": info,
         "cpu_baseline": None,
+        "full": bool(args.full),
     }
-    oracle_mod, flags = None, None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        oracle_mod, flags = load_oracle()
-        out["cpu_baseline"] = cpu_baseline(oracle_mod, flags, pairs, args.cpu_baseline_seconds, cpus)
-    if args.single_frames > 0 and rank == 0 and world == 1:
-        out["single_frame"] = single_frame_leg(args, pairs, out["cpu_baseline"])
-    if args.ba_calls > 0:
-        out["localba"] = localba_leg(args, rank, world, dev, odist, oracle_mod, flags, cpus)
-        out["localba_iters_per_s"] = out["localba"]["iters_per_s"]
-    if args.track_steps > 0:
-        out["track"] = track_leg(args, rank, world, dev, odist, ex, images, stream, pairs)
-    if args.pipeline_steps > 0:
-        out["config5"] = config5_leg(args, rank, world, dev, odist, exs, batch_images, pairs)
-    if args.c1_batch > 0 and rank == 0 and world == 1:
-        out["config1"] = config1_leg(args, dev, oracle_mod, flags, cpus)
-    if args.c3_steps > 0:
-        out["config3"] = config3_leg(args, rank, world, dev, odist, stream, oracle_mod, flags, cpus)
+    if args.full:
+        out.update(profiled_pass(args, rank, dev, ex, step, B, elapsed, kps_per_img, acc_per_frame))
+        oracle_mod, flags = None, None
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            oracle_mod, flags = load_oracle()
+            out["cpu_baseline"] = cpu_baseline(oracle_mod, flags, pairs, args.cpu_baseline_seconds, cpus)
+        if args.single_frames > 0 and rank == 0 and world == 1:
+            out["single_frame"] = single_frame_leg(args, pairs, out["cpu_baseline"])
+        if args.ba_calls > 0:
+            out["localba"] = localba_leg(args, rank, world, dev, odist, oracle_mod, flags, cpus)
+            out["localba_iters_per_s"] = out["localba"]["iters_per_s"]
+        if args.track_steps > 0:
+            out["track"] = track_leg(args, rank, world, dev, odist, ex, images, stream, pairs)
+        if args.pipeline_steps > 0:
+            out["config5"] = config5_leg(args, rank, world, dev, odist, exs, batch_images, pairs)
+        if args.c1_batch > 0 and rank == 0 and world == 1:
+            out["config1"] = config1_leg(args, dev, oracle_mod, flags, cpus)
+        if args.c3_steps > 0:
+            out["config3"] = config3_leg(args, rank, world, dev, odist, stream, oracle_mod, flags, cpus)
     if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:

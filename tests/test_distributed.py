@@ -111,3 +111,61 @@ def test_bench_launcher_refuses_more_ranks_than_gpus_under_rccl():
                        capture_output=True, text=True, timeout=300)
     assert r.returncode != 0
     assert "GPU(s) visible" in r.stderr
+
+
+# ------------------------------------------------------------------ bench.py --full / --dump-outputs
+def test_bench_plain_run_is_the_default(monkeypatch):
+    import sys
+    b, _ = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = b.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = b.parse()
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_bench_dump_outputs_layout(tmp_path):
+    """dump_outputs on host tensors: float32 files, whole-batch counts, the sampled frames' arrays with
+    the cv::KeyPoint fields in order and every row at or past an image's count zeroed."""
+    import numpy as np
+    import torch
+    from orb_slam2_commit_amd._lib import KEYPOINT_DTYPE
+    b, _ = _bench()
+    B, cap = 24, 40
+    rng = np.random.default_rng(11)
+    kps = np.zeros((2 * B, cap), KEYPOINT_DTYPE)
+    for f in KEYPOINT_DTYPE.names:
+        kps[f] = rng.integers(1, 1000, kps.shape)
+    desc = rng.integers(1, 256, (2 * B, cap, 32), dtype=np.uint8)
+    counts = rng.integers(0, cap + 1, 2 * B).astype(np.int32)
+    uR = rng.uniform(1, 100, (B, cap)).astype(np.float32)
+    depth = rng.uniform(1, 100, (B, cap)).astype(np.float32)
+    slot = dict(kps=torch.from_numpy(kps.view(np.uint8).reshape(2 * B, cap, 28)), desc=torch.from_numpy(desc),
+                counts=torch.from_numpy(counts), uR=torch.from_numpy(uR), depth=torch.from_numpy(depth),
+                nmatch=torch.arange(B, dtype=torch.int32))
+    out = [tmp_path / "a", tmp_path / "b"]
+    for d in out:
+        b.dump_outputs(str(d), slot, B)
+    got = {p.name[:-4]: np.load(p) for p in sorted(out[0].iterdir())}
+    assert sorted(got) == ["counts", "depth", "descriptors", "frames", "keypoints", "nmatches", "uright"]
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    for name, a in got.items():  # the sample is fixed: a second dump is the same, file for file
+        assert np.array_equal(a, np.load(out[1] / (name + ".npy")))
+    frames = got["frames"].astype(int)
+    n = len(frames)
+    assert n == b.DUMP_FRAMES and len(set(frames)) == n and frames.min() >= 0 and frames.max() < B
+    assert np.array_equal(got["counts"], counts) and np.array_equal(got["nmatches"], np.arange(B))
+    assert got["keypoints"].shape == (n, 2, cap, 7) and got["descriptors"].shape == (n, 2, cap, 32)
+    assert got["uright"].shape == (n, cap) and got["depth"].shape == (n, cap)
+    for i, f in enumerate(frames):
+        for side in (0, 1):
+            c = counts[2 * f + side]
+            for j, field in enumerate(KEYPOINT_DTYPE.names):
+                assert np.array_equal(got["keypoints"][i, side, :c, j], kps[field][2 * f + side, :c].astype(np.float32))
+            assert np.array_equal(got["descriptors"][i, side, :c], desc[2 * f + side, :c].astype(np.float32))
+            assert not got["keypoints"][i, side, c:].any() and not got["descriptors"][i, side, c:].any()
+        c = counts[2 * f]
+        assert np.array_equal(got["uright"][i, :c], uR[f, :c]) and not got["uright"][i, c:].any()
+        assert np.array_equal(got["depth"][i, :c], depth[f, :c]) and not got["depth"][i, c:].any()

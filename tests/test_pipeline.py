@@ -308,7 +308,7 @@ def test_gpu_two_rank_rehearsal_gathered_records(gpu):
 
 @pytest.mark.gpu
 def test_gpu_bench_launcher_gloo_two_ranks(gpu):
-    """`ORBX_DIST_BACKEND=gloo python bench.py --gpus 2` (no WORLD_SIZE): the launcher starts two ranks
+    """`ORBX_DIST_BACKEND=gloo python bench.py --full --gpus 2` (no WORLD_SIZE): the launcher starts two ranks
     under torch.distributed.run as a child process; rank 0's line says n_gpus 2, backend gloo, and the
     config-5 all-gather ran over 2 ranks with every gathered slot equal to its rank's arena."""
     import json
@@ -317,9 +317,9 @@ def test_gpu_bench_launcher_gloo_two_ranks(gpu):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["ORBX_DIST_BACKEND"] = "gloo"
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--batch", "8", "--inflight", "1", "--unique", "2", "--profile-steps", "1", "--no-cpu-baseline",
-           "--ba-calls", "0", "--single-frames", "0", "--track-steps", "0", "--c3-steps", "0",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "2",
+           "--warmup", "1", "--batch", "8", "--inflight", "1", "--unique", "2", "--profile-steps", "1",
+           "--no-cpu-baseline", "--ba-calls", "0", "--single-frames", "0", "--track-steps", "0", "--c3-steps", "0",
            "--pipeline-steps", "1", "--kf-every", "8"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-2000:]

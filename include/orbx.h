@@ -52,6 +52,18 @@
  *   orbx_local_ba / orbx_ba_*   Optimizer::LocalBundleAdjustment src/Optimizer.cc:530-885, include/Optimizer.h:61
  *                               (g2o graph build, optimize(5), outlier levels, optimize(10), vToErase;
  *                               the Map mutex/recovery part stays on the caller's side)
+ *   orbx_kfdb_create            KeyFrameDatabase::KeyFrameDatabase  src/KeyFrameDatabase.cc:33-37, include/KeyFrameDatabase.h:46
+ *   orbx_kfdb_add / _erase / _clear   KeyFrameDatabase::add / erase / clear   src/KeyFrameDatabase.cc:40-73
+ *   orbx_kfdb_set_neighbours    KeyFrame::GetBestCovisibilityKeyFrames(10) of the keyframes, read at
+ *                                                               src/KeyFrameDatabase.cc:167, 294
+ *   orbx_kfdb_reloc_candidates[_device]  KeyFrameDatabase::DetectRelocalizationCandidates
+ *                                                               src/KeyFrameDatabase.cc:219-341 (src/Tracking.cc:1362)
+ *   orbx_kfdb_loop_candidates[_device]   KeyFrameDatabase::DetectLoopCandidates
+ *                                                               src/KeyFrameDatabase.cc:76-217 (src/LoopClosing.cc DetectLoop)
+ *   orbx_kfdb_score             ORBVocabulary::score (DBoW2 L1Scoring::score; minScore loop of
+ *                               src/LoopClosing.cc DetectLoop, and :145, :274 of KeyFrameDatabase.cc)
+ *   orbx_kfdb_read_state        KeyFrame::mnRelocQuery, mnRelocWords, mRelocScore, mnLoopQuery, mnLoopWords,
+ *                               mLoopScore                      include/KeyFrame.h:145-150
  */
 #ifndef ORBX_H
 #define ORBX_H
@@ -256,6 +268,83 @@ orbx_status orbx_voc_transform_device(orbx_voc* v, const uint8_t* d_desc, int ca
                                       uint32_t* d_bow_words, double* d_bow_values, int32_t* d_n_bow,
                                       uint32_t* d_fv_nodes, int32_t* d_fv_off, int32_t* d_fv_feat, int32_t* d_n_fv,
                                       void* stream);
+
+/* KeyFrameDatabase (include/KeyFrameDatabase.h, src/KeyFrameDatabase.cc:33-341) as a device-resident
+ * object with the reference's exact results: the candidate list in the reference's order (the order
+ * keyframes are first met when the query's words are scanned ascending and each word's inverted list
+ * in add order; a pBestKF is listed once, where it first occurs), and the six per-keyframe members
+ * the queries read and write -- mnRelocQuery, mnRelocWords, mRelocScore, mnLoopQuery, mnLoopWords,
+ * mLoopScore -- kept on the device for every keyframe id the handle has ever seen.  The two query ids
+ * and word counts start at 0 as in the reference (src/KeyFrame.cc:35), so a query with id 0 finds
+ * nothing new on fresh keyframes; the two scores, which the reference leaves uninitialised, start at
+ * 0.0f.  The state of an id survives orbx_kfdb_erase followed by orbx_kfdb_add; orbx_kfdb_clear
+ * forgets every id.  A keyframe is its id (mnId, >= 0); a BowVector is n <= 8192 ascending word ids
+ * with their values, as orbx_voc_transform returns one.
+ * Only L1 scoring (scoring type 0, what ORBvoc uses) is supported: orbx_kfdb_create on a vocabulary
+ * with another scoring type returns ORBX_ERR_ARG.  Without a usable device it returns ORBX_ERR_NODEV
+ * (checked right after `out` and `device`, before the vocabulary).
+ * A handle is not thread-safe.  The host entry points are synchronous; they first wait for the
+ * queries queued by the _device forms. */
+typedef struct orbx_kfdb orbx_kfdb;
+orbx_status orbx_kfdb_create(const orbx_voc* voc, int device, orbx_kfdb** out);
+orbx_status orbx_kfdb_destroy(orbx_kfdb* db);
+/* The host-side check every entry point below applies to a BowVector before any device call, on its own
+ * (needs no handle and no device): 0 <= n <= 8192, non-NULL arrays when n > 0, words strictly ascending
+ * and below n_words.  ORBX_OK or ORBX_ERR_ARG. */
+orbx_status orbx_kfdb_check_bow(const uint32_t* words, const double* values, int n, uint32_t n_words);
+/* add(pKF) with pKF->mBowVec (host pointers).  Checked on the host before any device call: kf_id >= 0,
+ * 0 <= n <= 8192, words strictly ascending and below the vocabulary's word count (ORBX_ERR_ARG); an id
+ * that is live in the database: ORBX_ERR_STATE.  n == 0 is legal (the keyframe is in no list).  The
+ * tables and the word/value pool grow on demand. */
+orbx_status orbx_kfdb_add(orbx_kfdb* db, int64_t kf_id, const uint32_t* words, const double* values, int n);
+/* erase(pKF) (an id that is not live: nothing happens) / clear().  The pool is compacted once more of
+ * it is dead than live. */
+orbx_status orbx_kfdb_erase(orbx_kfdb* db, int64_t kf_id);
+orbx_status orbx_kfdb_clear(orbx_kfdb* db);
+/* GetBestCovisibilityKeyFrames(10) of n_kfs keyframes: keyframe kf_ids[i] has n_best[i] <= 10 neighbour
+ * ids at best10 + 10*i, in the covisibility graph's order.  Ids that are not live in the database are
+ * legal (the queries skip them); the lists stay until set again. */
+orbx_status orbx_kfdb_set_neighbours(orbx_kfdb* db, const int64_t* kf_ids, const int64_t* best10,
+                                     const int32_t* n_best, int n_kfs);
+/* DetectRelocalizationCandidates(F): frame_id = F->mnId, the BowVector = F->mBowVec.  Host pointers.
+ * cand receives *n_cand ids; ORBX_ERR_CAPACITY when cap is too small, *n_cand then holds the needed
+ * size (the state has been updated all the same). */
+orbx_status orbx_kfdb_reloc_candidates(orbx_kfdb* db, uint64_t frame_id, const uint32_t* words, const double* values,
+                                       int n, int64_t* cand, int cap, int* n_cand);
+/* DetectLoopCandidates(pKF, minScore): kf_mnid = pKF->mnId, connected = pKF->GetConnectedKeyFrames()
+ * (all of them; ids unknown to the database are ignored). */
+orbx_status orbx_kfdb_loop_candidates(orbx_kfdb* db, uint64_t kf_mnid, const uint32_t* words, const double* values,
+                                      int n, const int64_t* connected, int n_connected, float min_score,
+                                      int64_t* cand, int cap, int* n_cand);
+/* The same queued on `stream` (NULL: the handle's own; ORBX_STREAM_NULL: the device's legacy null
+ * stream) with no host synchronisation: d_words / d_values / d_n are device pointers laid out as
+ * orbx_voc_transform_device writes one set (the count is read on the device and clamped to 8192; word
+ * ids beyond the vocabulary match nothing), d_cand[cap] and d_n_cand are written on the device
+ * (*d_n_cand = the needed size; only the first cap candidates are stored).  Queries queued one after
+ * the other see each other's state updates in order, on one stream or several.  `connected` is a host
+ * array: it is staged in pinned memory the handle owns (four buffers in turn; a call waits on the host
+ * only when the query that used its buffer four loop queries ago has not run yet). */
+orbx_status orbx_kfdb_reloc_candidates_device(orbx_kfdb* db, uint64_t frame_id, const uint32_t* d_words,
+                                              const double* d_values, const int32_t* d_n, int64_t* d_cand, int cap,
+                                              int32_t* d_n_cand, void* stream);
+orbx_status orbx_kfdb_loop_candidates_device(orbx_kfdb* db, uint64_t kf_mnid, const uint32_t* d_words,
+                                             const double* d_values, const int32_t* d_n, const int64_t* connected,
+                                             int n_connected, float min_score, int64_t* d_cand, int cap,
+                                             int32_t* d_n_cand, void* stream);
+/* ORBVocabulary::score(query, keyframe) for n_kfs live keyframes (an id that is not live:
+ * ORBX_ERR_ARG): DBoW2's L1Scoring::score, -sum/2 with sum += (|vi - wi| - |vi|) - |wi| over the common
+ * words in ascending word order, vi the query's value -- the double the reference computes, bit for
+ * bit.  LoopClosing::DetectLoop derives minScore from it.  No state is touched. */
+orbx_status orbx_kfdb_score(orbx_kfdb* db, const uint32_t* words, const double* values, int n, const int64_t* kf_ids,
+                            int n_kfs, double* scores);
+/* The six members of n keyframes (ids the handle has seen, live or not; else ORBX_ERR_ARG).  Any output
+ * may be NULL.  Each requested array is read back whole (one entry per id the handle has ever seen)
+ * and gathered on the host, so the cost grows with the ids seen, not with n. */
+orbx_status orbx_kfdb_read_state(orbx_kfdb* db, const int64_t* kf_ids, int n, uint64_t* reloc_query,
+                                 int32_t* reloc_words, float* reloc_score, uint64_t* loop_query, int32_t* loop_words,
+                                 float* loop_score);
+/* live keyframes and pool entries in use (dead ones included until the next compaction) */
+orbx_status orbx_kfdb_size(const orbx_kfdb* db, int* live, long long* pool_entries);
 
 /* Optimizer::LocalBundleAdjustment on g2o semantics (BlockSolver_6_3 +
  * LinearSolverEigen + Levenberg, Huber kernels, two phases), FP64 on the GPU.

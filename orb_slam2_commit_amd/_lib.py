@@ -211,6 +211,22 @@ SIGNATURES = {
     "orbx_voc_transform": ([P, P, P, C.c_int, C.c_int, P, P, P, P, P, P, P], C.c_int),
     "orbx_voc_transform_device": ([P, P, C.c_int, C.c_longlong, P, C.c_int, C.c_int, C.c_int, P, P, P, P, P, P, P, P],
                                   C.c_int),
+    "orbx_kfdb_create": ([P, C.c_int, C.POINTER(C.c_void_p)], C.c_int),
+    "orbx_kfdb_destroy": ([P], C.c_int),
+    "orbx_kfdb_check_bow": ([P, P, C.c_int, C.c_uint32], C.c_int),
+    "orbx_kfdb_add": ([P, C.c_int64, P, P, C.c_int], C.c_int),
+    "orbx_kfdb_erase": ([P, C.c_int64], C.c_int),
+    "orbx_kfdb_clear": ([P], C.c_int),
+    "orbx_kfdb_set_neighbours": ([P, P, P, P, C.c_int], C.c_int),
+    "orbx_kfdb_reloc_candidates": ([P, C.c_uint64, P, P, C.c_int, P, C.c_int, C.POINTER(C.c_int)], C.c_int),
+    "orbx_kfdb_loop_candidates": ([P, C.c_uint64, P, P, C.c_int, P, C.c_int, C.c_float, P, C.c_int,
+                                   C.POINTER(C.c_int)], C.c_int),
+    "orbx_kfdb_reloc_candidates_device": ([P, C.c_uint64, P, P, P, P, C.c_int, P, P], C.c_int),
+    "orbx_kfdb_loop_candidates_device": ([P, C.c_uint64, P, P, P, P, C.c_int, C.c_float, P, C.c_int, P, P],
+                                         C.c_int),
+    "orbx_kfdb_score": ([P, P, P, C.c_int, P, C.c_int, P], C.c_int),
+    "orbx_kfdb_read_state": ([P, P, C.c_int, P, P, P, P, P, P], C.c_int),
+    "orbx_kfdb_size": ([P, C.POINTER(C.c_int), C.POINTER(C.c_longlong)], C.c_int),
     "orbx_track_gather_device": ([C.POINTER(TrackGather), C.c_int, P], C.c_int),
     "orbx_frame_points_device": ([C.POINTER(FramePoints), C.c_int, P], C.c_int),
     "orbx_track_step_device": ([C.POINTER(TrackStep), C.c_int, P], C.c_int),

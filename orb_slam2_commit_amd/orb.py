@@ -19,6 +19,7 @@ Every result is computed by the HIP kernels; this module only moves bytes.
 """
 import contextlib
 import ctypes as C
+import threading
 
 import numpy as np
 
@@ -909,6 +910,8 @@ class ORBVocabulary:
     def __init__(self, device=0):
         self.device = device
         self._h = None
+        self._score_db = None
+        self._score_lock = threading.Lock()
 
     def loadFromText(self, text):
         """The text of a vocabulary file (ORBvoc.txt format).  Returns True like the reference."""
@@ -952,7 +955,26 @@ class ORBVocabulary:
         """(BowVector as (words, values), FeatureVector as CSR (nodes, off, feat))."""
         return self.transform_sets([desc], levelsup)[0]
 
+    def score(self, v1_words, v1_values, v2_words, v2_values):
+        """ORBVocabulary::score(v1, v2) (DBoW2 L1Scoring::score) of two BowVectors given as ascending
+        word ids and values: the reference's double, computed on the GPU (v2 goes through a private
+        one-keyframe KeyFrameDatabase; KeyFrameDatabase.score scores many keyframes at once).  Calls are
+        serialised by a lock; each costs two small uploads, three launches and a read-back."""
+        with self._score_lock:
+            if self._score_db is None:
+                self._score_db = KeyFrameDatabase(self)
+                self._score_db.voc = None  # no reference cycle: the vocabulary owns this database
+            db = self._score_db
+            db.add(0, (v2_words, v2_values))
+            try:
+                return float(db.score((v1_words, v1_values), [0])[0])
+            finally:
+                db.erase(0)
+
     def close(self):
+        if getattr(self, "_score_db", None) is not None:
+            self._score_db.close()
+            self._score_db = None
         if getattr(self, "_h", None):
             _lib.lib().orbx_voc_destroy(self._h)
             self._h = None
@@ -962,3 +984,130 @@ class ORBVocabulary:
             self.close()
         except Exception:
             pass
+
+
+def _bow(bow):
+    w = np.ascontiguousarray(bow[0], np.uint32).reshape(-1)
+    v = np.ascontiguousarray(bow[1], np.float64).reshape(-1)
+    if len(w) != len(v):
+        raise ValueError("BowVector words and values differ in length")
+    return w, v
+
+
+class KeyFrameDatabase:
+    """The reference's KeyFrameDatabase (include/KeyFrameDatabase.h, src/KeyFrameDatabase.cc:33-341) on
+    the GPU over orbx_kfdb_*: the same candidate lists in the same order, and the six KeyFrame members
+    the queries touch (mnRelocQuery, mnRelocWords, mRelocScore, mnLoopQuery, mnLoopWords, mLoopScore)
+    kept on the device per keyframe id (read_state).  A keyframe is its mnId; a BowVector is a pair
+    (ascending word ids, values) as ORBVocabulary.transform returns it.  Raises OrbxError (code -4)
+    without a GPU -- there is no CPU fallback."""
+
+    def __init__(self, voc, device=None):
+        h = C.c_void_p()
+        dev = int(voc.device if device is None else device)
+        check(_lib.lib().orbx_kfdb_create(getattr(voc, "_h", None), dev, C.byref(h)), "orbx_kfdb_create")
+        self._h = h
+        self.voc = voc
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.lib().orbx_kfdb_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, kf_id, bow):
+        """add(pKF): kf_id = pKF->mnId, bow = pKF->mBowVec."""
+        w, v = _bow(bow)
+        check(_lib.lib().orbx_kfdb_add(self._h, int(kf_id), ptr(w), ptr(v), len(w)), "orbx_kfdb_add")
+
+    def erase(self, kf_id):
+        check(_lib.lib().orbx_kfdb_erase(self._h, int(kf_id)), "orbx_kfdb_erase")
+
+    def clear(self):
+        check(_lib.lib().orbx_kfdb_clear(self._h), "orbx_kfdb_clear")
+
+    def set_neighbours(self, neighbours):
+        """neighbours: {kf_id: GetBestCovisibilityKeyFrames(10) as ids, in the graph's order}."""
+        ids = np.array(list(neighbours.keys()), np.int64)
+        best = np.zeros((max(len(ids), 1), 10), np.int64)
+        nb = np.zeros(max(len(ids), 1), np.int32)
+        for i, k in enumerate(ids):
+            lst = [int(x) for x in neighbours[int(k)]]
+            if len(lst) > 10:
+                raise ValueError("more than 10 neighbours")
+            best[i, :len(lst)] = lst
+            nb[i] = len(lst)
+        check(_lib.lib().orbx_kfdb_set_neighbours(self._h, ptr(ids), ptr(best), ptr(nb), len(ids)),
+              "orbx_kfdb_set_neighbours")
+
+    def size(self):
+        """(live keyframes, pool entries in use)."""
+        live, pool = C.c_int(), C.c_longlong()
+        check(_lib.lib().orbx_kfdb_size(self._h, C.byref(live), C.byref(pool)), "orbx_kfdb_size")
+        return live.value, pool.value
+
+    def _cap(self, cap):
+        return max(self.size()[0], 1) if cap is None else int(cap)
+
+    def DetectRelocalizationCandidates(self, frame_id, bow, cap=None):
+        """DetectRelocalizationCandidates(F): frame_id = F->mnId, bow = F->mBowVec -> keyframe ids."""
+        w, v = _bow(bow)
+        cap = self._cap(cap)
+        cand, n = np.zeros(max(cap, 1), np.int64), C.c_int()
+        check(_lib.lib().orbx_kfdb_reloc_candidates(self._h, int(frame_id), ptr(w), ptr(v), len(w), ptr(cand), cap,
+                                                    C.byref(n)), "orbx_kfdb_reloc_candidates")
+        return [int(x) for x in cand[:n.value]]
+
+    def DetectLoopCandidates(self, kf_mnid, bow, connected, minScore, cap=None):
+        """DetectLoopCandidates(pKF, minScore): connected = pKF->GetConnectedKeyFrames() as ids."""
+        w, v = _bow(bow)
+        conn = np.ascontiguousarray(list(connected), np.int64)
+        cap = self._cap(cap)
+        cand, n = np.zeros(max(cap, 1), np.int64), C.c_int()
+        check(_lib.lib().orbx_kfdb_loop_candidates(self._h, int(kf_mnid), ptr(w), ptr(v), len(w), ptr(conn), len(conn),
+                                                   float(minScore), ptr(cand), cap, C.byref(n)),
+              "orbx_kfdb_loop_candidates")
+        return [int(x) for x in cand[:n.value]]
+
+    def score(self, bow, kf_ids):
+        """mpVoc->score(bow, pKF->mBowVec) for each listed (live) keyframe: float64 array."""
+        w, v = _bow(bow)
+        ids = np.ascontiguousarray(list(kf_ids), np.int64)
+        out = np.zeros(max(len(ids), 1), np.float64)
+        check(_lib.lib().orbx_kfdb_score(self._h, ptr(w), ptr(v), len(w), ptr(ids), len(ids), ptr(out)),
+              "orbx_kfdb_score")
+        return out[:len(ids)]
+
+    def read_state(self, kf_ids):
+        """The six members of the listed keyframes: dict of arrays named like the reference's members."""
+        ids = np.ascontiguousarray(list(kf_ids), np.int64)
+        m = max(len(ids), 1)
+        out = dict(mnRelocQuery=np.zeros(m, np.uint64), mnRelocWords=np.zeros(m, np.int32),
+                   mRelocScore=np.zeros(m, np.float32), mnLoopQuery=np.zeros(m, np.uint64),
+                   mnLoopWords=np.zeros(m, np.int32), mLoopScore=np.zeros(m, np.float32))
+        check(_lib.lib().orbx_kfdb_read_state(self._h, ptr(ids), len(ids), *[ptr(a) for a in out.values()]),
+              "orbx_kfdb_read_state")
+        return {k: a[:len(ids)] for k, a in out.items()}
+
+    def reloc_candidates_device(self, frame_id, words, values, n, cand, n_cand, stream=None):
+        """DetectRelocalizationCandidates queued on `stream` (a torch stream; None: the handle's own)
+        with no host synchronisation: words (uint32 as int32) / values (float64) / n (int32) are device
+        tensors laid out as orbx_voc_transform_device writes one set, cand (int64) and n_cand (int32)
+        device tensors that receive the ids and their number."""
+        check(_lib.lib().orbx_kfdb_reloc_candidates_device(self._h, int(frame_id), ptr(words), ptr(values), ptr(n),
+                                                           ptr(cand), int(cand.numel()), ptr(n_cand),
+                                                           _stream_ptr(stream, True)),
+              "orbx_kfdb_reloc_candidates_device")
+
+    def loop_candidates_device(self, kf_mnid, words, values, n, connected, minScore, cand, n_cand, stream=None):
+        """DetectLoopCandidates queued on `stream`; connected is a host list of ids."""
+        conn = np.ascontiguousarray(list(connected), np.int64)
+        check(_lib.lib().orbx_kfdb_loop_candidates_device(self._h, int(kf_mnid), ptr(words), ptr(values), ptr(n),
+                                                          ptr(conn), len(conn), float(minScore), ptr(cand),
+                                                          int(cand.numel()), ptr(n_cand), _stream_ptr(stream, True)),
+              "orbx_kfdb_loop_candidates_device")

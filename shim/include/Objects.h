@@ -136,6 +136,18 @@ class KeyFrame {
     std::unique_lock<std::mutex> lock(mMutexConnections);
     return mvpOrderedConnectedKeyFrames;
   }
+  // src/KeyFrame.cc:224-232: the first N of the ordered list (all of it when shorter)
+  std::vector<KeyFrame*> GetBestCovisibilityKeyFrames(const int& N) {
+    std::unique_lock<std::mutex> lock(mMutexConnections);
+    if ((int)mvpOrderedConnectedKeyFrames.size() < N) return mvpOrderedConnectedKeyFrames;
+    return std::vector<KeyFrame*>(mvpOrderedConnectedKeyFrames.begin(), mvpOrderedConnectedKeyFrames.begin() + N);
+  }
+  // src/KeyFrame.cc:198-205: every connected keyframe (the keys of mConnectedKeyFrameWeights, which
+  // the ordered list holds too)
+  std::set<KeyFrame*> GetConnectedKeyFrames() {
+    std::unique_lock<std::mutex> lock(mMutexConnections);
+    return std::set<KeyFrame*>(mvpOrderedConnectedKeyFrames.begin(), mvpOrderedConnectedKeyFrames.end());
+  }
   void EraseMapPointMatch(const size_t& idx) {  // include/KeyFrame.h:103
     std::unique_lock<std::mutex> lock(mMutexFeatures);
     mvpMapPoints[idx] = nullptr;
@@ -179,6 +191,14 @@ class KeyFrame {
 
   long unsigned int mnId = 0;
   long unsigned int mnBALocalForKF = 0, mnBAFixedForKF = 0;
+  // written by KeyFrameDatabase (include/KeyFrame.h:181-194); the two scores are uninitialised in the
+  // reference and start at 0 here, as on the device
+  long unsigned int mnLoopQuery = 0;
+  int mnLoopWords = 0;
+  float mLoopScore = 0.f;
+  long unsigned int mnRelocQuery = 0;
+  int mnRelocWords = 0;
+  float mRelocScore = 0.f;
   float fx = 0, fy = 0, cx = 0, cy = 0, invfx = 0, invfy = 0, mbf = 0, mb = 0, mThDepth = 0;
   int N = 0;
   std::vector<cv::KeyPoint> mvKeys, mvKeysUn;

@@ -24,6 +24,7 @@
 #include <set>
 #include <sstream>
 
+#include "KeyFrameDatabase.h"
 #include "ORBVocabulary.h"
 #include "ORBextractor.h"
 #include "ORBmatcher.h"
@@ -1037,10 +1038,158 @@ void MapPoint::ComputeDistinctiveDescriptors() {
 }
 
 ORBVocabulary::~ORBVocabulary() {
+  if (mpScoreDb) orbx_kfdb_destroy(mpScoreDb);
   if (mpGpu) orbx_voc_destroy(mpGpu);
 }
 
+namespace {
+void bow_arrays(const DBoW2::BowVector& v, std::vector<uint32_t>& words, std::vector<double>& values) {
+  words.clear();
+  values.clear();
+  words.reserve(v.size());
+  values.reserve(v.size());
+  for (const auto& e : v) {  // std::map: ascending word ids
+    words.push_back(e.first);
+    values.push_back(e.second);
+  }
+}
+}  // namespace
+
+double ORBVocabulary::score(const DBoW2::BowVector& v1, const DBoW2::BowVector& v2) const {
+  if (!mpGpu) throw std::runtime_error("ORBVocabulary::score: no vocabulary loaded");
+  std::unique_lock<std::mutex> lock(mMutexScore);
+  if (!mpScoreDb) check(orbx_kfdb_create(mpGpu, gOrbxDevice, &mpScoreDb), "orbx_kfdb_create");
+  std::vector<uint32_t> w1, w2;
+  std::vector<double> x1, x2;
+  bow_arrays(v1, w1, x1);
+  bow_arrays(v2, w2, x2);
+  const int64_t id = 0;
+  double s = 0.0;
+  check(orbx_kfdb_add(mpScoreDb, id, w2.data(), x2.data(), (int)w2.size()), "orbx_kfdb_add");
+  const orbx_status st = orbx_kfdb_score(mpScoreDb, w1.data(), x1.data(), (int)w1.size(), &id, 1, &s);
+  check(orbx_kfdb_erase(mpScoreDb, id), "orbx_kfdb_erase");
+  check(st, "orbx_kfdb_score");
+  return s;
+}
+
+// ------------------------------------------------------------------ KeyFrameDatabase
+KeyFrameDatabase::KeyFrameDatabase(const ORBVocabulary& voc) : mpVoc(&voc) {
+  check(orbx_kfdb_create(voc.gpu(), gOrbxDevice, &mpGpu), "orbx_kfdb_create");
+}
+
+KeyFrameDatabase::~KeyFrameDatabase() {
+  if (mpGpu) orbx_kfdb_destroy(mpGpu);
+}
+
+void KeyFrameDatabase::add(KeyFrame* pKF) {
+  std::unique_lock<std::mutex> lock(mMutex);
+  std::vector<uint32_t> w;
+  std::vector<double> x;
+  bow_arrays(pKF->mBowVec, w, x);
+  check(orbx_kfdb_add(mpGpu, (int64_t)pKF->mnId, w.data(), x.data(), (int)w.size()), "orbx_kfdb_add");
+  mKeyFrames[pKF->mnId] = pKF;
+}
+
+void KeyFrameDatabase::erase(KeyFrame* pKF) {
+  std::unique_lock<std::mutex> lock(mMutex);
+  check(orbx_kfdb_erase(mpGpu, (int64_t)pKF->mnId), "orbx_kfdb_erase");
+  mKeyFrames.erase(pKF->mnId);
+}
+
+void KeyFrameDatabase::clear() {
+  std::unique_lock<std::mutex> lock(mMutex);
+  check(orbx_kfdb_clear(mpGpu), "orbx_kfdb_clear");
+  mKeyFrames.clear();
+}
+
+void KeyFrameDatabase::UploadNeighbours() {
+  const size_t n = mKeyFrames.size();
+  std::vector<int64_t> ids(n), best(10 * n, 0);
+  std::vector<int32_t> nb(n);
+  size_t i = 0;
+  for (const auto& e : mKeyFrames) {
+    ids[i] = (int64_t)e.first;
+    const std::vector<KeyFrame*> vpNeighs = e.second->GetBestCovisibilityKeyFrames(10);
+    nb[i] = (int32_t)vpNeighs.size();
+    for (size_t j = 0; j < vpNeighs.size(); j++) best[10 * i + j] = (int64_t)vpNeighs[j]->mnId;
+    i++;
+  }
+  check(orbx_kfdb_set_neighbours(mpGpu, ids.data(), best.data(), nb.data(), (int)n), "orbx_kfdb_set_neighbours");
+}
+
+void KeyFrameDatabase::WriteBackState() {
+  const size_t n = mKeyFrames.size();
+  if (!n) return;
+  std::vector<int64_t> ids(n);
+  std::vector<uint64_t> rq(n), lq(n);
+  std::vector<int32_t> rw(n), lw(n);
+  std::vector<float> rs(n), ls(n);
+  size_t i = 0;
+  for (const auto& e : mKeyFrames) ids[i++] = (int64_t)e.first;
+  check(orbx_kfdb_read_state(mpGpu, ids.data(), (int)n, rq.data(), rw.data(), rs.data(), lq.data(), lw.data(),
+                             ls.data()),
+        "orbx_kfdb_read_state");
+  i = 0;
+  for (const auto& e : mKeyFrames) {
+    KeyFrame* pKF = e.second;
+    pKF->mnRelocQuery = rq[i];
+    pKF->mnRelocWords = rw[i];
+    pKF->mRelocScore = rs[i];
+    pKF->mnLoopQuery = lq[i];
+    pKF->mnLoopWords = lw[i];
+    pKF->mLoopScore = ls[i];
+    i++;
+  }
+}
+
+std::vector<KeyFrame*> KeyFrameDatabase::ToKeyFrames(const std::vector<int64_t>& ids) const {
+  std::vector<KeyFrame*> out;
+  out.reserve(ids.size());
+  for (int64_t id : ids) out.push_back(mKeyFrames.at((long unsigned int)id));
+  return out;
+}
+
+std::vector<KeyFrame*> KeyFrameDatabase::DetectRelocalizationCandidates(Frame* F) {
+  std::unique_lock<std::mutex> lock(mMutex);
+  UploadNeighbours();
+  std::vector<uint32_t> w;
+  std::vector<double> x;
+  bow_arrays(F->mBowVec, w, x);
+  std::vector<int64_t> cand(std::max<size_t>(mKeyFrames.size(), 1));
+  int n = 0;
+  check(orbx_kfdb_reloc_candidates(mpGpu, (uint64_t)F->mnId, w.data(), x.data(), (int)w.size(), cand.data(),
+                                   (int)cand.size(), &n),
+        "orbx_kfdb_reloc_candidates");
+  cand.resize(n);
+  WriteBackState();
+  return ToKeyFrames(cand);
+}
+
+std::vector<KeyFrame*> KeyFrameDatabase::DetectLoopCandidates(KeyFrame* pKF, float minScore) {
+  const std::set<KeyFrame*> spConnectedKeyFrames = pKF->GetConnectedKeyFrames();
+  std::unique_lock<std::mutex> lock(mMutex);
+  UploadNeighbours();
+  std::vector<int64_t> conn;
+  conn.reserve(spConnectedKeyFrames.size());
+  for (KeyFrame* c : spConnectedKeyFrames) conn.push_back((int64_t)c->mnId);
+  std::vector<uint32_t> w;
+  std::vector<double> x;
+  bow_arrays(pKF->mBowVec, w, x);
+  std::vector<int64_t> cand(std::max<size_t>(mKeyFrames.size(), 1));
+  int n = 0;
+  check(orbx_kfdb_loop_candidates(mpGpu, (uint64_t)pKF->mnId, w.data(), x.data(), (int)w.size(), conn.data(),
+                                  (int)conn.size(), minScore, cand.data(), (int)cand.size(), &n),
+        "orbx_kfdb_loop_candidates");
+  cand.resize(n);
+  WriteBackState();
+  return ToKeyFrames(cand);
+}
+
 bool ORBVocabulary::loadFromText(const std::string& text) {
+  if (mpScoreDb) {
+    orbx_kfdb_destroy(mpScoreDb);
+    mpScoreDb = nullptr;
+  }
   if (mpGpu) {
     orbx_voc_destroy(mpGpu);
     mpGpu = nullptr;

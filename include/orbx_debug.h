@@ -23,6 +23,29 @@ enum {
 /* Returns the number of bytes the item occupies (copies min(cap, size)); <0 on error. */
 long long orbx_debug_copy(orbx_extractor* h, int what, int image, int arg, void* dst, size_t cap);
 
+/* k_resize's launch descriptors and the block-remap constants for one image geometry, built on the
+ * host exactly as an extractor handle builds them (no device is needed or touched).  Every item is a list of
+ * int64 words; table pointers are reported as element offsets into their tables.  Returns the
+ * number of words of the item (copies min(cap, words) of them to dst, which may be NULL); <0 on
+ * error (ORBX_ERR_ARG, or the plan's ORBX_ERR_SIZE). */
+enum {
+  ORBX_LP_LEVELS = 1,     /* x8 per level: w, h, pyramid off, blurred off, bstride, tile_begin, tiles_x, tiles_y */
+  ORBX_LP_RESIZE = 2,     /* x16 per level >= 1 (k_resize): sw, sh, dw, dh, src_off (-1: the input image),
+                             dst_off, pyr_bytes, xtab_off, ytab_off, bx_off, by_off, stride, rows, lc,
+                             tile columns, tile rows */
+  ORBX_LP_BOUNDS = 3,     /* x2 per entry of the footprint-bound table bx_off / by_off index:
+                             (sx0 of a tile column's first, sx1 of its last output column), resp. (sy0, sy1) */
+  ORBX_LP_GRIDS = 4,      /* x3 per launch: the grids (gx, gy, gz) of k_resize for levels 1.. and of k_blur for a
+                             batch of a0 images */
+  ORBX_LP_REMAP = 5,      /* x8, the division-free block remap of a gx=a0, gy=a1, gz=a2 grid:
+                             gx, gy, total >> 3, total & 7, magic x, shift x, magic y, shift y;
+                             l / g == (((2l + 1) * magic) >> 32) >> shift for every l < gx*gy*gz */
+  ORBX_LP_XTAB = 6,       /* x4 per output column of level a0 >= 1: sx0, sx1, a0, a1 (the resize coefficients) */
+  ORBX_LP_YTAB = 7        /* x4 per output row of level a0 >= 1: sy0, sy1, b0, b1 */
+};
+long long orbx_debug_launch_plan(const orbx_extractor_params* params, int width, int height, int what, int a0,
+                                 int a1, int a2, long long* dst, size_t cap);
+
 /* Solve S x = b (N x N, N a multiple of 6) with the LocalBA reduced-system
  * LDLT kernel; *ms = mean kernel time over reps launches.  ORBX_ERR_STATE on
  * a zero pivot. */

@@ -266,6 +266,8 @@ SIGNATURES = {
                            C.POINTER(C.c_char_p)], C.c_int),
     # include/orbx_debug.h
     "orbx_debug_copy": ([P, C.c_int, C.c_int, C.c_int, P, C.c_size_t], C.c_longlong),
+    "orbx_debug_launch_plan": ([C.POINTER(ExtractorParams), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P,
+                                C.c_size_t], C.c_longlong),
     "orbx_debug_ldlt": ([P, P, C.c_int, P, C.c_int, C.POINTER(C.c_float)], C.c_int),
     "orbx_debug_ldlt_ex": ([P, P, C.c_int, P, C.c_int, C.POINTER(C.c_float), C.c_int, P], C.c_int),
     "orbx_debug_ba_options": ([P, C.POINTER(BaDebugOptions)], C.c_int),

@@ -30,9 +30,8 @@ hipError_t upload_constants(const int* umax16, const int* gauss7);
 hipError_t launch_blur(const Geometry& Gh, const Geometry* Gd, const int* tile_level, const BatchPtrs& B, int n_img,
                        hipStream_t st);
 hipError_t launch_extract_stages(const Geometry& Gh, const Geometry* Gd, const CellInfo* cells, const int* tile_level,
-                                 const ResizeX* xt, const ResizeY* yt, const BatchPtrs& B, int n_img,
-                                 orbx_keypoint* kps, uint8_t* desc, int32_t* counts, int kp_cap, hipStream_t st,
-                                 StageTimer* T);
+                                 const LaunchPlan& LP, const BatchPtrs& B, int n_img, orbx_keypoint* kps, uint8_t* desc, int32_t* counts,
+                                 int kp_cap, hipStream_t st, StageTimer* T);
 size_t octree_smem_host(int NC, int cell_cap, int kcap);
 hipError_t octree_set_smem_limit(size_t bytes);
 }  // namespace orbx
@@ -132,12 +131,41 @@ struct Plan {
   std::vector<int> tile_level;
   std::vector<ResizeX> xt;
   std::vector<ResizeY> yt;
+  std::vector<int2> rzb;  // k_resize footprint bounds: per level its tile columns, then its tile rows
+  int rzb_x[kMaxLevelsPlan] = {}, rzb_y[kMaxLevelsPlan] = {};  // where a level's two runs start in rzb
+  LaunchPlan LP{};  // k_resize's by-value descriptors, pointing into the device tables below
   DevBuf<Geometry> dG;
   DevBuf<CellInfo> dcells;
   DevBuf<int> dtiles;
   DevBuf<ResizeX> dxt;
   DevBuf<ResizeY> dyt;
+  DevBuf<int2> drzb;
 };
+
+// k_resize's launch descriptors of a built plan over the given table bases (the device copies in
+// use; the host vectors themselves for orbx_debug_launch_plan).  rm is left for the launch.
+void build_launch_plan(const Plan& P, const ResizeX* xt, const ResizeY* yt, const int2* rzb, LaunchPlan& LP) {
+  const Geometry& G = P.G;
+  LP = LaunchPlan{};
+  for (int l = 1; l < G.nlevels; l++) {
+    const LevelGeom &L = G.lv[l], &S = G.lv[l - 1];
+    ResizeDesc& D = LP.rz[l];
+    D.sw = S.w;
+    D.sh = S.h;
+    D.dw = L.w;
+    D.dh = L.h;
+    D.src_off = l == 1 ? -1 : S.off;
+    D.dst_off = L.off;
+    D.pyr_bytes = G.pyr_bytes;
+    D.X = xt + L.xtab_off;
+    D.Y = yt + L.ytab_off;
+    D.bx = rzb + P.rzb_x[l];
+    D.by = rzb + P.rzb_y[l];
+    D.stride = G.rz_stride;
+    D.rows = G.rz_rows;
+    D.lc = G.rz_lc;
+  }
+}
 
 // Builds the per-geometry plan.  Level sizes: ComputePyramid
 // (src/ORBextractor.cc:1219-1221); FAST cells: ComputeKeyPointsOctTree
@@ -158,6 +186,7 @@ orbx_status build_plan(const orbx_extractor_params& p, const Tables& t, int W, i
   P.tile_level.clear();
   P.xt.clear();
   P.yt.clear();
+  P.rzb.clear();
   for (int l = 0; l < p.nlevels; l++) {
     LevelGeom& L = G.lv[l];
     L.w = round_even((float)W * t.inv_scale[l]);
@@ -328,15 +357,20 @@ orbx_status build_plan(const orbx_extractor_params& p, const Tables& t, int W, i
   // k_resize staging bound: source footprint of every 128x16 output tile
   G.rz_rows = 1;
   G.rz_stride = 16;
+  // (the same bounds go into rzb, where a block finds its footprint without walking the tables)
   for (int l = 1; l < G.nlevels; l++) {
     const LevelGeom& L = G.lv[l];
-    for (int oy = 0; oy < L.h; oy += kRzTH) {
-      const int rows = P.yt[L.ytab_off + std::min(oy + kRzTH, L.h) - 1].sy1 - P.yt[L.ytab_off + oy].sy0 + 1;
-      G.rz_rows = std::max(G.rz_rows, rows);
-    }
+    P.rzb_x[l] = (int)P.rzb.size();
     for (int ox = 0; ox < L.w; ox += kRzTW) {
-      const int span = P.xt[L.xtab_off + std::min(ox + kRzTW, L.w) - 1].sx1 - P.xt[L.xtab_off + ox].sx0 + 1;
-      G.rz_stride = std::max(G.rz_stride, (span + 15) / 16 * 16);
+      const int sx0 = P.xt[L.xtab_off + ox].sx0, sx1 = P.xt[L.xtab_off + std::min(ox + kRzTW, L.w) - 1].sx1;
+      P.rzb.push_back(make_int2(sx0, sx1));
+      G.rz_stride = std::max(G.rz_stride, (sx1 - sx0 + 1 + 15) / 16 * 16);
+    }
+    P.rzb_y[l] = (int)P.rzb.size();
+    for (int oy = 0; oy < L.h; oy += kRzTH) {
+      const int sy0 = P.yt[L.ytab_off + oy].sy0, sy1 = P.yt[L.ytab_off + std::min(oy + kRzTH, L.h) - 1].sy1;
+      P.rzb.push_back(make_int2(sy0, sy1));
+      G.rz_rows = std::max(G.rz_rows, sy1 - sy0 + 1);
     }
   }
   if (G.rz_rows > kRzMaxRows || (size_t)G.rz_rows * (G.rz_stride + 2 * kRzTW) > 64 * 1024) return ORBX_ERR_SIZE;
@@ -513,16 +547,20 @@ orbx_status get_plan(orbx_extractor* h, int W, int H, Plan** out) {
   if ((e = P->dtiles.ensure(P->tile_level.size())) != hipSuccess) return ORBX_ERR_HIP;
   if ((e = P->dxt.ensure(P->xt.size())) != hipSuccess) return ORBX_ERR_HIP;
   if ((e = P->dyt.ensure(P->yt.size())) != hipSuccess) return ORBX_ERR_HIP;
+  if ((e = P->drzb.ensure(P->rzb.size())) != hipSuccess) return ORBX_ERR_HIP;
   e = hipMemcpy(P->dG.p, &P->G, sizeof(Geometry), hipMemcpyHostToDevice);
   if (e == hipSuccess && !P->cells.empty())
     e = hipMemcpy(P->dcells.p, P->cells.data(), P->cells.size() * sizeof(CellInfo), hipMemcpyHostToDevice);
   if (e == hipSuccess && !P->tile_level.empty())
     e = hipMemcpy(P->dtiles.p, P->tile_level.data(), P->tile_level.size() * sizeof(int), hipMemcpyHostToDevice);
+  if (e == hipSuccess && !P->rzb.empty())
+    e = hipMemcpy(P->drzb.p, P->rzb.data(), P->rzb.size() * sizeof(int2), hipMemcpyHostToDevice);
   if (e == hipSuccess && !P->xt.empty())
     e = hipMemcpy(P->dxt.p, P->xt.data(), P->xt.size() * sizeof(ResizeX), hipMemcpyHostToDevice);
   if (e == hipSuccess && !P->yt.empty())
     e = hipMemcpy(P->dyt.p, P->yt.data(), P->yt.size() * sizeof(ResizeY), hipMemcpyHostToDevice);
   if (e != hipSuccess) return ORBX_ERR_HIP;
+  build_launch_plan(*P, P->dxt.p, P->dyt.p, P->drzb.p, P->LP);
   {
     size_t mx = 0;
     for (int g = 0; g < P->G.n_og; g++)
@@ -572,8 +610,8 @@ orbx_status run_extract(orbx_extractor* h, Plan* P, int n, const uint8_t* d_in, 
   orbx_status s = ensure_batch(h, *P, n);
   if (s != ORBX_OK) return s;
   BatchPtrs B = batch_ptrs(h, d_in, pitch);
-  hipError_t e = launch_extract_stages(P->G, P->dG.p, P->dcells.p, P->dtiles.p, P->dxt.p, P->dyt.p, B, n, d_kps,
-                                       d_desc, d_counts, kp_cap, st, &h->timer);
+  hipError_t e = launch_extract_stages(P->G, P->dG.p, P->dcells.p, P->dtiles.p, P->LP, B, n, d_kps, d_desc, d_counts, kp_cap, st,
+                                       &h->timer);
   if (e != hipSuccess) return ORBX_ERR_HIP;
   h->last_plan = P;
   h->last_in = d_in;
@@ -1217,6 +1255,73 @@ extern "C" long long orbx_debug_copy(orbx_extractor* h, int what, int image, int
     if (hipMemcpy(dst, src, std::min(bytes, cap), hipMemcpyDeviceToHost) != hipSuccess) return ORBX_ERR_HIP;
   }
   return (long long)bytes;
+}
+
+extern "C" long long orbx_debug_launch_plan(const orbx_extractor_params* params, int width, int height, int what,
+                                            int a0, int a1, int a2, long long* dst, size_t cap) {
+  std::vector<long long> out;
+  auto done = [&]() {
+    if (dst) std::memcpy(dst, out.data(), std::min(out.size(), cap) * sizeof(long long));
+    return (long long)out.size();
+  };
+  if (what == ORBX_LP_REMAP) {
+    XcdRemap R{};
+    if (a0 < 1 || a1 < 1 || a2 < 1 || !make_xcd_remap((unsigned)a0, (unsigned)a1, (unsigned)a2, &R)) return ORBX_ERR_ARG;
+    out = {R.gx, R.gy, R.q, R.r, R.mx, R.sx, R.my, R.sy};
+    return done();
+  }
+  if (!params_ok(params) || width <= 0 || height <= 0) return ORBX_ERR_ARG;
+  Plan P;
+  const orbx_status s = build_plan(*params, make_tables(*params), width, height, P);
+  if (s != ORBX_OK) return s;
+  // the descriptors over the host tables: a pointer's element offset is its distance from the base
+  build_launch_plan(P, P.xt.data(), P.yt.data(), P.rzb.data(), P.LP);
+  const Geometry& G = P.G;
+  switch (what) {
+    case ORBX_LP_LEVELS:
+      for (int l = 0; l < G.nlevels; l++) {
+        const LevelGeom& L = G.lv[l];
+        out.insert(out.end(), {L.w, L.h, L.off, L.boff, L.bstride, L.tile_begin, L.tiles_x, L.tiles_y});
+      }
+      break;
+    case ORBX_LP_RESIZE:
+      for (int l = 1; l < G.nlevels; l++) {
+        const ResizeDesc& D = P.LP.rz[l];
+        out.insert(out.end(), {D.sw, D.sh, D.dw, D.dh, D.src_off, D.dst_off, D.pyr_bytes, D.X - P.xt.data(),
+                               D.Y - P.yt.data(), D.bx - P.rzb.data(), D.by - P.rzb.data(), D.stride, D.rows, D.lc,
+                               (D.dw + kRzTW - 1) / kRzTW, (D.dh + kRzTH - 1) / kRzTH});
+      }
+      break;
+    case ORBX_LP_BOUNDS:
+      for (const int2& b : P.rzb) out.insert(out.end(), {b.x, b.y});
+      break;
+    case ORBX_LP_GRIDS: {
+      if (a0 < 1) return ORBX_ERR_ARG;
+      for (int l = 1; l < G.nlevels; l++)
+        out.insert(out.end(), {(G.lv[l].w + kRzTW - 1) / kRzTW, (G.lv[l].h + kRzTH - 1) / kRzTH, a0});
+      out.insert(out.end(), {G.ntiles, a0, 1});
+      break;
+    }
+    case ORBX_LP_XTAB:
+    case ORBX_LP_YTAB: {
+      if (a0 < 1 || a0 >= G.nlevels) return ORBX_ERR_ARG;
+      const LevelGeom& L = G.lv[a0];
+      if (what == ORBX_LP_XTAB)
+        for (int i = 0; i < L.w; i++) {
+          const ResizeX& X = P.xt[L.xtab_off + i];
+          out.insert(out.end(), {X.sx0, X.sx1, X.a0, X.a1});
+        }
+      else
+        for (int i = 0; i < L.h; i++) {
+          const ResizeY& Y = P.yt[L.ytab_off + i];
+          out.insert(out.end(), {Y.sy0, Y.sy1, Y.b0, Y.b1});
+        }
+      break;
+    }
+    default:
+      return ORBX_ERR_ARG;
+  }
+  return done();
 }
 
 // On-box HBM reference for the roofline: a streaming device-to-device copy,

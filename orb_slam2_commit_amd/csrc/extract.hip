@@ -160,24 +160,30 @@ __device__ __forceinline__ void window_to_lds(const uint8_t* base, size_t stride
 //   3. the vertical pass for 4 output columns per item:
 //      ((b0*h0)>>16 + (b1*h1)>>16 + 2) >> 2 with v_mul_hi_u32_u24(b<<8, h<<8), packed
 //      into one dword store.
-__global__ __launch_bounds__(BS) void k_resize(const Geometry* __restrict__ G, const ResizeX* __restrict__ xt,
-                                               const ResizeY* __restrict__ yt, BatchPtrs B, int l) {
+//
+// Everything block-uniform comes in the by-value ResizeDesc; the only scalar loads ahead of the
+// footprint loads are the tile's two bound pairs (D.bx, D.by), issued together.
+__global__ __launch_bounds__(BS) void k_resize(ResizeDesc D, const uint8_t* __restrict__ in, size_t in_pitch,
+                                               uint8_t* __restrict__ pyr) {
   extern __shared__ __align__(16) uint8_t rz_smem[];
-  const LevelGeom& L = G->lv[l];
-  const LevelGeom& S = G->lv[l - 1];
-  const int3 bi = xcd_block3();
+  const int3 bi = xcd_block3(D.rm);
   const int img = bi.z, tid = threadIdx.x;
+  const int2 fx = D.bx[bi.x], fy = D.by[bi.y];
   const int ox0 = bi.x * kRzTW, oy0 = bi.y * kRzTH;
-  const int nx = min(kRzTW, L.w - ox0), ny = min(kRzTH, L.h - oy0);
-  const ResizeX* X = xt + L.xtab_off + ox0;
-  const ResizeY* Y = yt + L.ytab_off + oy0;
-  const int cx0 = X[0].sx0, span = X[nx - 1].sx1 - cx0 + 1;
-  const int ry0 = Y[0].sy0, nrows = Y[ny - 1].sy1 - ry0 + 1;
-  const int stride = G->rz_stride;
+  const int nx = min(kRzTW, D.dw - ox0), ny = min(kRzTH, D.dh - oy0);
+  const ResizeX* X = D.X + ox0;
+  const ResizeY* Y = D.Y + oy0;
+  const int cx0 = fx.x, span = fx.y - cx0 + 1;
+  const int ry0 = fy.x, nrows = fy.y - ry0 + 1;
+  const int stride = D.stride;
   uint8_t* tin = rz_smem;
-  int16_t* hb = (int16_t*)(rz_smem + G->rz_rows * stride);  // [rows][kRzTW]
-  const uint8_t* src = level_ptr(*G, B, img, l - 1);
-  const int swh = S.w * S.h;
+  int16_t* hb = (int16_t*)(rz_smem + D.rows * stride);  // [rows][kRzTW]
+  // (both candidates computed, then selected: as a branch each arm would fetch its kernel arguments
+  // itself, one more serial wait)
+  const uint8_t* const src0 = in + (size_t)img * in_pitch;
+  const uint8_t* const srcl = pyr + (size_t)img * D.pyr_bytes + D.src_off;
+  const uint8_t* src = D.src_off < 0 ? src0 : srcl;
+  const int swh = D.sw * D.sh;
   // the coefficient entries this thread needs later load first, beside the footprint: every
   // global load of the block is then in flight before the first wait (they used to trail the
   // barriers, one round trip each)
@@ -195,14 +201,14 @@ __global__ __launch_bounds__(BS) void k_resize(const Geometry* __restrict__ G, c
   {
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)src, (short)0, swh, 0x00020000);
     const int nch = (span + 15) >> 4;
-    const int lc = G->rz_lc;  // log2(chunk lanes per row)
+    const int lc = D.lc;  // log2(chunk lanes per row)
     const int c = tid & ((1 << lc) - 1), r0 = tid >> lc, rstep = BS >> lc;
     constexpr int kRzLd = (kRzMaxRows + 15) / 16;  // >= rows per thread when >= 16 rows per step
     uint4 v[kRzLd];
 #pragma unroll
     for (int u = 0; u < kRzLd; u++) {
       const int r = r0 + u * rstep;
-      const int o = (ry0 + r) * S.w + cx0 + 16 * c;
+      const int o = (ry0 + r) * D.sw + cx0 + 16 * c;
       v[u] = make_uint4(0, 0, 0, 0);
       if (r < nrows && c < nch) {
         if (o + 16 <= swh) {
@@ -236,7 +242,7 @@ __global__ __launch_bounds__(BS) void k_resize(const Geometry* __restrict__ G, c
   __syncthreads();
   // 3. vertical pass: item = (output row, group of 4 columns)
   const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(B.pyr + (size_t)img * G->pyr_bytes + L.off), (short)0, L.w * L.h, 0x00020000);
+      (void*)(pyr + (size_t)img * D.pyr_bytes + D.dst_off), (short)0, D.dw * D.dh, 0x00020000);
 #pragma unroll
   for (int k = 0; k < kVIt; k++) {
     const int it = tid + k * BS;
@@ -263,7 +269,7 @@ __global__ __launch_bounds__(BS) void k_resize(const Geometry* __restrict__ G, c
       const uint32_t v = (mulhi24(B0, h0[j]) + mulhi24(B1, h1[j]) + 2) >> 2;
       packed |= v << (8 * j);
     }
-    const int o = (oy0 + i) * L.w + ox0 + 4 * g;
+    const int o = (oy0 + i) * D.dw + ox0 + 4 * g;
     if (4 * g + 4 <= nx) {
       __builtin_amdgcn_raw_buffer_store_b32(packed, rd, o, 0, 0);
     } else {
@@ -299,7 +305,8 @@ __device__ __forceinline__ int reflect101(int p, int n) {
 // kernel is VALU-issue-bound).  A strip's 16 packed output dwords stay in
 // registers until the whole tile is done, then go through the (no longer
 // needed) input tile in LDS in the tiled blurred-level order (8x16-B tiles)
-// and out as whole 128-B tiles of b128 stores.  7 waves per SIMD: 68 VGPRs,
+// (chunks swizzled so that neither side has a bank conflict, see the write-out)
+// and out as whole 128-B tiles of b128 stores.  7 waves per SIMD: 72 VGPRs,
 // no scratch (8 spills 12 B per lane for the same time, profiles/r04/ab_blur_tiled.txt).
 constexpr int kBIn = kBlurTileW + 16;  // input tile row stride (bytes, 16-B multiple)
 constexpr int kBStrip = 16;            // output rows per thread
@@ -307,10 +314,10 @@ constexpr int kBStrip = 16;            // output rows per thread
 #define ORBX_BLUR_WPE 7
 #endif
 __global__ __launch_bounds__(BS, ORBX_BLUR_WPE) void k_blur(const Geometry* __restrict__ G, const int* __restrict__ tile_level,
-                                             BatchPtrs B) {
+                                                            BatchPtrs B, XcdRemap R) {
   constexpr int TR = kBlurTileH + 6;
   __shared__ __align__(16) uint8_t tin[(TR + 1) * kBIn];
-  const int2 bi = xcd_block2();
+  const int2 bi = xcd_block2(R);
   const int tile = bi.x, img = bi.y, tid = threadIdx.x;
   const int l = tile_level[tile];
   const LevelGeom& L = G->lv[l];
@@ -475,13 +482,29 @@ __global__ __launch_bounds__(BS, ORBX_BLUR_WPE) void k_blur(const Geometry* __re
   // gathers from): the outputs go to LDS (the input tile is no longer read) in tile order, then
   // leave as whole 128-B lines, 16 B per lane: the block's 128 x 128 outputs are 16 tile rows of
   // 8 consecutive tiles (1 KB each).  Columns past w and rows past h land in the level's padding.
+  //
+  // LDS staging layout: 16-B chunk q = tile * 8 + row (tile = (yr >> 3) * 8 + tc, tc = g >> 2 the
+  // tile column, row = yr & 7) sits at chunk  q ^ tc  = tile * 8 + (row ^ tc), not at q.  Why:
+  //  - ds_write_b32 is served in 2 groups of 32 lanes, bank = dword address mod 32.  A group is one
+  //    output row yr with g = 0..31, dword g & 3 of chunk (.. + tc) * 8 + row.  Unswizzled, all 8 tile
+  //    columns land on the 4 banks row * 4 .. + 3 (8 addresses per bank: 16 LDS cycles instead of
+  //    4, SQ_LDS_BANK_CONFLICT 177 per wave).  With row ^ tc the 8 tile columns take 8 different
+  //    chunks mod 8, so the 32 lanes cover all 32 banks once.
+  //  - ds_read_b128 is served in 4 groups of 16 lanes ({0-3,12-15,20-27}, {4-11,16-19,28-31} and the
+  //    same + 32), bank = dword address mod 64, i.e. chunk mod 16.  Lane = 8 * tl + row reads chunk
+  //    (tile << 3) | (row ^ tl) with tile & 7 = tl, so chunk mod 16 = (tl & 1) << 3 | (row ^ tl):
+  //    lanes 0-3 -> 0-3, 12-15 -> 12-15, 20-23 -> 4-7, 24-27 -> 8-11; lanes 4-7 -> 4-7, 8-11 ->
+  //    8-11, 16-19 -> 0-3, 28-31 -> 12-15; the upper half likewise (tl ^ 4 permutes the low two
+  //    bits' quads).  Every group covers the 16 chunk positions once, as the linear layout did.
+  // The swizzle permutes chunks inside a tile only; the staging area keeps its size.
   __syncthreads();
   if (active) {
+    // byte address of (row 0, this thread's dword): bits 4-6 hold the chunk, xor-ed per row below
+    const int tc = g >> 2;
+    const int a0 = ((ys >> 3) * (kBlurTileW / 16) + tc) * 128 + (tc & 7) * 16 + (g & 3) * 4;
 #pragma unroll
-    for (int r = 0; r < kBStrip; r++) {
-      const int yr = ys + r, c = 4 * g;
-      *(uint32_t*)&tin[((yr >> 3) * (kBlurTileW / 16) + (c >> 4)) * 128 + (yr & 7) * 16 + (c & 15)] = outv[r];
-    }
+    for (int r = 0; r < kBStrip; r++)
+      *(uint32_t*)&tin[(a0 ^ ((r & 7) * 16)) + (r >> 3) * (kBlurTileW / 16) * 128] = outv[r];
   }
   __syncthreads();
   {
@@ -494,7 +517,7 @@ __global__ __launch_bounds__(BS, ORBX_BLUR_WPE) void k_blur(const Geometry* __re
     for (int k = 0; k < kChunks / BS; k++) {
       const int q = tid + k * BS, t = q >> 3, tr = t / (kBlurTileW / 16), tc = t - tr * (kBlurTileW / 16);
       typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-      const u32x4 v = *(const u32x4*)&tin[q * 16];
+      const u32x4 v = *(const u32x4*)&tin[(q ^ (tc & 7)) * 16];  // the staging swizzle, undone
       if (tx0 + tc < ntx && ty0 + tr < nty)
         __builtin_amdgcn_raw_buffer_store_b128(v, rd, (uint32_t)(((ty0 + tr) * ntx + tx0 + tc) * 128 + (q & 7) * 16), 0, 0);
     }
@@ -616,14 +639,14 @@ __device__ unsigned int* fast_probe_buf;
 constexpr int kFastCPW = ORBX_FAST_CPW;  // FAST cells per wave
 template <int S, int RP>
 __global__ __launch_bounds__(64) void k_fast(const Geometry* __restrict__ G, const CellInfo* __restrict__ cells,
-                                             BatchPtrs B, int grp) {
+                                             BatchPtrs B, int grp, XcdRemap R) {
   // dynamic LDS sized by the launch group's largest cell (G->fg[grp])
   extern __shared__ __align__(16) uint8_t fast_smem[];
   const int tile_bytes = G->fg[grp].tile_bytes, map_bytes = G->fg[grp].map_bytes;
   uint8_t* tile = fast_smem;
   uint8_t* smap = fast_smem + tile_bytes;
   uint16_t* list = (uint16_t*)(fast_smem + tile_bytes + map_bytes);
-  const int2 bi = xcd_block2();
+  const int2 bi = xcd_block2(R);
   const int img = bi.y, lane = threadIdx.x;
   // 1. window -> registers -> LDS: lane = (row, 16-B chunk); window pixel (r, col) lands at tile[r*S + col]
   constexpr int CPR = (S + 15) / 16, RPI = 64 / CPR;
@@ -1402,9 +1425,9 @@ __device__ __forceinline__ float lane_f(float v, int j) {
 //   5. one coalesced store of the kDescK descriptors (lane = dword) and the keypoint records.
 __global__ __launch_bounds__(BS) void k_describe(const Geometry* __restrict__ G, BatchPtrs B,
                                                  orbx_keypoint* __restrict__ kps, uint8_t* __restrict__ desc,
-                                                 int32_t* __restrict__ counts, int kp_cap) {
+                                                 int32_t* __restrict__ counts, int kp_cap, XcdRemap R) {
   __shared__ __align__(16) uint8_t s_desc[BS / 64][kDescLds];
-  const int2 bi = xcd_block2();
+  const int2 bi = xcd_block2(R);
   const int img = bi.y;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int i0 = __builtin_amdgcn_readfirstlane((bi.x * (BS / 64) + wv) * kDescK);
@@ -1620,14 +1643,42 @@ hipError_t upload_constants(const int* umax16, const int* gauss7) {
   return hipMemcpyToSymbol(HIP_SYMBOL(c_gauss), gauss7, 7 * sizeof(int));
 }
 
-hipError_t launch_extract_stages(const Geometry& Gh, const Geometry* Gd, const CellInfo* cells,
-                                 const int* tile_level, const ResizeX* xt, const ResizeY* yt, const BatchPtrs& B,
-                                 int n_img, orbx_keypoint* kps, uint8_t* desc, int32_t* counts, int kp_cap,
-                                 hipStream_t st, StageTimer* T) {
+// The blurred levels of n_img images (also ORBX_DBG_BLUR_LEVEL, which re-blurs the last batch)
+hipError_t launch_blur(const Geometry& Gh, const Geometry* Gd, const int* tile_level, const BatchPtrs& B, int n_img,
+                       hipStream_t st) {
+  XcdRemap R;
+  if (!make_xcd_remap(Gh.ntiles, n_img, 1, &R)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_blur, dim3(Gh.ntiles, n_img), dim3(BS), 0, st, Gd, tile_level, B, R);
+  return hipGetLastError();
+}
+
+hipError_t launch_extract_stages(const Geometry& Gh, const Geometry* Gd, const CellInfo* cells, const int* tile_level,
+                                 const LaunchPlan& LP, const BatchPtrs& B, int n_img, orbx_keypoint* kps, uint8_t* desc,
+                                 int32_t* counts, int kp_cap, hipStream_t st, StageTimer* T) {
+  // every grid's block-remap constants first (the only launch data that depends on the batch size),
+  // so a grid they cannot serve is refused before any stage timer opens
+  const int nb = (Gh.max_kps + BS / 64 * kDescK - 1) / (BS / 64 * kDescK);  // kDescK keypoints per wave
+  ResizeDesc rz[kMaxLevelsPlan];
+  dim3 rz_grid[kMaxLevelsPlan], fast_grid[2];
+  XcdRemap fast_rm[2], desc_rm;
   for (int l = 1; l < Gh.nlevels; l++) {
-    dim3 grid((Gh.lv[l].w + kRzTW - 1) / kRzTW, (Gh.lv[l].h + kRzTH - 1) / kRzTH, n_img);
+    rz_grid[l] = dim3((Gh.lv[l].w + kRzTW - 1) / kRzTW, (Gh.lv[l].h + kRzTH - 1) / kRzTH, n_img);
+    rz[l] = LP.rz[l];
+    if (!make_xcd_remap(rz_grid[l].x, rz_grid[l].y, rz_grid[l].z, &rz[l].rm)) return hipErrorInvalidValue;
+  }
+  for (int g = 0; g < Gh.n_fg; g++) {
+    const Geometry::FastGroup& F = Gh.fg[g];
+    if (F.c1 <= F.c0) continue;
+    fast_grid[g] = dim3((F.c1 - F.c0 + kFastCPW - 1) / kFastCPW, n_img);
+    if (!make_xcd_remap(fast_grid[g].x, fast_grid[g].y, 1, &fast_rm[g])) return hipErrorInvalidValue;
+  }
+  XcdRemap blur_rm;
+  if (!make_xcd_remap(Gh.ntiles, n_img, 1, &blur_rm) || !make_xcd_remap(max(nb, 1), n_img, 1, &desc_rm))
+    return hipErrorInvalidValue;
+  for (int l = 1; l < Gh.nlevels; l++) {
     T->begin(st);
-    hipLaunchKernelGGL(k_resize, grid, dim3(BS), (size_t)Gh.rz_rows * (Gh.rz_stride + 2 * kRzTW), st, Gd, xt, yt, B, l);
+    hipLaunchKernelGGL(k_resize, rz_grid[l], dim3(BS), (size_t)Gh.rz_rows * (Gh.rz_stride + 2 * kRzTW), st, rz[l], B.in,
+                       B.in_pitch, B.pyr);
     T->end(ST_RESIZE, st);
   }
   if (Gh.ncells > 0) {
@@ -1638,7 +1689,7 @@ hipError_t launch_extract_stages(const Geometry& Gh, const Geometry* Gd, const C
       auto kf = F.s == 40   ? (F.rp == 2 ? k_fast<40, 2> : k_fast<40, 1>)
                 : F.s == 48 ? (F.rp == 2 ? k_fast<48, 2> : k_fast<48, 1>)
                             : k_fast<80, 1>;
-      hipLaunchKernelGGL(kf, dim3((F.c1 - F.c0 + kFastCPW - 1) / kFastCPW, n_img), dim3(64), F.smem, st, Gd, cells, B, g);
+      hipLaunchKernelGGL(kf, fast_grid[g], dim3(64), F.smem, st, Gd, cells, B, g, fast_rm[g]);
     }
     T->end(ST_FAST, st);
   } else {
@@ -1646,7 +1697,7 @@ hipError_t launch_extract_stages(const Geometry& Gh, const Geometry* Gd, const C
   }
   {
     T->begin(st);
-    hipLaunchKernelGGL(k_blur, dim3(Gh.ntiles, n_img), dim3(BS), 0, st, Gd, tile_level, B);
+    hipLaunchKernelGGL(k_blur, dim3(Gh.ntiles, n_img), dim3(BS), 0, st, Gd, tile_level, B, blur_rm);
     T->end(ST_BLUR, st);
   }
   if (Gh.ncells > 0) {
@@ -1664,17 +1715,9 @@ hipError_t launch_extract_stages(const Geometry& Gh, const Geometry* Gd, const C
     }
     T->end(ST_OCTREE, st);
   }
-  const int nb = (Gh.max_kps + BS / 64 * kDescK - 1) / (BS / 64 * kDescK);  // kDescK keypoints per wave
   T->begin(st);
-  hipLaunchKernelGGL(k_describe, dim3(max(nb, 1), n_img), dim3(BS), 0, st, Gd, B, kps, desc, counts, kp_cap);
+  hipLaunchKernelGGL(k_describe, dim3(max(nb, 1), n_img), dim3(BS), 0, st, Gd, B, kps, desc, counts, kp_cap, desc_rm);
   T->end(ST_DESCRIBE, st);
-  return hipGetLastError();
-}
-
-// The blurred levels of n_img images (ORBX_DBG_BLUR_LEVEL; the extraction itself never writes them)
-hipError_t launch_blur(const Geometry& Gh, const Geometry* Gd, const int* tile_level, const BatchPtrs& B, int n_img,
-                       hipStream_t st) {
-  hipLaunchKernelGGL(k_blur, dim3(Gh.ntiles, n_img), dim3(BS), 0, st, Gd, tile_level, B);
   return hipGetLastError();
 }
 

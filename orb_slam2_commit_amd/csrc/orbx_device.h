@@ -42,6 +42,58 @@ __device__ __forceinline__ int3 xcd_block3() {
   return make_int3((int)(l - q * gx), (int)(q - z * gy), (int)z);
 }
 
+// The same two maps without run-time divisions, for kernels short enough that the two
+// v_rcp / v_readfirstlane / s_mul_hi sequences of about 25 instructions each show: the grid's
+// constants come from the host by value (make_xcd_remap, once per launch).
+//   l / d  ==  mulhi(2l + 1, m) >> s   with m = ceil(2^(31+s) / d), e = m*d - 2^(31+s) in [0, d):
+//   (2l+1) m / 2^(32+s) = (2l+1)/(2d) + (2l+1) e / (2d 2^(31+s)); the first term is l/d + 1/(2d),
+//   whose fraction is at most 1 - 1/(2d), so the floor is l / d as long as the second term stays
+//   below 1/(2d), i.e. (2l+1) e < 2^(31+s).  make_xcd_remap takes the smallest s for which that
+//   holds for every l < total with m below 2^32 (d = 1: m = 2^31, s = 0).  Needs total <= 2^30.
+struct XcdRemap {
+  unsigned gx, gy;  // grid x, y (the logical grid is gx * gy * gz blocks, total = q * 8 + r)
+  unsigned q, r;    // total >> 3, total & 7
+  unsigned mx, sx;  // magic and shift of the division by gx
+  unsigned my, sy;  // ... by gy (3-D grids; 2^31, 0 otherwise)
+};
+__host__ __device__ inline bool xcd_magic(unsigned d, unsigned long long total, unsigned* m, unsigned* s) {
+  if (d == 0 || total == 0 || total > (1ull << 30)) return false;
+  for (unsigned sh = 0; sh < 32; sh++) {
+    const unsigned long long p = 1ull << (31 + sh), mm = (p + d - 1) / d;
+    if (mm >> 32) break;
+    if ((2 * total - 1) * (mm * d - p) < p) {
+      *m = (unsigned)mm;
+      *s = sh;
+      return true;
+    }
+  }
+  return false;
+}
+__host__ __device__ inline bool make_xcd_remap(unsigned gx, unsigned gy, unsigned gz, XcdRemap* R) {
+  const unsigned long long total = (unsigned long long)gx * gy * gz;
+  if (!xcd_magic(gx, total, &R->mx, &R->sx) || !xcd_magic(gy, total, &R->my, &R->sy)) return false;
+  R->gx = gx;
+  R->gy = gy;
+  R->q = (unsigned)(total >> 3);
+  R->r = (unsigned)(total & 7);
+  return true;
+}
+__device__ __forceinline__ unsigned xcd_div(unsigned l, unsigned m, unsigned s) { return __umulhi(2u * l + 1u, m) >> s; }
+__device__ __forceinline__ unsigned xcd_block(unsigned hw, const XcdRemap& R) {
+  const unsigned x = hw & 7;
+  return x * R.q + min(x, R.r) + (hw >> 3);
+}
+__device__ __forceinline__ int2 xcd_block2(const XcdRemap& R) {
+  const unsigned l = xcd_block(blockIdx.x + R.gx * blockIdx.y, R);
+  const unsigned q = xcd_div(l, R.mx, R.sx);
+  return make_int2((int)(l - q * R.gx), (int)q);
+}
+__device__ __forceinline__ int3 xcd_block3(const XcdRemap& R) {
+  const unsigned l = xcd_block(blockIdx.x + R.gx * (blockIdx.y + R.gy * blockIdx.z), R);
+  const unsigned q = xcd_div(l, R.mx, R.sx), z = xcd_div(q, R.my, R.sy);
+  return make_int3((int)(l - q * R.gx), (int)(q - z * R.gy), (int)z);
+}
+
 __device__ __forceinline__ int round_even(float v) { return (int)__builtin_rintf(v); }
 
 // fastAtan2 (OpenCV 3.2 core): degrees in [0,360).

@@ -6,13 +6,18 @@
 //   pyramid  (levels>=1): pyr  + img*pyr_bytes  + lv[l].off
 //   blurred  (all levels): blur + img*blur_bytes + lv[l].boff, 8x16-byte tiles (128 B each),
 //                          tile (ty, tx) at (ty * bstride/16 + tx) * 128, row y&7 at 16 * (y & 7)
-//   FAST candidates     : cand + img*cand_total + cells[c].cand_off   (u32 score<<24|y<<12|x)
+//   FAST candidates     : cand + img*cand_total + cell_slot(cells[c], p) (u32 score<<24|y<<12|x): a cell's
+//                          first kin survivors in its inline slots at cand_off, the rest at ovf_off
 //   octree output       : oct  + img*oct_total  + lv[l].oct_off        (same packing, list order)
+//
+// Geometry is the plan as the kernels read it from device memory.  k_resize alone never touches it:
+// what it needs comes by value in its launch descriptor (ResizeDesc, below).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/orbx.h"
+#include "orbx_device.h"
 
 namespace orbx {
 
@@ -123,5 +128,31 @@ struct BatchPtrs {
 __host__ __device__ inline const uint8_t* level_ptr(const Geometry& G, const BatchPtrs& B, int img, int l) {
   return l == 0 ? B.in + (size_t)img * B.in_pitch : B.pyr + (size_t)img * G.pyr_bytes + G.lv[l].off;
 }
+
+// ------------------------------------------------------------ launch descriptor
+// Everything block-uniform that k_resize needs before its first pixel load, passed BY VALUE as a
+// kernel argument: a block reads its kernel arguments, then its tile's footprint bounds (two pairs,
+// one wait), then pixels -- two serial scalar-load waits where walking Geometry took seven, in a
+// kernel whose waves live under 3,000 cycles.  Built once per plan on the host (build_launch_plan);
+// only `rm` depends on the batch size and is filled at launch.  (k_blur and k_fast were given the
+// same treatment and measured flat against the Geometry walk, profiles/r07/ab_descriptors_blur_fast.txt:
+// their waves live 6,000-10,000 cycles.  They keep the walk.)
+// One per level l >= 1 (source = level l - 1).
+struct ResizeDesc {
+  XcdRemap rm;
+  int sw, sh, dw, dh;      // source and destination level sizes
+  long long src_off;       // source level in an image's pyramid block; < 0: level 0, the input image
+  long long dst_off;       // destination level in an image's pyramid block
+  long long pyr_bytes;
+  const ResizeX* X;        // the level's coefficient tables (xt + xtab_off, yt + ytab_off)
+  const ResizeY* Y;
+  const int2* bx;          // per tile column: (sx0 of its first, sx1 of its last output column)
+  const int2* by;          // per tile row:    (sy0 of its first, sy1 of its last output row)
+  int stride, rows, lc;    // Geometry::rz_stride, rz_rows, rz_lc
+};
+
+struct LaunchPlan {
+  ResizeDesc rz[kMaxLevelsPlan];  // [l], l >= 1
+};
 
 }  // namespace orbx

@@ -168,11 +168,11 @@ __device__ uint32_t g_probe_bits[4][kProbeWords];         // L input, L pyramid,
 __device__ unsigned long long g_probe_count[3];           // sectors, lines, staged keypoints
 #endif
 
-__global__ __launch_bounds__(SBS, 8) void k_stereo_match(StereoArgs A, const Geometry* __restrict__ G) {
+__global__ __launch_bounds__(SBS, 8) void k_stereo_match(StereoArgs A, const Geometry* __restrict__ G, XcdRemap R) {
   constexpr int NQ = SBS / 16;                // quarters (keypoints) per block
   __shared__ uint32_t s_raw[NQ][11 * kSadDw];  // per quarter: 11 rows x (4 left + 6 right) dwords
   __shared__ uint32_t s_sw[NQ][66 + 121];  // per quarter: u16-pair forms of the patch and strip
-  const int2 bi = xcd_block2();
+  const int2 bi = xcd_block2(R);
   const int f = bi.y, tid = threadIdx.x, lane = tid & 63, ql = lane & 15, qb = tid >> 4;
   const int nL = min(A.nL[(size_t)f * A.n_stride_L], A.maxL);
   const int iL = bi.x * NQ + qb;
@@ -460,9 +460,9 @@ __device__ inline void probe_rows(const StereoArgs& A, const Geometry* G, int f,
   }
 }
 
-__global__ __launch_bounds__(SBS) void k_stereo_rows_only(StereoArgs A, const Geometry* __restrict__ G, uint32_t* sink) {
+__global__ __launch_bounds__(SBS) void k_stereo_rows_only(StereoArgs A, const Geometry* __restrict__ G, uint32_t* sink, XcdRemap R) {
   constexpr int NQ = SBS / 16;
-  const int2 bi = xcd_block2();
+  const int2 bi = xcd_block2(R);
   const int f = bi.y, tid = threadIdx.x, ql = tid & 15, qb = tid >> 4;
   const int nL = min(A.nL[(size_t)f * A.n_stride_L], A.maxL);
   const int iL = bi.x * NQ + qb;
@@ -521,14 +521,16 @@ hipError_t launch_stereo(const StereoArgs& A, const Geometry* Gd, int n_frames, 
   hipLaunchKernelGGL(k_stereo_prep, dim3(n_frames), dim3(PBS), 0, st, A, Gd);
   T->end(ST_STEREO_PREP, st);
   const int nb = (maxL + kKpsPerBlock - 1) / kKpsPerBlock;
+  XcdRemap R;  // the match grid's block order, division-free (orbx_device.h)
+  if (!make_xcd_remap(max(nb, 1), n_frames, 1, &R)) return hipErrorInvalidValue;
   T->begin(st);
-  hipLaunchKernelGGL(k_stereo_match, dim3(max(nb, 1), n_frames), dim3(SBS), 0, st, A, Gd);
+  hipLaunchKernelGGL(k_stereo_match, dim3(max(nb, 1), n_frames), dim3(SBS), 0, st, A, Gd, R);
   T->end(ST_STEREO_MATCH, st);
   T->begin(st);
   hipLaunchKernelGGL(k_stereo_finalize, dim3(n_frames), dim3(SBS), 0, st, A);
   T->end(ST_STEREO_FINAL, st);
 #ifdef ORBX_STEREO_ROWS_PROBE
-  hipLaunchKernelGGL(k_stereo_rows_only, dim3(max(nb, 1), n_frames), dim3(SBS), 0, st, A, Gd, (uint32_t*)A.nmatches);
+  hipLaunchKernelGGL(k_stereo_rows_only, dim3(max(nb, 1), n_frames), dim3(SBS), 0, st, A, Gd, (uint32_t*)A.nmatches, R);
   hipLaunchKernelGGL(k_stereo_rows_mark, dim3(max(nb, 1), n_frames), dim3(SBS), 0, st, A, Gd);
   hipLaunchKernelGGL(k_stereo_rows_count, dim3(1024), dim3(256), 0, st);
 #endif

@@ -35,6 +35,11 @@
  *   orbx_pnp_create             PnPsolver::PnPsolver + SetRansacParameters
  *                                                               src/PnPsolver.cc:67-179, include/PnPsolver.h:66,71
  *   orbx_pnp_iterate            PnPsolver::iterate              src/PnPsolver.cc:182-384, include/PnPsolver.h:77
+ *   orbx_sim3_create            Sim3Solver::Sim3Solver + SetRansacParameters
+ *                                                               src/Sim3Solver.cc:37-151, include/Sim3Solver.h:40,42
+ *   orbx_sim3_iterate           Sim3Solver::iterate / find      src/Sim3Solver.cc:153-245, include/Sim3Solver.h:44,46
+ *   orbx_sim3_get_estimate      GetEstimatedRotation / Translation / Scale   src/Sim3Solver.cc:425-438
+ *   orbx_sim3_iterate_candidates  the solver sweep of LoopClosing::ComputeSim3   src/LoopClosing.cc:372-402
  *   orbx_voc_load_text          TemplatedVocabulary::loadFromTextFile (ORBVocabulary)
  *                                                               Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1338-1420
  *   orbx_voc_transform          TemplatedVocabulary::transform(features, BowVector, FeatureVector, levelsup)
@@ -516,6 +521,81 @@ orbx_status orbx_pnp_iterate_candidates(orbx_pnp* const* solvers, int n, int n_i
  * batched into shared launches. */
 orbx_status orbx_pnp_iterate_many(orbx_pnp* const* solvers, int n, int n_iterations, orbx_rand_state* const* rngs,
                                   orbx_pnp_result* results, uint8_t* const* inliers);
+
+/* Sim3Solver (src/Sim3Solver.cc, include/Sim3Solver.h), the RANSAC stage of LoopClosing::ComputeSim3
+ * (src/LoopClosing.cc:372-402).  The caller gathers exactly like the constructor (:37-125): for each
+ * i1 with vpMatched12[i1], a non-null non-bad pMP1 = vpKeyFrameMP1[i1], a non-bad pMP2 and both
+ * GetIndexInKeyFrame >= 0: x3dc1 = Rcw1*X1w + tcw1, x3dc2 = Rcw2*X2w + tcw2 (camera frames),
+ * sigma2_j = pKFj->mvLevelSigma2[kpj.octave]; it keeps i1 (mvnIndices1) to map the returned inlier
+ * bytes back to a vector<bool> of length mN1.  (The struct is not named orbx_sim3_problem because
+ * that name belongs to orbx_search_by_sim3 below.) */
+typedef struct {
+  int n;
+  const float* x3dc1;    /* n x 3, mvX3Dc1 */
+  const float* x3dc2;    /* n x 3, mvX3Dc2 */
+  const float* sigma2_1; /* n; mvnMaxError1 = (size_t)(9.210 * sigma2), :95 */
+  const float* sigma2_2; /* n */
+  float fx1, fy1, cx1, cy1; /* mK1 */
+  float fx2, fy2, cx2, cy2; /* mK2 */
+  int fix_scale;            /* mbFixScale */
+} orbx_sim3_solver_problem;
+
+typedef struct { /* SetRansacParameters arguments (defaults 0.99, 6, 300; LoopClosing: 0.99, 20, 300) */
+  double probability;
+  int min_inliers;
+  int max_iterations;
+} orbx_sim3_params;
+
+typedef struct orbx_sim3 orbx_sim3;
+/* Sim3Solver::Sim3Solver + SetRansacParameters -- src/Sim3Solver.cc:37-151, include/Sim3Solver.h:40,42.
+ * ORBX_ERR_ARG (before the device is touched) when n >= min_inliers and n < 3: the reference would
+ * sample 3 of fewer than 3 correspondences. */
+orbx_status orbx_sim3_create(const orbx_sim3_solver_problem* problem, const orbx_sim3_params* params, int device,
+                             orbx_sim3** out);
+/* n solvers (one per loop candidate) with one parameter set, every correspondence in one upload. */
+orbx_status orbx_sim3_create_many(const orbx_sim3_solver_problem* problems, int n, const orbx_sim3_params* params,
+                                  int device, orbx_sim3** out);
+orbx_status orbx_sim3_destroy(orbx_sim3* h);
+/* Sim3Solver::SetRansacParameters -- src/Sim3Solver.cc:127-151, include/Sim3Solver.h:42: derives
+ * mRansacMaxIts and, like the reference, resets mnIterations to 0; the best set is kept. */
+orbx_status orbx_sim3_set_ransac_parameters(orbx_sim3* h, const orbx_sim3_params* params);
+/* mRansacMinInliers, the derived mRansacMaxIts, mnIterations, mnBestInliers (any may be NULL). */
+orbx_status orbx_sim3_get_params(const orbx_sim3* h, int* min_inliers, int* max_iterations, int* iterations,
+                                 int* best_inliers);
+/* Sim3Solver::iterate(nIterations, bNoMore, vbInliers, nInliers) -- src/Sim3Solver.cc:153-239,
+ * include/Sim3Solver.h:46.  rand_vals: the next rand() outputs of the caller's stream, at least
+ * 3 * min(nIterations, maxIts - done) of them; *used = values consumed (3 per iteration run).
+ * *found = 1 when a Sim3 (T12, row-major 4x4) is returned; inliers[n] = 1 per inlier correspondence
+ * (all 0 otherwise). */
+orbx_status orbx_sim3_iterate(orbx_sim3* h, int n_iterations, const int32_t* rand_vals, int n_rand, int* used,
+                              int* no_more, float T12[16], uint8_t* inliers, int* n_inliers, int* found);
+/* The same drawing from *rng, which advances by exactly `used`.  Sim3Solver::find (:241-245,
+ * include/Sim3Solver.h:44) is this with n_iterations = the derived mRansacMaxIts. */
+orbx_status orbx_sim3_iterate_stream(orbx_sim3* h, int n_iterations, orbx_rand_state* rng, int* no_more,
+                                     float T12[16], uint8_t* inliers, int* n_inliers, int* found);
+/* GetEstimatedRotation / GetEstimatedTranslation / GetEstimatedScale -- src/Sim3Solver.cc:425-438,
+ * include/Sim3Solver.h:48-50: the best hypothesis so far (zeros before the first iteration). */
+orbx_status orbx_sim3_get_estimate(orbx_sim3* h, float R[9], float t[3], float* s);
+
+typedef struct {
+  int no_more;   /* bNoMore */
+  int found;     /* a Sim3 was returned */
+  int n_inliers; /* nInliers */
+  int used;      /* rand() values this call drew for the solver */
+  float T12[16]; /* row-major 4x4 when found */
+} orbx_sim3_result;
+/* One sweep of LoopClosing::ComputeSim3's candidate loop (src/LoopClosing.cc:372-402):
+ * iterate(n_iterations) on solvers[0], solvers[1], ... in order, all drawing from *rng, stopping
+ * after the first solver that returns a Sim3 (*stopped = its index, n when none did); later
+ * solvers are untouched (results zeroed) and the caller resumes with the remaining slice after its
+ * SearchBySim3 / OptimizeSim3.  The hypothesis launch spans all solvers.  inliers[s] (may be NULL,
+ * or any entry NULL): solvers[s]->n bytes, written when results[s].found.  Same device for all. */
+orbx_status orbx_sim3_iterate_candidates(orbx_sim3* const* solvers, int n, int n_iterations, orbx_rand_state* rng,
+                                         orbx_sim3_result* results, uint8_t* const* inliers, int* stopped);
+/* Independent solvers, each with its own rand() stream rngs[s] (distinct pointers): iterate(n_iterations)
+ * on every solver in shared launches -- src/Sim3Solver.cc:153-239 per solver. */
+orbx_status orbx_sim3_iterate_many(orbx_sim3* const* solvers, int n, int n_iterations, orbx_rand_state* const* rngs,
+                                   orbx_sim3_result* results, uint8_t* const* inliers);
 
 /* ORBmatcher::SearchByProjection -- the three overloads run on every tracked
  * frame -- with Frame::AssignFeaturesToGrid / GetFeaturesInArea

@@ -46,6 +46,10 @@ enum {
 long long orbx_debug_launch_plan(const orbx_extractor_params* params, int width, int height, int what, int a0,
                                  int a1, int a2, long long* dst, size_t cap);
 
+/* The library's deterministic double atan2 (Sim3Solver's half-angle, src/Sim3Solver.cc:325) evaluated
+ * on the host: the same operation sequence as the kernels run (no device is needed or touched). */
+double orbx_debug_atan2_det(double y, double x);
+
 /* Solve S x = b (N x N, N a multiple of 6) with the LocalBA reduced-system
  * LDLT kernel; *ms = mean kernel time over reps launches.  ORBX_ERR_STATE on
  * a zero pivot. */

@@ -171,6 +171,22 @@ class PnpResult(C.Structure):
                 ("Tcw", C.c_float * 16)]
 
 
+class Sim3SolverProblem(C.Structure):  # orbx_sim3_solver_problem (Sim3Solver; Sim3Problem is SearchBySim3's)
+    _fields_ = [("n", C.c_int), ("x3dc1", C.c_void_p), ("x3dc2", C.c_void_p), ("sigma2_1", C.c_void_p),
+                ("sigma2_2", C.c_void_p)] + \
+               [(k, C.c_float) for k in ("fx1", "fy1", "cx1", "cy1", "fx2", "fy2", "cx2", "cy2")] + \
+               [("fix_scale", C.c_int)]
+
+
+class Sim3Params(C.Structure):
+    _fields_ = [("probability", C.c_double), ("min_inliers", C.c_int), ("max_iterations", C.c_int)]
+
+
+class Sim3Result(C.Structure):
+    _fields_ = [("no_more", C.c_int), ("found", C.c_int), ("n_inliers", C.c_int), ("used", C.c_int),
+                ("T12", C.c_float * 16)]
+
+
 # Every entry point of include/orbx.h with its ctypes signature.
 P = C.c_void_p
 SIGNATURES = {
@@ -244,6 +260,21 @@ SIGNATURES = {
     "orbx_undistort_keypoints_device": ([P, P, C.c_int, C.c_int, P, P, P], C.c_int),
     "orbx_pnp_iterate_candidates": ([P, C.c_int, C.c_int, C.POINTER(RandState), P, P, C.POINTER(C.c_int)], C.c_int),
     "orbx_pnp_iterate_many": ([P, C.c_int, C.c_int, P, P, P], C.c_int),
+    "orbx_sim3_create": ([C.POINTER(Sim3SolverProblem), C.POINTER(Sim3Params), C.c_int, C.POINTER(C.c_void_p)],
+                         C.c_int),
+    "orbx_sim3_create_many": ([P, C.c_int, C.POINTER(Sim3Params), C.c_int, P], C.c_int),
+    "orbx_sim3_destroy": ([P], C.c_int),
+    "orbx_sim3_set_ransac_parameters": ([P, C.POINTER(Sim3Params)], C.c_int),
+    "orbx_sim3_get_params": ([P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
+                             C.c_int),
+    "orbx_sim3_iterate": ([P, C.c_int, P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), P, P,
+                           C.POINTER(C.c_int), C.POINTER(C.c_int)], C.c_int),
+    "orbx_sim3_iterate_stream": ([P, C.c_int, C.POINTER(RandState), C.POINTER(C.c_int), P, P, C.POINTER(C.c_int),
+                                  C.POINTER(C.c_int)], C.c_int),
+    "orbx_sim3_get_estimate": ([P, P, P, C.POINTER(C.c_float)], C.c_int),
+    "orbx_sim3_iterate_candidates": ([P, C.c_int, C.c_int, C.POINTER(RandState), P, P, C.POINTER(C.c_int)],
+                                     C.c_int),
+    "orbx_sim3_iterate_many": ([P, C.c_int, C.c_int, P, P, P], C.c_int),
     "orbx_rand_seed":([C.POINTER(RandState), C.c_uint32], None),
     "orbx_rand_next": ([C.POINTER(RandState)], C.c_int32),
     "orbx_ba_create": ([C.c_int, C.POINTER(C.c_void_p)], C.c_int),
@@ -268,6 +299,7 @@ SIGNATURES = {
     "orbx_debug_copy": ([P, C.c_int, C.c_int, C.c_int, P, C.c_size_t], C.c_longlong),
     "orbx_debug_launch_plan": ([C.POINTER(ExtractorParams), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P,
                                 C.c_size_t], C.c_longlong),
+    "orbx_debug_atan2_det": ([C.c_double, C.c_double], C.c_double),
     "orbx_debug_ldlt": ([P, P, C.c_int, P, C.c_int, C.POINTER(C.c_float)], C.c_int),
     "orbx_debug_ldlt_ex": ([P, P, C.c_int, P, C.c_int, C.POINTER(C.c_float), C.c_int, P], C.c_int),
     "orbx_debug_ba_options": ([P, C.POINTER(BaDebugOptions)], C.c_int),

@@ -151,6 +151,93 @@ __device__ __forceinline__ void sincos_det(float xf, const double* __restrict__ 
   *c_out = (float)c;
 }
 
+// Double sin/cos by Cody-Waite reduction + Taylor polynomials: basic IEEE operations only, so the
+// CPU restatements reproduce it bit for bit (SE3Quat::exp in poseopt.hip, cv::Rodrigues in sim3.hip).
+__device__ __forceinline__ void sincos_d(double x, double* s_out, double* c_out) {
+  const double kInvPio2 = 6.36619772367581382433e-01;
+  const double kPio2Hi = 1.57079632673412561417e+00;
+  const double kPio2Lo = 6.07710050650619224932e-11;
+  const double kd = __builtin_rint(x * kInvPio2);
+  const int q = (int)kd;
+  const double r = (x - kd * kPio2Hi) - kd * kPio2Lo;
+  const double r2 = r * r;
+  double ps = 1.0 / 51090942171709440000.0;
+  ps = ps * r2 - 1.0 / 121645100408832000.0;
+  ps = ps * r2 + 1.0 / 355687428096000.0;
+  ps = ps * r2 - 1.0 / 1307674368000.0;
+  ps = ps * r2 + 1.0 / 6227020800.0;
+  ps = ps * r2 - 1.0 / 39916800.0;
+  ps = ps * r2 + 1.0 / 362880.0;
+  ps = ps * r2 - 1.0 / 5040.0;
+  ps = ps * r2 + 1.0 / 120.0;
+  ps = ps * r2 - 1.0 / 6.0;
+  const double sr = r + r * (r2 * ps);
+  double pc = 1.0 / 2432902008176640000.0;
+  pc = pc * r2 - 1.0 / 6402373705728000.0;
+  pc = pc * r2 + 1.0 / 20922789888000.0;
+  pc = pc * r2 - 1.0 / 87178291200.0;
+  pc = pc * r2 + 1.0 / 479001600.0;
+  pc = pc * r2 - 1.0 / 3628800.0;
+  pc = pc * r2 + 1.0 / 40320.0;
+  pc = pc * r2 - 1.0 / 720.0;
+  pc = pc * r2 + 1.0 / 24.0;
+  pc = pc * r2 - 0.5;
+  const double cr = 1.0 + r2 * pc;
+  double s, c;
+  switch (q & 3) {
+    case 0: s = sr; c = cr; break;
+    case 1: s = cr; c = -sr; break;
+    case 2: s = -sr; c = -cr; break;
+    default: s = -cr; c = sr; break;
+  }
+  *s_out = s;
+  *c_out = c;
+}
+
+// Double atan2 from basic IEEE operations only (+ - * / rint, compares), the same sequence on the
+// host, the device and in the tests' Python twin; std::atan2's special values (signed zeros, axes,
+// infinities, NaN).  t = min(|y|,|x|) / max(|y|,|x|) in [0,1]; atan t = atan c + atan((t-c)/(1+tc))
+// with c the nearest multiple of 1/4, |(t-c)/(1+tc)| <= 1/8, odd series to r^23 (truncation
+// below 1e-23); then the octant, half-plane and sign folds with two-word pi/2 and pi.
+__host__ __device__ inline double atan2_det(double y, double x) {
+  if (y != y || x != x) return y + x;
+  const bool ny = __builtin_signbit(y), nx = __builtin_signbit(x);
+  const double ay = ny ? -y : y, ax = nx ? -x : x;
+  const bool sw = ay > ax;
+  const double hi = sw ? ay : ax, lo = sw ? ax : ay;
+  double t;
+  if (hi == 0.0)
+    t = 0.0;
+  else if (lo == hi)  // also inf / inf
+    t = 1.0;
+  else
+    t = lo / hi;
+  const double k = __builtin_rint(t * 4.0);
+  const double c = k * 0.25;
+  const double base = k == 0.0   ? 0.0
+                      : k == 1.0 ? 2.44978663126864143e-01
+                      : k == 2.0 ? 4.63647609000806094e-01
+                      : k == 3.0 ? 6.43501108793284371e-01
+                                 : 7.85398163397448279e-01;
+  const double r = (t - c) / (1.0 + t * c);
+  const double r2 = r * r;
+  double p = 1.0 / 23.0;
+  p = p * r2 - 1.0 / 21.0;
+  p = p * r2 + 1.0 / 19.0;
+  p = p * r2 - 1.0 / 17.0;
+  p = p * r2 + 1.0 / 15.0;
+  p = p * r2 - 1.0 / 13.0;
+  p = p * r2 + 1.0 / 11.0;
+  p = p * r2 - 1.0 / 9.0;
+  p = p * r2 + 1.0 / 7.0;
+  p = p * r2 - 1.0 / 5.0;
+  p = p * r2 + 1.0 / 3.0;
+  double a = base + (r - r * (r2 * p));
+  if (sw) a = (1.57079632679489656e+00 - a) + 6.12323399573676604e-17;
+  if (nx) a = (3.14159265358979312e+00 - a) + 1.22464679914735321e-16;
+  return ny ? -a : a;
+}
+
 // Hamming distance of two 256-bit descriptors held as 4 x u64.
 __device__ __forceinline__ int hamming256(const uint64_t a[4], const uint64_t b[4]) {
   return __popcll(a[0] ^ b[0]) + __popcll(a[1] ^ b[1]) + __popcll(a[2] ^ b[2]) + __popcll(a[3] ^ b[3]);

@@ -120,47 +120,6 @@ __device__ __forceinline__ void qnormalize(Quat& q) {
   q.x /= n; q.y /= n; q.z /= n; q.w /= n;
 }
 
-__device__ __forceinline__ void sincos_d(double x, double* s_out, double* c_out) {
-  const double kInvPio2 = 6.36619772367581382433e-01;
-  const double kPio2Hi = 1.57079632673412561417e+00;
-  const double kPio2Lo = 6.07710050650619224932e-11;
-  const double kd = __builtin_rint(x * kInvPio2);
-  const int q = (int)kd;
-  const double r = (x - kd * kPio2Hi) - kd * kPio2Lo;
-  const double r2 = r * r;
-  double ps = 1.0 / 51090942171709440000.0;
-  ps = ps * r2 - 1.0 / 121645100408832000.0;
-  ps = ps * r2 + 1.0 / 355687428096000.0;
-  ps = ps * r2 - 1.0 / 1307674368000.0;
-  ps = ps * r2 + 1.0 / 6227020800.0;
-  ps = ps * r2 - 1.0 / 39916800.0;
-  ps = ps * r2 + 1.0 / 362880.0;
-  ps = ps * r2 - 1.0 / 5040.0;
-  ps = ps * r2 + 1.0 / 120.0;
-  ps = ps * r2 - 1.0 / 6.0;
-  const double sr = r + r * (r2 * ps);
-  double pc = 1.0 / 2432902008176640000.0;
-  pc = pc * r2 - 1.0 / 6402373705728000.0;
-  pc = pc * r2 + 1.0 / 20922789888000.0;
-  pc = pc * r2 - 1.0 / 87178291200.0;
-  pc = pc * r2 + 1.0 / 479001600.0;
-  pc = pc * r2 - 1.0 / 3628800.0;
-  pc = pc * r2 + 1.0 / 40320.0;
-  pc = pc * r2 - 1.0 / 720.0;
-  pc = pc * r2 + 1.0 / 24.0;
-  pc = pc * r2 - 0.5;
-  const double cr = 1.0 + r2 * pc;
-  double s, c;
-  switch (q & 3) {
-    case 0: s = sr; c = cr; break;
-    case 1: s = cr; c = -sr; break;
-    case 2: s = -sr; c = -cr; break;
-    default: s = -cr; c = sr; break;
-  }
-  *s_out = s;
-  *c_out = c;
-}
-
 // SE3Quat::exp(update), types/se3quat.h:223-257 (then operator* with T)
 __device__ __forceinline__ SE3 se3_exp(const double u[6]) {
   const double w[3] = {u[0], u[1], u[2]}, up[3] = {u[3], u[4], u[5]};

@@ -887,6 +887,182 @@ def pnp_iterate_candidates(solvers, nIterations, rng, raw_results=None):
     return stopped.value, _pnp_outputs(solvers[:k], res[:k], inl[:k])
 
 
+def sim3_iterate_candidates(solvers, nIterations, rng, raw_results=None):
+    """One sweep of LoopClosing::ComputeSim3's solver loop (src/LoopClosing.cc:372-402) in one call:
+    solvers[0].iterate(n), solvers[1].iterate(n), ... on the shared stream `rng` (GlibcRand), stopping
+    after the first that returns a Sim3; the caller resumes with solvers[stopped+1:] after its
+    SearchBySim3 / OptimizeSim3.  Returns (stopped, [(T12|None, bNoMore, vbInliers[mN1], nInliers)] for
+    solvers[0..stopped]); rng advances by exactly what was drawn.  raw_results: optional list that
+    receives every solver's orbx_sim3_result (tests)."""
+    n = len(solvers)
+    hs = (C.c_void_p * max(n, 1))(*[s._h for s in solvers])
+    res = (_lib.Sim3Result * max(n, 1))()
+    inl = [np.zeros(max(s.n, 1), np.uint8) for s in solvers]
+    ip = (C.c_void_p * max(n, 1))(*[ptr(b) for b in inl])
+    st = _rand_state(rng)
+    stopped = C.c_int()
+    check(_lib.lib().orbx_sim3_iterate_candidates(hs, n, int(nIterations), C.byref(st), res, ip, C.byref(stopped)),
+          "orbx_sim3_iterate_candidates")
+    _rand_restore(rng, st)
+    if raw_results is not None:
+        raw_results.extend(res[i] for i in range(n))
+    k = min(stopped.value + 1, n)
+    return stopped.value, [s._output(r, b) for s, r, b in zip(solvers[:k], res[:k], inl[:k])]
+
+
+def sim3_iterate_many(solvers, nIterations, rngs):
+    """iterate(n) on independent Sim3Solvers, rngs[i] its own GlibcRand stream; one batched call."""
+    n = len(solvers)
+    hs = (C.c_void_p * max(n, 1))(*[s._h for s in solvers])
+    res = (_lib.Sim3Result * max(n, 1))()
+    inl = [np.zeros(max(s.n, 1), np.uint8) for s in solvers]
+    ip = (C.c_void_p * max(n, 1))(*[ptr(b) for b in inl])
+    sts = [_rand_state(r) for r in rngs]
+    sp = (C.c_void_p * max(n, 1))(*[C.addressof(x) for x in sts])
+    check(_lib.lib().orbx_sim3_iterate_many(hs, n, int(nIterations), sp, res, ip), "orbx_sim3_iterate_many")
+    for r, x in zip(rngs, sts):
+        _rand_restore(r, x)
+    return [s._output(r, b) for s, r, b in zip(solvers, res[:n], inl)]
+
+
+class Sim3Solver:
+    """Sim3Solver (include/Sim3Solver.h:36-50) over orbx_sim3_*.
+
+    Correspondences are given in the constructor's gather order (src/Sim3Solver.cc:37-125): the
+    camera-frame points mvX3Dc1 / mvX3Dc2, mvLevelSigma2[octave] of the two keypoints, K1 / K2 as
+    (fx, fy, cx, cy), and mvnIndices1 with mN1 = len(vpMatched12) so vbInliers comes back with the
+    reference's length and indexing.  Like the reference the constructor applies
+    SetRansacParameters() with its defaults (0.99, 6, 300); LoopClosing sets (0.99, 20, 300)."""
+
+    def __init__(self, x3dc1, x3dc2, sigma2_1, sigma2_2, K1, K2, bFixScale, mvnIndices1=None, mN1=None, device=0):
+        self._set_problem(x3dc1, x3dc2, sigma2_1, sigma2_2, K1, K2, bFixScale, mvnIndices1, mN1, device)
+        prm = _lib.Sim3Params(0.99, 6, 300)
+        h = C.c_void_p()
+        check(_lib.lib().orbx_sim3_create(C.byref(self._struct()), C.byref(prm), self.device, C.byref(h)),
+              "orbx_sim3_create")
+        self._h = h
+        self._read_params()
+
+    def _set_problem(self, x3dc1, x3dc2, sigma2_1, sigma2_2, K1, K2, bFixScale, mvnIndices1, mN1, device):
+        self.x3dc1 = np.ascontiguousarray(x3dc1, np.float32).reshape(-1, 3)
+        self.x3dc2 = np.ascontiguousarray(x3dc2, np.float32).reshape(-1, 3)
+        self.sigma2_1 = np.ascontiguousarray(sigma2_1, np.float32).reshape(-1)
+        self.sigma2_2 = np.ascontiguousarray(sigma2_2, np.float32).reshape(-1)
+        self.n = len(self.x3dc1)
+        if not (len(self.x3dc2) == len(self.sigma2_1) == len(self.sigma2_2) == self.n):
+            raise ValueError("Sim3Solver: correspondence arrays differ in length")
+        self.K1 = tuple(float(v) for v in K1)
+        self.K2 = tuple(float(v) for v in K2)
+        self.bFixScale = bool(bFixScale)
+        self.mvnIndices1 = (np.arange(self.n) if mvnIndices1 is None else np.asarray(mvnIndices1, np.int64)).reshape(-1)
+        self.mN1 = self.n if mN1 is None else int(mN1)
+        self.device = int(device)
+        self._h = None
+
+    def _struct(self):
+        return _lib.Sim3SolverProblem(self.n, ptr(self.x3dc1), ptr(self.x3dc2), ptr(self.sigma2_1), ptr(self.sigma2_2),
+                                      *self.K1, *self.K2, int(self.bFixScale))
+
+    def _read_params(self):
+        a, b, c, d = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        check(_lib.lib().orbx_sim3_get_params(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)),
+              "orbx_sim3_get_params")
+        self.mRansacMinInliers, self.mRansacMaxIts, self.mnIterations, self.mnBestInliers = (a.value, b.value, c.value,
+                                                                                          d.value)
+
+    @classmethod
+    def create_many(cls, problems, probability=0.99, minInliers=6, maxIterations=300, device=0):
+        """len(problems) solvers (dicts x3dc1, x3dc2, sigma2_1, sigma2_2, K1, K2, bFixScale and optionally
+        mvnIndices1, mN1) with one parameter set, by one orbx_sim3_create_many call (one upload)."""
+        n = len(problems)
+        objs, structs = [], (_lib.Sim3SolverProblem * max(n, 1))()
+        for i, P in enumerate(problems):
+            o = cls.__new__(cls)
+            o._set_problem(P["x3dc1"], P["x3dc2"], P["sigma2_1"], P["sigma2_2"], P["K1"], P["K2"], P["bFixScale"],
+                           P.get("mvnIndices1"), P.get("mN1"), device)
+            structs[i] = o._struct()
+            objs.append(o)
+        prm = _lib.Sim3Params(float(probability), int(minInliers), int(maxIterations))
+        hs = (C.c_void_p * max(n, 1))()
+        check(_lib.lib().orbx_sim3_create_many(structs, n, C.byref(prm), int(device), hs), "orbx_sim3_create_many")
+        for o, h in zip(objs, hs):
+            o._h = C.c_void_p(h)
+            o._read_params()
+        return objs
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.lib().orbx_sim3_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def SetRansacParameters(self, probability=0.99, minInliers=6, maxIterations=300):
+        """src/Sim3Solver.cc:127-151; resets mnIterations to 0 as the reference does."""
+        prm = _lib.Sim3Params(float(probability), int(minInliers), int(maxIterations))
+        check(_lib.lib().orbx_sim3_set_ransac_parameters(self._h, C.byref(prm)), "orbx_sim3_set_ransac_parameters")
+        self._read_params()
+
+    def _output(self, r, inl):
+        self._read_params()
+        vb = np.zeros(self.mN1, bool)
+        if r.found:
+            vb[self.mvnIndices1[inl[:self.n] != 0]] = True
+        T = np.ctypeslib.as_array(r.T12).reshape(4, 4).copy() if r.found else None
+        return T, bool(r.no_more), vb, int(r.n_inliers)
+
+    def iterate(self, nIterations, rng):
+        """iterate(nIterations, bNoMore, vbInliers, nInliers), src/Sim3Solver.cc:153-239.  rng: a rand()
+        stream (glibc_rand.GlibcRand(1) is the reference's unseeded process rand()).  Returns
+        (T12[4,4] or None, bNoMore, vbInliers[mN1] bool, nInliers); the stream advances by exactly
+        what was drawn."""
+        st = _rand_state(rng)
+        nm, ni, found = C.c_int(), C.c_int(), C.c_int()
+        r = _lib.Sim3Result()
+        inl = np.zeros(max(self.n, 1), np.uint8)
+        check(_lib.lib().orbx_sim3_iterate_stream(self._h, int(nIterations), C.byref(st), C.byref(nm), r.T12,
+                                                  ptr(inl), C.byref(ni), C.byref(found)), "orbx_sim3_iterate_stream")
+        _rand_restore(rng, st)
+        r.no_more, r.found, r.n_inliers = nm.value, found.value, ni.value
+        return self._output(r, inl)
+
+    def iterate_values(self, nIterations, rand_vals):
+        """The same from explicit rand() values (orbx_sim3_iterate); returns (used, *iterate's tuple)."""
+        vals = np.ascontiguousarray(rand_vals, np.int32)
+        used, nm, ni, found = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        r = _lib.Sim3Result()
+        inl = np.zeros(max(self.n, 1), np.uint8)
+        check(_lib.lib().orbx_sim3_iterate(self._h, int(nIterations), ptr(vals), len(vals), C.byref(used),
+                                           C.byref(nm), r.T12, ptr(inl), C.byref(ni), C.byref(found)),
+              "orbx_sim3_iterate")
+        r.no_more, r.found, r.n_inliers = nm.value, found.value, ni.value
+        return (used.value,) + self._output(r, inl)
+
+    def find(self, rng):
+        """find(vbInliers12, nInliers), src/Sim3Solver.cc:241-245: iterate(mRansacMaxIts).  Returns
+        (T12 or None, vbInliers12, nInliers)."""
+        T, _, vb, ni = self.iterate(self.mRansacMaxIts, rng)
+        return T, vb, ni
+
+    def _estimate(self):
+        R, t, s = np.zeros(9, np.float32), np.zeros(3, np.float32), C.c_float()
+        check(_lib.lib().orbx_sim3_get_estimate(self._h, ptr(R), ptr(t), C.byref(s)), "orbx_sim3_get_estimate")
+        return R.reshape(3, 3), t, s.value
+
+    def GetEstimatedRotation(self):
+        return self._estimate()[0]
+
+    def GetEstimatedTranslation(self):
+        return self._estimate()[1]
+
+    def GetEstimatedScale(self):
+        return self._estimate()[2]
+
+
 def pnp_iterate_many(solvers, nIterations, rngs):
     """iterate(n) on independent solvers, rngs[i] its own GlibcRand stream; one batched call."""
     n = len(solvers)

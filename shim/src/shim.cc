@@ -31,6 +31,7 @@
 #include "Objects.h"
 #include "Optimizer.h"
 #include "PnPsolver.h"
+#include "Sim3Solver.h"
 #include "orbx.h"
 #include "orbx_shim.h"
 
@@ -1332,6 +1333,134 @@ cv::Mat PnPsolver::iterate(int nIterations, bool& bNoMore, std::vector<bool>& vb
   for (int r = 0; r < 4; r++)
     for (int c = 0; c < 4; c++) Tcw.at<float>(r, c) = T[4 * r + c];
   return Tcw;
+}
+
+// ------------------------------------------------------------------ Sim3Solver
+namespace {
+// Rcw*X + tcw on 3x1 CV_32F Mats: cv::gemm(R, X, 1, t, 1) on OpenCV 3.2's small-matrix path -- the
+// dot product in float, left to right, then (float)(t0*alpha + c*beta) in double
+void mat3x1(const cv::Mat& R, const cv::Mat& t, const cv::Mat& X, float out[3]) {
+  for (int r = 0; r < 3; r++) {
+    const float t0 = R.at<float>(r, 0) * X.at<float>(0, 0) + R.at<float>(r, 1) * X.at<float>(1, 0) +
+                     R.at<float>(r, 2) * X.at<float>(2, 0);
+    out[r] = (float)((double)t0 * 1.0 + (double)t.at<float>(r, 0) * 1.0);
+  }
+}
+}  // namespace
+
+Sim3Solver::Sim3Solver(KeyFrame* pKF1, KeyFrame* pKF2, const std::vector<MapPoint*>& vpMatched12, const bool bFixScale)
+    : mbFixScale(bFixScale) {
+  // src/Sim3Solver.cc:37-125
+  const std::vector<MapPoint*> vpKeyFrameMP1 = pKF1->GetMapPointMatches();
+  mN1 = (int)vpMatched12.size();
+  const cv::Mat Rcw1 = pKF1->GetRotation(), tcw1 = pKF1->GetTranslation();
+  const cv::Mat Rcw2 = pKF2->GetRotation(), tcw2 = pKF2->GetTranslation();
+  for (int i1 = 0; i1 < mN1; i1++) {
+    if (!vpMatched12[i1]) continue;
+    MapPoint* pMP1 = vpKeyFrameMP1[i1];
+    MapPoint* pMP2 = vpMatched12[i1];
+    if (!pMP1) continue;
+    if (pMP1->isBad() || pMP2->isBad()) continue;
+    const int indexKF1 = pMP1->GetIndexInKeyFrame(pKF1);
+    const int indexKF2 = pMP2->GetIndexInKeyFrame(pKF2);
+    if (indexKF1 < 0 || indexKF2 < 0) continue;
+    const cv::KeyPoint& kp1 = pKF1->mvKeysUn[indexKF1];
+    const cv::KeyPoint& kp2 = pKF2->mvKeysUn[indexKF2];
+    mvSigma2_1.push_back(pKF1->mvLevelSigma2[kp1.octave]);
+    mvSigma2_2.push_back(pKF2->mvLevelSigma2[kp2.octave]);
+    mvnIndices1.push_back(i1);
+    float X[3];
+    mat3x1(Rcw1, tcw1, pMP1->GetWorldPos(), X);
+    mvX3Dc1.insert(mvX3Dc1.end(), X, X + 3);
+    mat3x1(Rcw2, tcw2, pMP2->GetWorldPos(), X);
+    mvX3Dc2.insert(mvX3Dc2.end(), X, X + 3);
+  }
+  mK1[0] = pKF1->fx, mK1[1] = pKF1->fy, mK1[2] = pKF1->cx, mK1[3] = pKF1->cy;  // mK's entries
+  mK2[0] = pKF2->fx, mK2[1] = pKF2->fy, mK2[2] = pKF2->cx, mK2[3] = pKF2->cy;
+  SetRansacParameters();
+}
+
+Sim3Solver::~Sim3Solver() {
+  if (mpGpu) orbx_sim3_destroy(mpGpu);
+}
+
+void Sim3Solver::SetRansacParameters(double probability, int minInliers, int maxIterations) {
+  mParams = orbx_sim3_params{probability, minInliers, maxIterations};
+  if (mpGpu) {  // a live solver: mnIterations back to 0, the best set kept (:150)
+    check(orbx_sim3_set_ransac_parameters(mpGpu, &mParams), "orbx_sim3_set_ransac_parameters");
+    check(orbx_sim3_get_params(mpGpu, nullptr, &mRansacMaxIts, nullptr, nullptr), "orbx_sim3_get_params");
+  }
+}
+
+void Sim3Solver::ensure_solver() {
+  if (mpGpu) return;
+  const int n = (int)mvnIndices1.size();
+  const orbx_sim3_solver_problem prob{n,
+                                      n ? mvX3Dc1.data() : nullptr,
+                                      n ? mvX3Dc2.data() : nullptr,
+                                      n ? mvSigma2_1.data() : nullptr,
+                                      n ? mvSigma2_2.data() : nullptr,
+                                      mK1[0], mK1[1], mK1[2], mK1[3],
+                                      mK2[0], mK2[1], mK2[2], mK2[3],
+                                      mbFixScale ? 1 : 0};
+  check(orbx_sim3_create(&prob, &mParams, gOrbxDevice, &mpGpu), "orbx_sim3_create");
+  check(orbx_sim3_get_params(mpGpu, nullptr, &mRansacMaxIts, nullptr, nullptr), "orbx_sim3_get_params");
+}
+
+cv::Mat Sim3Solver::find(std::vector<bool>& vbInliers12, int& nInliers) {
+  ensure_solver();
+  bool bFlag;
+  return iterate(mRansacMaxIts, bFlag, vbInliers12, nInliers);  // src/Sim3Solver.cc:241-245
+}
+
+cv::Mat Sim3Solver::iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers) {
+  ensure_solver();
+  bNoMore = false;
+  vbInliers = std::vector<bool>(mN1, false);  // :157
+  nInliers = 0;
+  const int n = (int)mvnIndices1.size();
+  std::vector<uint8_t> inl(n > 0 ? n : 1, 0);
+  float T[16];
+  int no_more = 0, ni = 0, found = 0;
+  {
+    std::lock_guard<std::mutex> lock(g_rand_mu);
+    check(orbx_sim3_iterate_stream(mpGpu, nIterations, &g_rand, &no_more, T, inl.data(), &ni, &found),
+          "orbx_sim3_iterate_stream");
+  }
+  bNoMore = no_more != 0;
+  if (!found) return cv::Mat();
+  nInliers = ni;
+  for (int i = 0; i < n; i++)
+    if (inl[i]) vbInliers[mvnIndices1[i]] = true;  // :226-228
+  cv::Mat T12(4, 4, CV_32F);
+  for (int r = 0; r < 4; r++)
+    for (int c = 0; c < 4; c++) T12.at<float>(r, c) = T[4 * r + c];
+  return T12;
+}
+
+cv::Mat Sim3Solver::GetEstimatedRotation() {
+  ensure_solver();
+  float R[9], t[3], s;
+  check(orbx_sim3_get_estimate(mpGpu, R, t, &s), "orbx_sim3_get_estimate");
+  cv::Mat m(3, 3, CV_32F);
+  for (int i = 0; i < 9; i++) m.at<float>(i / 3, i % 3) = R[i];
+  return m;
+}
+
+cv::Mat Sim3Solver::GetEstimatedTranslation() {
+  ensure_solver();
+  float R[9], t[3], s;
+  check(orbx_sim3_get_estimate(mpGpu, R, t, &s), "orbx_sim3_get_estimate");
+  cv::Mat m(3, 1, CV_32F);
+  for (int i = 0; i < 3; i++) m.at<float>(i, 0) = t[i];
+  return m;
+}
+
+float Sim3Solver::GetEstimatedScale() {
+  ensure_solver();
+  float R[9], t[3], s;
+  check(orbx_sim3_get_estimate(mpGpu, R, t, &s), "orbx_sim3_get_estimate");
+  return s;
 }
 
 // ------------------------------------------------------------------ Optimizer

@@ -1,18 +1,20 @@
 // pnp.hip -- PnPsolver (src/PnPsolver.cc:67-1101) on the GPU: RANSAC
 // hypotheses evaluated in parallel, resolved in the reference's order.
 //
-//   k_pnp_hyp     one 256-thread block per hypothesis: EPnP compute_pose on
-//                 its minimal set (DUtils::Random::RandomInt + swap-remove
-//                 sampling replayed on the host from the caller's rand()
-//                 values), everything in LDS
-//   k_pnp_check   one block per hypothesis: CheckInliers (float/double mix
-//                 exactly as :352-384) -> inlier bytes + count
-//   k_pnp_refine  one block: Refine() (:303-349) = EPnP on every inlier of
-//                 the best hypothesis (staged in LDS) + CheckInliers
-// The host walks hypotheses in order (best = first strict maximum, Refine at
-// each hypothesis reaching minInliers, return on the first successful
-// Refine), which is iterate() (:182-301) including its
-// `mnIterations<maxIts || nCurrent<nIterations` loop condition.
+//   k_pnp_hyp_many     one wave per (hypothesis, solver): EPnP compute_pose on its
+//                      minimal set (DUtils::Random::RandomInt + swap-remove sampling
+//                      replayed on the host from the caller's rand() values), everything
+//                      in LDS; k_pnp_hyp is its 4-wave form for a round with one solver
+//   k_pnp_check_many   one block per (hypothesis, solver): CheckInliers (float/double
+//                      mix exactly as :352-384) -> inlier bytes + count
+//   k_pnp_refine_many  one block per solver: Refine() (:303-349) = EPnP on every inlier
+//                      of the best hypothesis (staged in LDS) + CheckInliers
+// There is one iterate path, pnp_run_many, for one solver or many: hypotheses are
+// computed a chunk at a time for every solver that needs them, and the host walks each
+// solver's hypotheses in order (best = first strict maximum, Refine at each hypothesis
+// reaching minInliers, return on the first successful Refine), which is iterate()
+// (:182-301) including its `mnIterations<maxIts || nCurrent<nIterations` loop condition.
+// orbx_pnp_iterate is that path with one run, its whole H as the first chunk.
 //
 // EPnP and the OpenCV 3.2 helpers it calls (cvMulTransposed, Jacobi cvSVD,
 // cvInvert/cvSolve through SVBkSb) use only IEEE + - * / sqrt in the same
@@ -27,13 +29,13 @@
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
-#include <cstdlib>
-#include <cstdio>
 #include <cstring>
 #include <mutex>
+#include <new>
 #include <vector>
 
 #include "../../include/orbx.h"
+#include "orbx_ransac.h"
 
 namespace orbx {
 
@@ -841,7 +843,6 @@ __device__ inline bool check_inlier(const PnpIn& in, const double* R, const doub
 }
 
 // ------------------------------------------------------------ kernels
-constexpr int kHypThreads = 256;  // 4 waves: the beta approximations run one per wave
 constexpr int kRefThreads = 256;
 constexpr int kRefineLdsPts = 2000;  // Refine stages up to this many inliers in LDS
 constexpr size_t kRefinePtBytes = 4 * 8 + 3 * 8 + 3 * 4 + 2 * 4;  // alphas, pcs/errors, pw, uv
@@ -870,12 +871,6 @@ __device__ __forceinline__ void pnp_hyp_body(const PnpIn& in, const int* __restr
   }
 }
 
-__global__ __launch_bounds__(kHypThreads) void k_pnp_hyp(PnpIn in, const int* __restrict__ sets, int set_size,
-                                                         double* __restrict__ poses) {
-  const int h = blockIdx.x;
-  pnp_hyp_body<kHypThreads>(in, sets + (size_t)h * set_size, set_size, poses + 12 * (size_t)h);
-}
-
 // CheckInliers (src/PnPsolver.cc:352-384) of one hypothesis -> mask + count.
 __device__ __forceinline__ void pnp_check_body(const PnpIn& in, const double* __restrict__ P,
                                                uint8_t* __restrict__ m, int* __restrict__ count) {
@@ -895,15 +890,9 @@ __device__ __forceinline__ void pnp_check_body(const PnpIn& in, const double* __
   if (threadIdx.x == 0) *count = red[0] + red[1] + red[2] + red[3];
 }
 
-__global__ __launch_bounds__(256) void k_pnp_check(PnpIn in, const double* __restrict__ poses,
-                                                   uint8_t* __restrict__ masks, int* __restrict__ counts) {
-  const int h = blockIdx.x;
-  pnp_check_body(in, poses + 12 * (size_t)h, masks + (size_t)h * in.N, counts + h);
-}
-
-// Many solvers in one launch (orbx_pnp_iterate_candidates / _many): grid (hypotheses
-// of the largest job, jobs); job j runs its hypotheses h0 .. h0+H-1 (their minimal
-// sets at sets[(h0 + h) * set_size], results at index h0 + h of its own arrays).
+// One launch for every solver of a round: grid (hypotheses of the largest job, jobs); job j
+// runs its hypotheses h0 .. h0+H-1 (their minimal sets at sets[(h0 + h) * set_size], results
+// at index h0 + h of its own arrays).
 struct PnpHypJob {
   PnpIn in;
   const int* sets;
@@ -914,7 +903,7 @@ struct PnpHypJob {
 };
 
 // throughput form: one wave per hypothesis (the three beta approximations in series on it), so
-// four hypotheses share a CU where the 4-wave latency form (whose VGPR budget allows one
+// four hypotheses share a CU where the 4-wave latency form below (whose VGPR budget allows one
 // block per CU) runs one
 constexpr int kHypManyThreads = 64;
 __global__ __launch_bounds__(kHypManyThreads) __attribute__((amdgpu_waves_per_eu(2))) void k_pnp_hyp_many(const PnpHypJob* __restrict__ jobs) {
@@ -922,6 +911,15 @@ __global__ __launch_bounds__(kHypManyThreads) __attribute__((amdgpu_waves_per_eu
   if ((int)blockIdx.x >= J.H) return;  // block-uniform
   const int h = J.h0 + blockIdx.x;
   pnp_hyp_body<kHypManyThreads>(J.in, J.sets + (size_t)h * J.set_size, J.set_size, J.poses + 12 * (size_t)h);
+}
+
+// latency form for a round with one job: 4 waves per hypothesis, the beta approximations one per
+// wave -- a lone solver's call is as long as its slowest hypothesis
+constexpr int kHypThreads = 256;
+__global__ __launch_bounds__(kHypThreads) void k_pnp_hyp(const PnpHypJob* __restrict__ jobs) {
+  const PnpHypJob& J = jobs[0];
+  const int h = J.h0 + blockIdx.x;
+  pnp_hyp_body<kHypThreads>(J.in, J.sets + (size_t)h * J.set_size, J.set_size, J.poses + 12 * (size_t)h);
 }
 
 __global__ __launch_bounds__(256) void k_pnp_check_many(const PnpHypJob* __restrict__ jobs) {
@@ -1008,14 +1006,6 @@ __device__ __forceinline__ void pnp_refine_body(const PnpRefJob& J) {
   }
 }
 
-template <bool kLds>
-__global__ __launch_bounds__(kRefThreads) void k_pnp_refine(PnpIn in, const uint8_t* __restrict__ best,
-                                                            int* __restrict__ idx, double* __restrict__ work,
-                                                            double* __restrict__ out, uint8_t* __restrict__ mask_out,
-                                                            int* __restrict__ count) {
-  pnp_refine_body<kLds>(PnpRefJob{in, best, idx, work, out, mask_out, count});
-}
-
 // one block per job
 template <bool kLds>
 __global__ __launch_bounds__(kRefThreads) void k_pnp_refine_many(const PnpRefJob* __restrict__ jobs) {
@@ -1059,60 +1049,21 @@ __global__ __launch_bounds__(256) void k_pnp_setup(const PnpSetupJob* __restrict
 }  // namespace orbx
 
 // ------------------------------------------------------------------ host / C ABI
-// One stream and one pinned readback block per device, shared by every
-// solver (the reference creates a PnPsolver per relocalisation candidate, so
-// creation must be cheap); each solver owns one stream-ordered allocation
-// (hipMallocAsync) holding all of its arrays.
+// One context per device (orbx_ransac.h), shared by every solver; each solver owns one
+// stream-ordered allocation (hipMallocAsync) holding all of its arrays.
 namespace {
 
-struct PnpDevice {
-  std::once_flag once;
-  hipError_t init_err = hipSuccess;
-  hipStream_t st = nullptr;
-  std::mutex mu;  // serialises iterate() calls that share the stream and readback block
-  void* pinned = nullptr;
-  size_t pinned_cap = 0;
-  void* dstage = nullptr;  // device staging of the batched calls: job records, minimal sets, counts
-  size_t dstage_cap = 0;
-  hipError_t dstage_reserve(size_t bytes) {
-    if (bytes <= dstage_cap) return hipSuccess;
-    if (dstage) (void)hipFree(dstage);
-    dstage = nullptr;
-    dstage_cap = 0;
-    hipError_t e = hipMalloc(&dstage, bytes);
-    if (e == hipSuccess) dstage_cap = bytes;
-    return e;
-  }
-  hipError_t pinned_reserve(size_t bytes) {
-    if (bytes <= pinned_cap) return hipSuccess;
-    if (pinned) (void)hipHostFree(pinned);
-    pinned = nullptr;
-    pinned_cap = 0;
-    hipError_t e = hipHostMalloc(&pinned, bytes, hipHostMallocDefault);
-    if (e == hipSuccess) pinned_cap = bytes;
-    return e;
-  }
-};
-PnpDevice g_pnp_dev[64];
+using orbx::align256;
+using orbx::RansacDevice;
 
-hipError_t pnp_device_init(int device) {
-  PnpDevice& d = g_pnp_dev[device];
-  std::call_once(d.once, [&] {
-    d.init_err = hipStreamCreateWithFlags(&d.st, hipStreamNonBlocking);
-    if (d.init_err == hipSuccess)
-      d.init_err = hipFuncSetAttribute((const void*)orbx::k_pnp_refine<true>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)(orbx::kRefineLdsPts * orbx::kRefinePtBytes));
-    if (d.init_err == hipSuccess)
-      d.init_err = hipFuncSetAttribute((const void*)orbx::k_pnp_refine_many<true>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)(orbx::kRefineLdsPts * orbx::kRefinePtBytes));
-    if (d.init_err == hipSuccess) d.init_err = d.pinned_reserve(1 << 16);
-  });
-  return d.init_err;
+RansacDevice g_pnp_dev[64];
+
+hipError_t pnp_kernel_setup() {
+  return hipFuncSetAttribute((const void*)orbx::k_pnp_refine_many<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                             (int)(orbx::kRefineLdsPts * orbx::kRefinePtBytes));
 }
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+orbx_status pnp_device_check(int device) { return orbx::ransac_device_check(g_pnp_dev, device, pnp_kernel_setup); }
 
 }  // namespace
 
@@ -1124,17 +1075,15 @@ struct orbx_pnp {
   double prob;
   int min_inliers, max_its, min_set;
   float epsilon;
-  // device (one allocation): correspondences, refine buffers, per-hypothesis buffers
+  // device (one allocation): correspondences, best set, refine buffers, per-hypothesis buffers
   uint8_t* d_mem = nullptr;
   float *d_p3d = nullptr, *d_p2d = nullptr, *d_maxerr = nullptr;
-  uint8_t *d_best = nullptr, *d_refmask = nullptr;
+  uint8_t* d_best = nullptr;
+  double* d_best_pose = nullptr;  // R t (12) of the best set
   int* d_idx = nullptr;
   double* d_rwork = nullptr;
-  double* d_res = nullptr;  // refine result: R t (12) + count; best pose (12)
-  int* d_sets = nullptr;
   double* d_poses = nullptr;
   uint8_t* d_masks = nullptr;
-  int* d_counts = nullptr;
   int cap_hyp = 0;
   // iterate() state
   int iterations = 0, best_inliers = 0;
@@ -1156,37 +1105,29 @@ struct orbx_pnp {
     d_p2d = (float*)take(8 * nn);
     d_maxerr = (float*)take(4 * nn);
     d_best = take(nn);
-    d_refmask = take(nn);
+    d_best_pose = (double*)take(8 * 12);
     d_idx = (int*)take(4 * nn);
     d_rwork = (double*)take(orbx::kRefinePtBytes * nn);  // global-fallback refine: same per-point layout
-    d_res = (double*)take(8 * 32);
-    d_sets = (int*)take(sizeof(int) * (size_t)cap * orbx::kPnpMaxSet);
     d_poses = (double*)take(sizeof(double) * 12 * (size_t)cap);
     d_masks = take((size_t)cap * nn);
-    d_counts = (int*)take(sizeof(int) * (size_t)cap);
     return o;
   }
-  // grows the per-hypothesis buffers to H, keeping correspondences, best mask and results
+  // grows the per-hypothesis buffers to H, keeping the correspondences, the best mask and the
+  // best pose (the head of the layout, up to d_idx)
   hipError_t ensure_cap(int H) {
     if (H <= cap_hyp) return hipSuccess;
     uint8_t* old = d_mem;
-    const size_t keep = (uint8_t*)d_best - (uint8_t*)d_p3d;
-    const size_t best_off = (uint8_t*)d_best - old, res_off = (uint8_t*)d_res - old;
-    d_mem = nullptr;
-    const size_t bytes = layout(H, nullptr);
-    hipError_t e = hipMallocAsync((void**)&d_mem, bytes, st);
-    if (e != hipSuccess) return e;
-    layout(H, d_mem);
-    cap_hyp = H;
-    if ((e = hipMemcpyAsync(d_p3d, old, keep, hipMemcpyDeviceToDevice, st)) != hipSuccess) return e;
-    if ((e = hipMemcpyAsync(d_best, old + best_off, std::max(N, 1), hipMemcpyDeviceToDevice, st)) != hipSuccess)
+    const size_t keep = (uint8_t*)d_idx - (uint8_t*)d_p3d;
+    hipError_t e = alloc(H);
+    if (e != hipSuccess) {  // the solver stays usable at its old capacity
+      d_mem = old;
+      layout(cap_hyp, old);
       return e;
-    if ((e = hipMemcpyAsync(d_res, old + res_off, 8 * 32, hipMemcpyDeviceToDevice, st)) != hipSuccess) return e;
+    }
+    if ((e = hipMemcpyAsync(d_mem, old, keep, hipMemcpyDeviceToDevice, st)) != hipSuccess) return e;
     return hipFreeAsync(old, st);
   }
-  hipError_t alloc(int cap) {  // (re)allocates d_mem; the correspondences are re-uploaded by the caller
-    if (d_mem) (void)hipFreeAsync(d_mem, st);
-    d_mem = nullptr;
+  hipError_t alloc(int cap) {  // a fresh d_mem for cap hypotheses; the caller fills or frees the old one
     const size_t bytes = layout(cap, nullptr);
     hipError_t e = hipMallocAsync((void**)&d_mem, bytes, st);
     if (e != hipSuccess) return e;
@@ -1206,31 +1147,9 @@ void pose_to_Tcw(const double* P, float T[16]) {  // Rcw/tcw convertTo(CV_32F) i
   }
 }
 
-#define PNP_CHECK(x)                             \
-  do {                                           \
-    if ((x) != hipSuccess) return ORBX_ERR_HIP;  \
-  } while (0)
-
-}  // namespace
-
-extern "C" {
-
-}  // extern "C"
-
-namespace {
-
 orbx_status pnp_check_problem(const orbx_pnp_problem* p, const orbx_pnp_params* prm) {
   if (!p || !prm || p->n < 0 || (p->n > 0 && (!p->p3d || !p->p2d || !p->sigma2))) return ORBX_ERR_ARG;
   if (prm->min_set < 1 || prm->min_set > orbx::kPnpMaxSet) return ORBX_ERR_ARG;
-  return ORBX_OK;
-}
-
-orbx_status pnp_device_check(int device) {
-  int nd = 0;
-  if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) return ORBX_ERR_NODEV;
-  if (device < 0 || device >= nd || device >= 64) return ORBX_ERR_ARG;
-  if (hipSetDevice(device) != hipSuccess) return ORBX_ERR_HIP;
-  if (pnp_device_init(device) != hipSuccess) return ORBX_ERR_HIP;
   return ORBX_OK;
 }
 
@@ -1281,33 +1200,18 @@ void pnp_stage_problem(const orbx_pnp* h, const orbx_pnp_problem* p, const orbx_
   for (int i = 0; i < n; i++) me[i] = p->sigma2[i] * prm->th2;
 }
 
+void pnp_free(orbx_pnp* h) {
+  if (!h) return;
+  if (h->d_mem) (void)hipFreeAsync(h->d_mem, h->st);
+  delete h;
+}
+
 }  // namespace
 
 extern "C" {
 
 orbx_status orbx_pnp_create(const orbx_pnp_problem* p, const orbx_pnp_params* prm, int device, orbx_pnp** out) {
-  orbx_status s = pnp_check_problem(p, prm);
-  if (s != ORBX_OK || !out) return s != ORBX_OK ? s : ORBX_ERR_ARG;
-  *out = nullptr;
-  if ((s = pnp_device_check(device)) != ORBX_OK) return s;
-  orbx_pnp* h = pnp_new(p, prm, device);
-  if (!h) return ORBX_ERR_HIP;
-  const int n = p->n;
-  hipError_t e = h->alloc(std::max(h->max_its, 8));
-  if (e == hipSuccess && n > 0) {
-    // one upload: p3d | p2d | maxerr are consecutive in the layout
-    std::vector<uint8_t> stage((uint8_t*)h->d_best - (uint8_t*)h->d_p3d);
-    pnp_stage_problem(h, p, prm, stage.data());
-    e = hipMemcpyAsync(h->d_p3d, stage.data(), stage.size(), hipMemcpyHostToDevice, h->st);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->st);  // stage is pageable and local
-  }
-  if (e != hipSuccess) {
-    if (h->d_mem) (void)hipFreeAsync(h->d_mem, h->st);
-    delete h;
-    return ORBX_ERR_HIP;
-  }
-  *out = h;
-  return ORBX_OK;
+  return orbx_pnp_create_many(p, 1, prm, device, out);
 }
 
 orbx_status orbx_pnp_create_many(const orbx_pnp_problem* problems, int n, const orbx_pnp_params* prm, int device,
@@ -1321,15 +1225,11 @@ orbx_status orbx_pnp_create_many(const orbx_pnp_problem* problems, int n, const 
   if (n == 0) return ORBX_OK;
   orbx_status s = pnp_device_check(device);
   if (s != ORBX_OK) return s;
-  PnpDevice& dev = g_pnp_dev[device];
+  RansacDevice& dev = g_pnp_dev[device];
   std::lock_guard<std::mutex> lock(dev.mu);
   std::vector<orbx_pnp*> hs(n, nullptr);
   auto fail = [&](orbx_status code) {
-    for (orbx_pnp* h : hs)
-      if (h) {
-        if (h->d_mem) (void)hipFreeAsync(h->d_mem, h->st);
-        delete h;
-      }
+    for (orbx_pnp* h : hs) pnp_free(h);
     return code;
   };
   size_t stage = 0;
@@ -1355,8 +1255,14 @@ orbx_status orbx_pnp_create_many(const orbx_pnp_problem* problems, int n, const 
     o += align256(len);
   }
   hipStream_t st = dev.st;
-  if (hipMemcpyAsync(dp, hp, bytes, hipMemcpyHostToDevice, st) != hipSuccess) return fail(ORBX_ERR_HIP);
-  hipLaunchKernelGGL(orbx::k_pnp_gather, dim3(n), dim3(256), 0, st, (const orbx::PnpGatherJob*)dp);
+  if (n == 1) {  // one destination range: uploaded in place, nothing to gather
+    if (jobs[0].n > 0 &&
+        hipMemcpyAsync(jobs[0].dst, hp + off_data, jobs[0].n, hipMemcpyHostToDevice, st) != hipSuccess)
+      return fail(ORBX_ERR_HIP);
+  } else {
+    if (hipMemcpyAsync(dp, hp, bytes, hipMemcpyHostToDevice, st) != hipSuccess) return fail(ORBX_ERR_HIP);
+    hipLaunchKernelGGL(orbx::k_pnp_gather, dim3(n), dim3(256), 0, st, (const orbx::PnpGatherJob*)dp);
+  }
   if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return fail(ORBX_ERR_HIP);
   for (int i = 0; i < n; i++) out[i] = hs[i];
   return ORBX_OK;
@@ -1374,15 +1280,11 @@ orbx_status orbx_pnp_create_many_device(const float* d_p3d, const float* d_p2d, 
   }
   orbx_status s = pnp_device_check(device);
   if (s != ORBX_OK) return s;
-  PnpDevice& dev = g_pnp_dev[device];
+  RansacDevice& dev = g_pnp_dev[device];
   std::lock_guard<std::mutex> lock(dev.mu);
   std::vector<orbx_pnp*> hs(n, nullptr);
   auto fail = [&](orbx_status code) {
-    for (orbx_pnp* h : hs)
-      if (h) {
-        if (h->d_mem) (void)hipFreeAsync(h->d_mem, h->st);
-        delete h;
-      }
+    for (orbx_pnp* h : hs) pnp_free(h);
     return code;
   };
   const size_t bytes = n * sizeof(orbx::PnpSetupJob);
@@ -1409,8 +1311,7 @@ orbx_status orbx_pnp_create_many_device(const float* d_p3d, const float* d_p2d, 
 orbx_status orbx_pnp_destroy(orbx_pnp* h) {
   if (!h) return ORBX_ERR_ARG;
   (void)hipSetDevice(h->device);
-  if (h->d_mem) (void)hipFreeAsync(h->d_mem, h->st);
-  delete h;
+  pnp_free(h);
   return ORBX_OK;
 }
 
@@ -1418,18 +1319,18 @@ orbx_status orbx_pnp_set_ransac_parameters(orbx_pnp* h, const float* sigma2, con
   if (!h || !prm || (h->N > 0 && !sigma2)) return ORBX_ERR_ARG;
   if (prm->min_set < 1 || prm->min_set > orbx::kPnpMaxSet) return ORBX_ERR_ARG;
   if (hipSetDevice(h->device) != hipSuccess) return ORBX_ERR_HIP;
-  PnpDevice& dev = g_pnp_dev[h->device];
+  RansacDevice& dev = g_pnp_dev[h->device];
   std::lock_guard<std::mutex> lock(dev.mu);
   // src/PnPsolver.cc:136-179 recomputes the parameters in place: mnIterations, mnBestInliers and
   // mvbBestInliers (and the best pose) are kept; mvMaxError = sigma2 * th2 is rebuilt
   pnp_derive(h, prm);
   h->refine_valid = false;  // Refine() succeeds on "> mRansacMinInliers", which may have changed
   if (h->N > 0) {
-    PNP_CHECK(dev.pinned_reserve(4 * (size_t)h->N));
+    RANSAC_CHECK(dev.pinned_reserve(4 * (size_t)h->N));
     float* me = (float*)dev.pinned;
     for (int i = 0; i < h->N; i++) me[i] = sigma2[i] * prm->th2;
-    PNP_CHECK(hipMemcpyAsync(h->d_maxerr, me, 4 * (size_t)h->N, hipMemcpyHostToDevice, h->st));
-    PNP_CHECK(hipStreamSynchronize(h->st));  // the pinned block is reused by the next call
+    RANSAC_CHECK(hipMemcpyAsync(h->d_maxerr, me, 4 * (size_t)h->N, hipMemcpyHostToDevice, h->st));
+    RANSAC_CHECK(hipStreamSynchronize(h->st));  // the pinned block is reused by the next call
   }
   return ORBX_OK;
 }
@@ -1442,112 +1343,14 @@ orbx_status orbx_pnp_get_params(const orbx_pnp* h, int* min_inliers, int* max_it
   return ORBX_OK;
 }
 
-orbx_status orbx_pnp_iterate(orbx_pnp* h, int n_iterations, const int32_t* rand_vals, int n_rand, int* used,
-                             int* no_more, float Tcw[16], uint8_t* inliers, int* n_inliers, int* found) {
-  if (!h || !used || !no_more || !Tcw || !n_inliers || !found || (h->N > 0 && !inliers) || n_rand < 0 ||
-      (n_rand > 0 && !rand_vals))
-    return ORBX_ERR_ARG;
-  *used = 0;
-  *no_more = 0;
-  *n_inliers = 0;
-  *found = 0;
-  const int N = h->N, ms = h->min_set;
-  if (N < h->min_inliers) {
-    *no_more = 1;
-    return ORBX_OK;
-  }
-  if (hipSetDevice(h->device) != hipSuccess) return ORBX_ERR_HIP;
-  // hypotheses this call may run: while (iterations < maxIts || current < nIterations)
-  const int H = std::max(h->max_its - h->iterations, n_iterations);
-  if (H <= 0) return ORBX_OK;
-  if ((long long)H * ms > n_rand) return ORBX_ERR_CAPACITY;
-  PnpDevice& dev = g_pnp_dev[h->device];
-  std::lock_guard<std::mutex> lock(dev.mu);
-  const size_t pin_bytes = std::max(sizeof(int) * (size_t)H * ms, sizeof(int) * (size_t)H) + 8 * 32;
-  PNP_CHECK(dev.pinned_reserve(pin_bytes));
-  PNP_CHECK(h->ensure_cap(H));  // keeps the correspondences
-  // DUtils::Random::RandomInt(0, size-1) on the rand() stream + swap-remove
-  int* sets = (int*)dev.pinned;
-  std::vector<int> avail(N);
-  for (int k = 0; k < H; k++) {
-    for (int i = 0; i < N; i++) avail[i] = i;
-    int size = N;
-    for (int i = 0; i < ms; i++) {
-      const int randi = (int)(((double)rand_vals[k * ms + i] / ((double)RAND_MAX + 1.0)) * size);
-      sets[(size_t)k * ms + i] = avail[randi];
-      avail[randi] = avail[size - 1];
-      size--;
-    }
-  }
-  hipStream_t st = h->st;
-  PNP_CHECK(hipMemcpyAsync(h->d_sets, sets, sizeof(int) * (size_t)H * ms, hipMemcpyHostToDevice, st));
-  const orbx::PnpIn in = h->in();
-  hipLaunchKernelGGL(orbx::k_pnp_hyp, dim3(H), dim3(orbx::kHypThreads), 0, st, in, h->d_sets, ms, h->d_poses);
-  hipLaunchKernelGGL(orbx::k_pnp_check, dim3(H), dim3(256), 0, st, in, h->d_poses, h->d_masks, h->d_counts);
-  PNP_CHECK(hipGetLastError());
-  int* counts = (int*)dev.pinned;  // the sets were consumed by the copy above (stream order)
-  PNP_CHECK(hipMemcpyAsync(counts, h->d_counts, sizeof(int) * H, hipMemcpyDeviceToHost, st));
-  PNP_CHECK(hipStreamSynchronize(st));
-  double* res = (double*)((uint8_t*)dev.pinned + align256(sizeof(int) * (size_t)H));
-  int cur = 0;
-  for (int k = 0; k < H && (h->iterations < h->max_its || cur < n_iterations); k++) {
-    cur++;
-    h->iterations++;
-    *used += ms;
-    if (counts[k] < h->min_inliers) continue;
-    if (counts[k] > h->best_inliers) {  // new best: mask + pose stay on the device
-      h->best_inliers = counts[k];
-      PNP_CHECK(hipMemcpyAsync(h->d_best, h->d_masks + (size_t)k * N, N, hipMemcpyDeviceToDevice, st));
-      PNP_CHECK(hipMemcpyAsync(h->d_res + 16, h->d_poses + 12 * (size_t)k, 12 * sizeof(double),
-                               hipMemcpyDeviceToDevice, st));
-      h->refine_valid = false;
-    }
-    if (h->refine_valid) continue;  // same best set: Refine() fails again
-    if (h->best_inliers <= orbx::kRefineLdsPts)  // the refined set is the best mask
-      hipLaunchKernelGGL(orbx::k_pnp_refine<true>, dim3(1), dim3(orbx::kRefThreads),
-                         orbx::kRefineLdsPts * orbx::kRefinePtBytes, st, in, h->d_best, h->d_idx, h->d_rwork,
-                         h->d_res, h->d_refmask, (int*)(h->d_res + 12));
-    else
-      hipLaunchKernelGGL(orbx::k_pnp_refine<false>, dim3(1), dim3(orbx::kRefThreads), 0, st, in, h->d_best, h->d_idx,
-                         h->d_rwork, h->d_res, h->d_refmask, (int*)(h->d_res + 12));
-    PNP_CHECK(hipGetLastError());
-    PNP_CHECK(hipMemcpyAsync(res, h->d_res, 13 * sizeof(double), hipMemcpyDeviceToHost, st));
-    PNP_CHECK(hipStreamSynchronize(st));
-    const int rc = *(const int*)(res + 12);
-    if (rc > h->min_inliers) {
-      PNP_CHECK(hipMemcpyAsync(inliers, h->d_refmask, N, hipMemcpyDeviceToHost, st));
-      PNP_CHECK(hipStreamSynchronize(st));
-      pose_to_Tcw(res, Tcw);
-      *n_inliers = rc;
-      *found = 1;
-      return ORBX_OK;
-    }
-    h->refine_valid = true;
-  }
-  if (h->iterations >= h->max_its) {
-    *no_more = 1;
-    if (h->best_inliers >= h->min_inliers) {
-      PNP_CHECK(hipMemcpyAsync(res, h->d_res + 16, 12 * sizeof(double), hipMemcpyDeviceToHost, st));
-      PNP_CHECK(hipMemcpyAsync(inliers, h->d_best, N, hipMemcpyDeviceToHost, st));
-      PNP_CHECK(hipStreamSynchronize(st));
-      pose_to_Tcw(res, h->best_Tcw);
-      std::memcpy(Tcw, h->best_Tcw, sizeof(float) * 16);
-      *n_inliers = h->best_inliers;
-      *found = 1;
-    }
-  }
-  return ORBX_OK;
-}
-
 }  // extern "C"
 
-// ---------------------------------------------------------------- many solvers
-// The walk of PnPsolver::iterate (the loop above) over several solvers at once.
-// Hypotheses are computed a chunk at a time for every solver that needs them
-// (one k_pnp_hyp_many + one k_pnp_check_many launch per round, minimal sets and
-// job records in one upload, counts in one readback), each solver's walk runs on
-// the host exactly as in orbx_pnp_iterate, and the Refine() calls the walks ask
-// for in the same round go out as one k_pnp_refine_many launch.
+// ---------------------------------------------------------------- iterate
+// PnPsolver::iterate (:182-301) for one solver or several at once.  Hypotheses are
+// computed a chunk at a time for every solver that needs them (one k_pnp_hyp_many + one
+// k_pnp_check_many launch per round, minimal sets and job records in one upload, counts
+// in one readback), each solver's walk runs on the host, and the Refine() calls the
+// walks ask for in the same round go out as one k_pnp_refine_many launch.
 namespace {
 
 struct PnpRun {
@@ -1557,10 +1360,10 @@ struct PnpRun {
   int k = 0;                    // next hypothesis to walk
   int launched = 0;             // hypotheses [0, launched) have counts
   int cur = 0, used = 0;
-  bool eligible = true, done = false, pending = false, read_best = false;
-  int best_k = -1;  // hypothesis of this call holding the best set (-1: d_best / d_res+16 of an earlier call)
+  bool done = false, pending = false, read_best = false;
+  int best_k = -1;  // hypothesis of this call holding the best set (-1: d_best / d_best_pose of an earlier call)
   const uint8_t* best_mask() const { return best_k >= 0 ? h->d_masks + (size_t)best_k * h->N : h->d_best; }
-  const double* best_pose() const { return best_k >= 0 ? h->d_poses + 12 * (size_t)best_k : h->d_res + 16; }
+  const double* best_pose() const { return best_k >= 0 ? h->d_poses + 12 * (size_t)best_k : h->d_best_pose; }
   std::vector<int> counts;
   orbx_pnp_result* out = nullptr;
   uint8_t* inliers = nullptr;
@@ -1587,7 +1390,7 @@ orbx_status pnp_begin(PnpRun& r, int n_iterations) {
 }
 
 // hypotheses [launched, launched + c) of every run in `rs` with c > 0
-orbx_status pnp_launch_chunks(PnpDevice& dev, hipStream_t st, std::vector<std::pair<PnpRun*, int>>& rs) {
+orbx_status pnp_launch_chunks(RansacDevice& dev, hipStream_t st, std::vector<std::pair<PnpRun*, int>>& rs) {
   if (rs.empty()) return ORBX_OK;
   const size_t nj = rs.size();
   size_t nsets = 0, ncounts = 0;
@@ -1600,8 +1403,8 @@ orbx_status pnp_launch_chunks(PnpDevice& dev, hipStream_t st, std::vector<std::p
   const size_t off_sets = align256(nj * sizeof(orbx::PnpHypJob));
   const size_t off_counts = off_sets + align256(nsets * sizeof(int));
   const size_t bytes = off_counts + align256(ncounts * sizeof(int));
-  PNP_CHECK(dev.pinned_reserve(bytes));
-  PNP_CHECK(dev.dstage_reserve(bytes));
+  RANSAC_CHECK(dev.pinned_reserve(bytes));
+  RANSAC_CHECK(dev.dstage_reserve(bytes));
   uint8_t* hp = (uint8_t*)dev.pinned;
   uint8_t* dp = (uint8_t*)dev.dstage;
   orbx::PnpHypJob* jobs = (orbx::PnpHypJob*)hp;
@@ -1611,19 +1414,7 @@ orbx_status pnp_launch_chunks(PnpDevice& dev, hipStream_t st, std::vector<std::p
     PnpRun& r = *rs[j].first;
     orbx_pnp* h = r.h;
     const int c = rs[j].second, ms = h->min_set, N = h->N, h0 = r.launched;
-    // DUtils::Random::RandomInt(0, size-1) on the rand() stream + swap-remove (src/PnPsolver.cc:214-229)
-    std::vector<int> avail(N);
-    for (int k = 0; k < c; k++) {
-      for (int i = 0; i < N; i++) avail[i] = i;
-      int size = N;
-      for (int i = 0; i < ms; i++) {
-        const int32_t v = r.rv[(size_t)(h0 + k) * ms + i];
-        const int randi = (int)(((double)v / ((double)RAND_MAX + 1.0)) * size);
-        sets[so + (size_t)k * ms + i] = avail[randi];
-        avail[randi] = avail[size - 1];
-        size--;
-      }
-    }
+    orbx::ransac_sample_sets(r.rv + (size_t)h0 * ms, c, ms, N, sets + so);  // src/PnPsolver.cc:214-229
     orbx::PnpHypJob& J = jobs[j];
     J.in = h->in();
     J.sets = (const int*)(dp + off_sets) + so - (size_t)h0 * ms;  // indexed by absolute hypothesis
@@ -1636,14 +1427,17 @@ orbx_status pnp_launch_chunks(PnpDevice& dev, hipStream_t st, std::vector<std::p
     so += (size_t)c * ms;
     co += c;
   }
-  PNP_CHECK(hipMemcpyAsync(dp, hp, off_counts, hipMemcpyHostToDevice, st));
+  RANSAC_CHECK(hipMemcpyAsync(dp, hp, off_counts, hipMemcpyHostToDevice, st));
   const orbx::PnpHypJob* dj = (const orbx::PnpHypJob*)dp;
-  hipLaunchKernelGGL(orbx::k_pnp_hyp_many, dim3(maxc, nj), dim3(orbx::kHypManyThreads), 0, st, dj);
+  if (nj == 1)
+    hipLaunchKernelGGL(orbx::k_pnp_hyp, dim3(maxc), dim3(orbx::kHypThreads), 0, st, dj);
+  else
+    hipLaunchKernelGGL(orbx::k_pnp_hyp_many, dim3(maxc, nj), dim3(orbx::kHypManyThreads), 0, st, dj);
   hipLaunchKernelGGL(orbx::k_pnp_check_many, dim3(maxc, nj), dim3(256), 0, st, dj);
-  PNP_CHECK(hipGetLastError());
+  RANSAC_CHECK(hipGetLastError());
   int* hc = (int*)(hp + off_counts);
-  PNP_CHECK(hipMemcpyAsync(hc, dp + off_counts, ncounts * sizeof(int), hipMemcpyDeviceToHost, st));
-  PNP_CHECK(hipStreamSynchronize(st));
+  RANSAC_CHECK(hipMemcpyAsync(hc, dp + off_counts, ncounts * sizeof(int), hipMemcpyDeviceToHost, st));
+  RANSAC_CHECK(hipStreamSynchronize(st));
   co = 0;
   for (auto& q : rs) {
     PnpRun& r = *q.first;
@@ -1654,9 +1448,9 @@ orbx_status pnp_launch_chunks(PnpDevice& dev, hipStream_t st, std::vector<std::p
   return ORBX_OK;
 }
 
-// the walk of orbx_pnp_iterate from hypothesis r.k: stops at a Refine() request,
-// at the end of the launched hypotheses, or at the end of the call
-orbx_status pnp_walk(PnpRun& r) {
+// iterate()'s loop body from hypothesis r.k: stops at a Refine() request, at the end of
+// the launched hypotheses, or at the end of the call
+void pnp_walk(PnpRun& r) {
   orbx_pnp* h = r.h;
   while (!r.pending && r.k < r.launched) {
     const int k = r.k++;
@@ -1672,7 +1466,6 @@ orbx_status pnp_walk(PnpRun& r) {
     if (h->refine_valid) continue;  // same best set: Refine() fails again
     r.pending = true;
   }
-  return ORBX_OK;
 }
 
 // the end of iterate() once all H hypotheses were walked without a refined pose
@@ -1691,15 +1484,15 @@ void pnp_finish(PnpRun& r) {
 }
 
 // best pose (12 doubles) + best mask of every run in `rs`: one gather launch, one readback
-orbx_status pnp_read_best(PnpDevice& dev, hipStream_t st, std::vector<PnpRun*>& rs) {
+orbx_status pnp_read_best(RansacDevice& dev, hipStream_t st, std::vector<PnpRun*>& rs) {
   if (rs.empty()) return ORBX_OK;
   const size_t nj = 2 * rs.size();
   size_t data = 0;
   for (PnpRun* r : rs) data += 96 + align256((size_t)r->h->N);
   const size_t off_data = align256(nj * sizeof(orbx::PnpGatherJob));
   const size_t bytes = off_data + data;
-  PNP_CHECK(dev.pinned_reserve(bytes));
-  PNP_CHECK(dev.dstage_reserve(bytes));
+  RANSAC_CHECK(dev.pinned_reserve(bytes));
+  RANSAC_CHECK(dev.dstage_reserve(bytes));
   uint8_t* hp = (uint8_t*)dev.pinned;
   uint8_t* dp = (uint8_t*)dev.dstage;
   orbx::PnpGatherJob* jobs = (orbx::PnpGatherJob*)hp;
@@ -1710,11 +1503,11 @@ orbx_status pnp_read_best(PnpDevice& dev, hipStream_t st, std::vector<PnpRun*>& 
     jobs[2 * j + 1] = orbx::PnpGatherJob{rs[j]->best_mask(), dp + o + 96, h->N};
     o += 96 + align256((size_t)h->N);
   }
-  PNP_CHECK(hipMemcpyAsync(dp, hp, nj * sizeof(orbx::PnpGatherJob), hipMemcpyHostToDevice, st));
+  RANSAC_CHECK(hipMemcpyAsync(dp, hp, nj * sizeof(orbx::PnpGatherJob), hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(orbx::k_pnp_gather, dim3(nj), dim3(256), 0, st, (const orbx::PnpGatherJob*)dp);
-  PNP_CHECK(hipGetLastError());
-  PNP_CHECK(hipMemcpyAsync(hp + off_data, dp + off_data, data, hipMemcpyDeviceToHost, st));
-  PNP_CHECK(hipStreamSynchronize(st));
+  RANSAC_CHECK(hipGetLastError());
+  RANSAC_CHECK(hipMemcpyAsync(hp + off_data, dp + off_data, data, hipMemcpyDeviceToHost, st));
+  RANSAC_CHECK(hipStreamSynchronize(st));
   o = off_data;
   for (PnpRun* r : rs) {
     orbx_pnp* h = r->h;
@@ -1728,7 +1521,7 @@ orbx_status pnp_read_best(PnpDevice& dev, hipStream_t st, std::vector<PnpRun*>& 
   return ORBX_OK;
 }
 
-orbx_status pnp_refine_round(PnpDevice& dev, hipStream_t st, std::vector<PnpRun*>& pend) {
+orbx_status pnp_refine_round(RansacDevice& dev, hipStream_t st, std::vector<PnpRun*>& pend) {
   if (pend.empty()) return ORBX_OK;
   const size_t nj = pend.size();
   // staging: job records | per job 16 doubles (R t, count) | per job its refined mask
@@ -1737,8 +1530,8 @@ orbx_status pnp_refine_round(PnpDevice& dev, hipStream_t st, std::vector<PnpRun*
   const size_t off_res = align256(nj * sizeof(orbx::PnpRefJob));
   const size_t off_mask = off_res + align256(nj * 16 * sizeof(double));
   const size_t bytes = off_mask + masks;
-  PNP_CHECK(dev.pinned_reserve(bytes));
-  PNP_CHECK(dev.dstage_reserve(bytes));
+  RANSAC_CHECK(dev.pinned_reserve(bytes));
+  RANSAC_CHECK(dev.dstage_reserve(bytes));
   uint8_t* hp = (uint8_t*)dev.pinned;
   uint8_t* dp = (uint8_t*)dev.dstage;
   orbx::PnpRefJob* jobs = (orbx::PnpRefJob*)hp;
@@ -1758,7 +1551,7 @@ orbx_status pnp_refine_round(PnpDevice& dev, hipStream_t st, std::vector<PnpRun*
     jobs[j] = orbx::PnpRefJob{h->in(), order[j]->best_mask(), h->d_idx, h->d_rwork, out, dp + mo, (int*)(out + 12)};
     mo += align256((size_t)h->N);
   }
-  PNP_CHECK(hipMemcpyAsync(dp, hp, nj * sizeof(orbx::PnpRefJob), hipMemcpyHostToDevice, st));
+  RANSAC_CHECK(hipMemcpyAsync(dp, hp, nj * sizeof(orbx::PnpRefJob), hipMemcpyHostToDevice, st));
   const orbx::PnpRefJob* dj = (const orbx::PnpRefJob*)dp;
   if (n_lds > 0)
     hipLaunchKernelGGL(orbx::k_pnp_refine_many<true>, dim3(n_lds), dim3(orbx::kRefThreads),
@@ -1766,9 +1559,9 @@ orbx_status pnp_refine_round(PnpDevice& dev, hipStream_t st, std::vector<PnpRun*
   if ((int)nj > n_lds)
     hipLaunchKernelGGL(orbx::k_pnp_refine_many<false>, dim3((int)nj - n_lds), dim3(orbx::kRefThreads), 0, st,
                        dj + n_lds);
-  PNP_CHECK(hipGetLastError());
-  PNP_CHECK(hipMemcpyAsync(hp + off_res, dp + off_res, bytes - off_res, hipMemcpyDeviceToHost, st));
-  PNP_CHECK(hipStreamSynchronize(st));
+  RANSAC_CHECK(hipGetLastError());
+  RANSAC_CHECK(hipMemcpyAsync(hp + off_res, dp + off_res, bytes - off_res, hipMemcpyDeviceToHost, st));
+  RANSAC_CHECK(hipStreamSynchronize(st));
   const double* res = (const double*)(hp + off_res);
   for (size_t j = 0; j < nj; j++) {
     PnpRun& r = *order[j];
@@ -1790,11 +1583,12 @@ orbx_status pnp_refine_round(PnpDevice& dev, hipStream_t st, std::vector<PnpRun*
 
 // shared: all runs draw from one stream in order and the call stops at the first run
 // that returns a pose (Tracking::Relocalization's candidate loop); otherwise the runs
-// are independent and all of them complete.
-orbx_status pnp_run_many(std::vector<PnpRun>& runs, bool shared, int* stopped) {
+// are independent and all of them complete.  first_chunk: hypotheses of a run's first round
+// (kPnpFirstChunk; the lone entry passes its whole H, measured in profiles/pnp_one_path.txt).
+orbx_status pnp_run_many(std::vector<PnpRun>& runs, bool shared, int* stopped, int first_chunk) {
   if (runs.empty()) return ORBX_OK;
   const int device = runs[0].h->device;
-  PnpDevice& dev = g_pnp_dev[device];
+  RansacDevice& dev = g_pnp_dev[device];
   hipStream_t st = dev.st;
   std::vector<PnpRun*> best_reads;
   const int nr = (int)runs.size();
@@ -1821,7 +1615,7 @@ orbx_status pnp_run_many(std::vector<PnpRun>& runs, bool shared, int* stopped) {
       // the first chunk, then everything left: a solver still without a pose after its first
       // hypotheses most often runs all of them (no set reaches minInliers), and one launch of
       // them beats a chain of doubling rounds
-      const int c = r.launched == 0 ? std::min(r.H, kPnpFirstChunk) : r.H - r.launched;
+      const int c = r.launched == 0 ? std::min(r.H, first_chunk) : r.H - r.launched;
       chunk.push_back({&r, c});
     }
     first_round = false;
@@ -1832,7 +1626,7 @@ orbx_status pnp_run_many(std::vector<PnpRun>& runs, bool shared, int* stopped) {
     for (int i = 0; i < nr; i++) {
       PnpRun& r = runs[i];
       if (r.done || (shared && i != active)) continue;
-      if ((s = pnp_walk(r)) != ORBX_OK) return s;
+      pnp_walk(r);
       if (r.pending) {
         pend.push_back(&r);
       } else if (r.k >= r.H) {
@@ -1850,10 +1644,7 @@ orbx_status pnp_run_many(std::vector<PnpRun>& runs, bool shared, int* stopped) {
     if ((s = pnp_read_best(dev, st, best_reads)) != ORBX_OK) return s;
     bool all_done = true;
     for (int i = 0; i < nr; i++) all_done = all_done && runs[i].done;
-    if (!shared && all_done) break;
-    if (shared && all_done) {
-      // fall through to the stop scan at the top
-    }
+    if (!shared && all_done) break;  // shared: the stop scan at the top ends the call
   }
   // persist the best set of every solver whose best now comes from this call (the next call
   // reuses the hypothesis buffers): one gather launch
@@ -1861,19 +1652,19 @@ orbx_status pnp_run_many(std::vector<PnpRun>& runs, bool shared, int* stopped) {
   for (PnpRun& r : runs)
     if (r.best_k >= 0) {
       keep.push_back(orbx::PnpGatherJob{r.best_mask(), r.h->d_best, r.h->N});
-      keep.push_back(orbx::PnpGatherJob{(const uint8_t*)r.best_pose(), (uint8_t*)(r.h->d_res + 16), 96});
+      keep.push_back(orbx::PnpGatherJob{(const uint8_t*)r.best_pose(), (uint8_t*)r.h->d_best_pose, 96});
       r.best_k = -1;
     }
   if (!keep.empty()) {
     const size_t bytes = keep.size() * sizeof(orbx::PnpGatherJob);
-    PNP_CHECK(dev.pinned_reserve(bytes));
-    PNP_CHECK(dev.dstage_reserve(bytes));
+    RANSAC_CHECK(dev.pinned_reserve(bytes));
+    RANSAC_CHECK(dev.dstage_reserve(bytes));
     std::memcpy(dev.pinned, keep.data(), bytes);
-    PNP_CHECK(hipMemcpyAsync(dev.dstage, dev.pinned, bytes, hipMemcpyHostToDevice, st));
+    RANSAC_CHECK(hipMemcpyAsync(dev.dstage, dev.pinned, bytes, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(orbx::k_pnp_gather, dim3((unsigned)keep.size()), dim3(256), 0, st,
                        (const orbx::PnpGatherJob*)dev.dstage);
-    PNP_CHECK(hipGetLastError());
-    PNP_CHECK(hipStreamSynchronize(st));
+    RANSAC_CHECK(hipGetLastError());
+    RANSAC_CHECK(hipStreamSynchronize(st));
   }
   return ORBX_OK;
 }
@@ -1893,6 +1684,41 @@ orbx_status pnp_check_solvers(orbx_pnp* const* solvers, int n, const orbx_pnp_re
 
 extern "C" {
 
+orbx_status orbx_pnp_iterate(orbx_pnp* h, int n_iterations, const int32_t* rand_vals, int n_rand, int* used,
+                             int* no_more, float Tcw[16], uint8_t* inliers, int* n_inliers, int* found) {
+  if (!h || !used || !no_more || !Tcw || !n_inliers || !found || (h->N > 0 && !inliers) || n_rand < 0 ||
+      (n_rand > 0 && !rand_vals))
+    return ORBX_ERR_ARG;
+  *used = 0;
+  *no_more = 0;
+  *n_inliers = 0;
+  *found = 0;
+  if (h->N < h->min_inliers) {
+    *no_more = 1;
+    return ORBX_OK;
+  }
+  if (hipSetDevice(h->device) != hipSuccess) return ORBX_ERR_HIP;
+  // hypotheses this call may run: while (iterations < maxIts || current < nIterations)
+  const int H = std::max(h->max_its - h->iterations, n_iterations);
+  if (H <= 0) return ORBX_OK;
+  if ((long long)H * h->min_set > n_rand) return ORBX_ERR_CAPACITY;
+  std::lock_guard<std::mutex> lock(g_pnp_dev[h->device].mu);
+  orbx_pnp_result res;
+  std::vector<PnpRun> runs(1);
+  runs[0].h = h;
+  runs[0].rv = rand_vals;
+  runs[0].out = &res;
+  runs[0].inliers = inliers;
+  orbx_status s = pnp_begin(runs[0], n_iterations);
+  if (s != ORBX_OK || (s = pnp_run_many(runs, false, nullptr, H)) != ORBX_OK) return s;
+  *used = runs[0].used;
+  *no_more = res.no_more;
+  *n_inliers = res.n_inliers;
+  *found = res.found;
+  if (res.found) std::memcpy(Tcw, res.Tcw, sizeof(float) * 16);
+  return ORBX_OK;
+}
+
 orbx_status orbx_pnp_iterate_candidates(orbx_pnp* const* solvers, int n, int n_iterations, orbx_rand_state* rng,
                                         orbx_pnp_result* results, uint8_t* const* inliers, int* stopped) {
   orbx_status s = pnp_check_solvers(solvers, n, results);
@@ -1911,22 +1737,20 @@ orbx_status orbx_pnp_iterate_candidates(orbx_pnp* const* solvers, int n, int n_i
     total += (size_t)runs[i].H * solvers[i]->min_set;
   }
   // run i draws from where run i-1 would end without a pose (all of its hypotheses)
-  orbx_rand_state peek = *rng;
-  std::vector<int32_t> vals(std::max(total, (size_t)1));
-  for (size_t k = 0; k < total; k++) vals[k] = orbx_rand_next(&peek);
+  const std::vector<int32_t> vals = orbx::rand_peek(rng, total);
   size_t o = 0;
   for (int i = 0; i < n; i++) {
     runs[i].rv = vals.data() + o;
     o += (size_t)runs[i].H * solvers[i]->min_set;
   }
-  if ((s = pnp_run_many(runs, true, stopped)) != ORBX_OK) return s;
+  if ((s = pnp_run_many(runs, true, stopped, kPnpFirstChunk)) != ORBX_OK) return s;
   for (int i = 0; i < n; i++) results[i].used = runs[i].used;
   // the reference never reaches the candidates after the one that returned a pose: their
   // results are all zero (pnp_begin above already set bNoMore for N < minInliers on them)
   for (int i = *stopped + 1; i < n; i++) std::memset(&results[i], 0, sizeof(results[i]));
   size_t used = 0;
   for (int i = 0; i < n && i <= *stopped; i++) used += runs[i].used;
-  for (size_t k = 0; k < used; k++) (void)orbx_rand_next(rng);
+  orbx::rand_advance(rng, used);
   return ORBX_OK;
 }
 
@@ -1950,16 +1774,13 @@ orbx_status orbx_pnp_iterate_many(orbx_pnp* const* solvers, int n, int n_iterati
     runs[i].out = &results[i];
     runs[i].inliers = inliers ? inliers[i] : nullptr;
     if ((s = pnp_begin(runs[i], n_iterations)) != ORBX_OK) return s;
-    const size_t need = (size_t)runs[i].H * solvers[i]->min_set;
-    orbx_rand_state peek = *rngs[i];
-    vals[i].resize(std::max(need, (size_t)1));
-    for (size_t k = 0; k < need; k++) vals[i][k] = orbx_rand_next(&peek);
+    vals[i] = orbx::rand_peek(rngs[i], (size_t)runs[i].H * solvers[i]->min_set);
     runs[i].rv = vals[i].data();
   }
-  if ((s = pnp_run_many(runs, false, nullptr)) != ORBX_OK) return s;
+  if ((s = pnp_run_many(runs, false, nullptr, kPnpFirstChunk)) != ORBX_OK) return s;
   for (int i = 0; i < n; i++) {
     results[i].used = runs[i].used;
-    for (int k = 0; k < runs[i].used; k++) (void)orbx_rand_next(rngs[i]);
+    orbx::rand_advance(rngs[i], runs[i].used);
   }
   return ORBX_OK;
 }
@@ -1994,14 +1815,12 @@ orbx_status orbx_pnp_iterate_stream(orbx_pnp* h, int n_iterations, orbx_rand_sta
                                     uint8_t* inliers, int* n_inliers, int* found) {
   if (!h || !rng) return ORBX_ERR_ARG;
   const int need = h->min_set * std::max(std::max(h->max_its - h->iterations, n_iterations), 0);
-  orbx_rand_state peek = *rng;
-  std::vector<int32_t> vals(need);
-  for (int k = 0; k < need; k++) vals[k] = orbx_rand_next(&peek);
+  const std::vector<int32_t> vals = orbx::rand_peek(rng, need);
   int used = 0;
   const orbx_status st =
       orbx_pnp_iterate(h, n_iterations, vals.data(), need, &used, no_more, Tcw, inliers, n_inliers, found);
   if (st != ORBX_OK) return st;
-  for (int k = 0; k < used; k++) (void)orbx_rand_next(rng);
+  orbx::rand_advance(rng, used);
   return ORBX_OK;
 }
 

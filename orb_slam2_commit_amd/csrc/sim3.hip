@@ -26,7 +26,6 @@
 #include <algorithm>
 #include <climits>
 #include <cmath>
-#include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include <new>
@@ -35,6 +34,7 @@
 #include "../../include/orbx.h"
 #include "../../include/orbx_debug.h"
 #include "orbx_device.h"
+#include "orbx_ransac.h"
 
 namespace orbx {
 
@@ -550,63 +550,10 @@ using orbx::Sim3Job;
 using orbx::Sim3Rec;
 using orbx::Sim3State;
 
-inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// One stream, one pinned block and one device scratch block per device, shared by every solver
-// (LoopClosing creates a Sim3Solver per loop candidate): a solver owns only its correspondences,
-// its best mask and its state; the per-hypothesis arrays of a call live in the scratch block.
-struct Sim3Device {
-  std::once_flag once;
-  hipError_t init_err = hipSuccess;
-  hipStream_t st = nullptr;
-  std::mutex mu;
-  void* pinned = nullptr;
-  size_t pinned_cap = 0;
-  void* scratch = nullptr;
-  size_t scratch_cap = 0;
-  hipError_t scratch_reserve(size_t bytes) {
-    if (bytes <= scratch_cap) return hipSuccess;
-    if (scratch) (void)hipFree(scratch);
-    scratch = nullptr;
-    scratch_cap = 0;
-    hipError_t e = hipMalloc(&scratch, bytes);
-    if (e == hipSuccess) scratch_cap = bytes;
-    return e;
-  }
-  hipError_t pinned_reserve(size_t bytes) {
-    if (bytes <= pinned_cap) return hipSuccess;
-    if (pinned) (void)hipHostFree(pinned);
-    pinned = nullptr;
-    pinned_cap = 0;
-    hipError_t e = hipHostMalloc(&pinned, bytes, hipHostMallocDefault);
-    if (e == hipSuccess) pinned_cap = bytes;
-    return e;
-  }
-};
-Sim3Device g_sim3_dev[64];
-
-hipError_t sim3_device_init(int device) {
-  Sim3Device& d = g_sim3_dev[device];
-  std::call_once(d.once, [&] {
-    d.init_err = hipStreamCreateWithFlags(&d.st, hipStreamNonBlocking);
-    if (d.init_err == hipSuccess) d.init_err = d.pinned_reserve(1 << 16);
-  });
-  return d.init_err;
-}
-
-orbx_status sim3_device_check(int device) {
-  int nd = 0;
-  if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) return ORBX_ERR_NODEV;
-  if (device < 0 || device >= nd || device >= 64) return ORBX_ERR_ARG;
-  if (hipSetDevice(device) != hipSuccess) return ORBX_ERR_HIP;
-  if (sim3_device_init(device) != hipSuccess) return ORBX_ERR_HIP;
-  return ORBX_OK;
-}
-
-#define SIM3_CHECK(x)                            \
-  do {                                           \
-    if ((x) != hipSuccess) return ORBX_ERR_HIP;  \
-  } while (0)
+// One context per device (orbx_ransac.h), shared by every solver (LoopClosing creates a Sim3Solver
+// per loop candidate): a solver owns only its correspondences, its best mask and its state; the
+// per-hypothesis arrays of a call live in the context's device staging block.
+orbx::RansacDevice g_sim3_dev[64];
 
 }  // namespace
 
@@ -629,7 +576,7 @@ struct orbx_sim3 {
     size_t o = 0;
     auto take = [&](size_t bytes) {
       uint8_t* p = base ? base + o : nullptr;
-      o += al256(bytes);
+      o += orbx::align256(bytes);
       return p;
     };
     d_x1 = (float*)take(12 * nn);
@@ -751,56 +698,43 @@ void sim3_begin(Sim3Run& r, int n_iterations) {
 orbx_status sim3_run(std::vector<Sim3Run>& runs, bool shared, uint8_t* const* inliers) {
   const int n = (int)runs.size();
   const int device = runs[0].h->device;
-  Sim3Device& dev = g_sim3_dev[device];
+  orbx::RansacDevice& dev = g_sim3_dev[device];
   hipStream_t st = dev.st;
-  // scratch layout: [jobs | sets] uploaded, [hyps | masks | counts] device only, [recs + masks] read back
-  const size_t off_sets = al256(sizeof(Sim3Job) * (size_t)n);
+  // staging layout: [jobs | sets] uploaded, [hyps | masks | counts] device only, [recs + masks] read back
+  const size_t off_sets = orbx::align256(sizeof(Sim3Job) * (size_t)n);
   size_t o = off_sets;
   std::vector<size_t> o_sets(n), o_hyps(n), o_masks(n), o_counts(n), o_rec(n);
   int Hmax = 0;
   for (int i = 0; i < n; i++) {
     o_sets[i] = o;
-    o += al256(sizeof(int) * 3 * (size_t)runs[i].H);
+    o += orbx::align256(sizeof(int) * 3 * (size_t)runs[i].H);
     Hmax = std::max(Hmax, runs[i].H);
   }
   const size_t up_bytes = o;
   for (int i = 0; i < n; i++) {
     const size_t H = runs[i].H, N = std::max(runs[i].h->N, 1);
     o_hyps[i] = o;
-    o += al256(sizeof(Sim3Hyp) * H);
+    o += orbx::align256(sizeof(Sim3Hyp) * H);
     o_masks[i] = o;
-    o += al256(H * N);
+    o += orbx::align256(H * N);
     o_counts[i] = o;
-    o += al256(sizeof(int) * H);
+    o += orbx::align256(sizeof(int) * H);
   }
   const size_t off_back = o;
   for (int i = 0; i < n; i++) {
     o_rec[i] = o;
-    o += al256(sizeof(Sim3Rec) + (size_t)std::max(runs[i].h->N, 1));
+    o += orbx::align256(sizeof(Sim3Rec) + (size_t)std::max(runs[i].h->N, 1));
   }
   const size_t total = o, back_bytes = total - off_back;
-  SIM3_CHECK(dev.scratch_reserve(total));
-  SIM3_CHECK(dev.pinned_reserve(up_bytes + back_bytes));
+  RANSAC_CHECK(dev.dstage_reserve(total));
+  RANSAC_CHECK(dev.pinned_reserve(up_bytes + back_bytes));
   uint8_t* hp = (uint8_t*)dev.pinned;
-  uint8_t* dp = (uint8_t*)dev.scratch;
+  uint8_t* dp = (uint8_t*)dev.dstage;
   Sim3Job* jobs = (Sim3Job*)hp;
-  std::vector<int> avail;
   for (int i = 0; i < n; i++) {
     orbx_sim3* h = runs[i].h;
     const int N = h->N, H = runs[i].H;
-    // DUtils::Random::RandomInt(0, size-1) on the rand() stream + swap-remove (:180-202)
-    int* sets = (int*)(hp + o_sets[i]);
-    avail.resize(std::max(N, 1));
-    for (int k = 0; k < H; k++) {
-      for (int j = 0; j < N; j++) avail[j] = j;
-      int size = N;
-      for (int j = 0; j < 3; j++) {
-        const int randi = (int)(((double)runs[i].rv[3 * k + j] / ((double)RAND_MAX + 1.0)) * size);
-        sets[3 * k + j] = avail[randi];
-        avail[randi] = avail[size - 1];
-        size--;
-      }
-    }
+    orbx::ransac_sample_sets(runs[i].rv, H, 3, N, (int*)(hp + o_sets[i]));  // :180-202
     Sim3Job& J = jobs[i];
     J.in = h->in();
     J.sets = (const int*)(dp + o_sets[i]);
@@ -816,18 +750,18 @@ orbx_status sim3_run(std::vector<Sim3Run>& runs, bool shared, uint8_t* const* in
     J.min_inliers = h->min_inliers;
     J.too_few = runs[i].too_few;
   }
-  SIM3_CHECK(hipMemcpyAsync(dp, hp, up_bytes, hipMemcpyHostToDevice, st));
-  SIM3_CHECK(hipMemsetAsync(dp + off_back, 0, back_bytes, st));
+  RANSAC_CHECK(hipMemcpyAsync(dp, hp, up_bytes, hipMemcpyHostToDevice, st));
+  RANSAC_CHECK(hipMemsetAsync(dp + off_back, 0, back_bytes, st));
   if (Hmax > 0)
     hipLaunchKernelGGL(orbx::k_sim3_hyp, dim3(Hmax, n), dim3(orbx::kSim3Threads), 0, st, (const Sim3Job*)dp);
   if (shared)
     hipLaunchKernelGGL(orbx::k_sim3_select, dim3(1), dim3(64 * std::min(n, 16)), 0, st, (const Sim3Job*)dp, n, 1);
   else
     hipLaunchKernelGGL(orbx::k_sim3_select, dim3(n), dim3(64), 0, st, (const Sim3Job*)dp, n, 0);
-  SIM3_CHECK(hipGetLastError());
+  RANSAC_CHECK(hipGetLastError());
   uint8_t* back = hp + up_bytes;
-  SIM3_CHECK(hipMemcpyAsync(back, dp + off_back, back_bytes, hipMemcpyDeviceToHost, st));
-  SIM3_CHECK(hipStreamSynchronize(st));
+  RANSAC_CHECK(hipMemcpyAsync(back, dp + off_back, back_bytes, hipMemcpyDeviceToHost, st));
+  RANSAC_CHECK(hipStreamSynchronize(st));
   bool stopped = false;
   for (int i = 0; i < n; i++) {
     Sim3Run& r = runs[i];
@@ -886,9 +820,9 @@ orbx_status orbx_sim3_create_many(const orbx_sim3_solver_problem* problems, int 
   }
   for (int i = 0; i < n; i++) out[i] = nullptr;
   if (n == 0) return ORBX_OK;
-  orbx_status s = sim3_device_check(device);
+  orbx_status s = orbx::ransac_device_check(g_sim3_dev, device, nullptr);
   if (s != ORBX_OK) return s;
-  Sim3Device& dev = g_sim3_dev[device];
+  orbx::RansacDevice& dev = g_sim3_dev[device];
   std::lock_guard<std::mutex> lock(dev.mu);
   std::vector<orbx_sim3*> hs(n, nullptr);
   auto fail = [&](orbx_status code) {
@@ -903,11 +837,11 @@ orbx_status orbx_sim3_create_many(const orbx_sim3_solver_problem* problems, int 
     stage += hs[i]->upload_bytes();
   }
   // every solver's correspondences in one pinned block, one upload, one gather launch
-  const size_t off_data = al256(sizeof(Sim3GatherJob) * (size_t)n);
+  const size_t off_data = orbx::align256(sizeof(Sim3GatherJob) * (size_t)n);
   const size_t bytes = off_data + stage;
-  if (dev.pinned_reserve(bytes) != hipSuccess || dev.scratch_reserve(bytes) != hipSuccess) return fail(ORBX_ERR_HIP);
+  if (dev.pinned_reserve(bytes) != hipSuccess || dev.dstage_reserve(bytes) != hipSuccess) return fail(ORBX_ERR_HIP);
   uint8_t* hp = (uint8_t*)dev.pinned;
-  uint8_t* dp = (uint8_t*)dev.scratch;
+  uint8_t* dp = (uint8_t*)dev.dstage;
   Sim3GatherJob* jobs = (Sim3GatherJob*)hp;
   size_t o = off_data;
   for (int i = 0; i < n; i++) {
@@ -943,7 +877,7 @@ orbx_status orbx_sim3_set_ransac_parameters(orbx_sim3* h, const orbx_sim3_params
   h->max_its = its;
   // :150 mnIterations = 0; the best set, its count and the best Sim3 are kept
   h->iterations = 0;
-  SIM3_CHECK(hipMemsetAsync(&h->d_state->iterations, 0, sizeof(int), h->st));
+  RANSAC_CHECK(hipMemsetAsync(&h->d_state->iterations, 0, sizeof(int), h->st));
   return ORBX_OK;
 }
 
@@ -996,14 +930,12 @@ orbx_status orbx_sim3_iterate_stream(orbx_sim3* h, int n_iterations, orbx_rand_s
   r.h = h;
   sim3_begin(r, n_iterations);
   const int need = 3 * r.H;
-  orbx_rand_state peek = *rng;
-  std::vector<int32_t> vals(std::max(need, 1));
-  for (int k = 0; k < need; k++) vals[k] = orbx_rand_next(&peek);
+  const std::vector<int32_t> vals = orbx::rand_peek(rng, need);
   int used = 0;
   const orbx_status st =
       orbx_sim3_iterate(h, n_iterations, vals.data(), need, &used, no_more, T12, inliers, n_inliers, found);
   if (st != ORBX_OK) return st;
-  for (int k = 0; k < used; k++) (void)orbx_rand_next(rng);
+  orbx::rand_advance(rng, used);
   return ORBX_OK;
 }
 
@@ -1012,8 +944,8 @@ orbx_status orbx_sim3_get_estimate(orbx_sim3* h, float R[9], float t[3], float* 
   if (hipSetDevice(h->device) != hipSuccess) return ORBX_ERR_HIP;
   std::lock_guard<std::mutex> lock(g_sim3_dev[h->device].mu);
   Sim3Hyp best;
-  SIM3_CHECK(hipMemcpyAsync(&best, &h->d_state->best, sizeof(best), hipMemcpyDeviceToHost, h->st));
-  SIM3_CHECK(hipStreamSynchronize(h->st));
+  RANSAC_CHECK(hipMemcpyAsync(&best, &h->d_state->best, sizeof(best), hipMemcpyDeviceToHost, h->st));
+  RANSAC_CHECK(hipStreamSynchronize(h->st));
   std::memcpy(R, best.R, sizeof(best.R));
   std::memcpy(t, best.t, sizeof(best.t));
   *s = best.s;
@@ -1034,9 +966,7 @@ orbx_status orbx_sim3_iterate_candidates(orbx_sim3* const* solvers, int n, int n
     total += 3 * (size_t)runs[i].H;
   }
   // solver i draws from where solver i-1 ends when it returns nothing (all of its iterations)
-  orbx_rand_state peek = *rng;
-  std::vector<int32_t> vals(std::max(total, (size_t)1));
-  for (size_t k = 0; k < total; k++) vals[k] = orbx_rand_next(&peek);
+  const std::vector<int32_t> vals = orbx::rand_peek(rng, total);
   size_t o = 0;
   for (int i = 0; i < n; i++) {
     runs[i].rv = vals.data() + o;
@@ -1051,7 +981,7 @@ orbx_status orbx_sim3_iterate_candidates(orbx_sim3* const* solvers, int n, int n
     if (i <= *stopped) used += (size_t)results[i].used;
     if (results[i].found && *stopped == n) *stopped = i;
   }
-  for (size_t k = 0; k < used; k++) (void)orbx_rand_next(rng);
+  orbx::rand_advance(rng, used);
   return ORBX_OK;
 }
 
@@ -1071,10 +1001,7 @@ orbx_status orbx_sim3_iterate_many(orbx_sim3* const* solvers, int n, int n_itera
   for (int i = 0; i < n; i++) {
     runs[i].h = solvers[i];
     sim3_begin(runs[i], n_iterations);
-    const size_t need = 3 * (size_t)runs[i].H;
-    orbx_rand_state peek = *rngs[i];
-    vals[i].resize(std::max(need, (size_t)1));
-    for (size_t k = 0; k < need; k++) vals[i][k] = orbx_rand_next(&peek);
+    vals[i] = orbx::rand_peek(rngs[i], 3 * (size_t)runs[i].H);
     runs[i].rv = vals[i].data();
   }
   if (hipSetDevice(solvers[0]->device) != hipSuccess) return ORBX_ERR_HIP;
@@ -1082,7 +1009,7 @@ orbx_status orbx_sim3_iterate_many(orbx_sim3* const* solvers, int n, int n_itera
   if ((s = sim3_run(runs, false, inliers)) != ORBX_OK) return s;
   for (int i = 0; i < n; i++) {
     sim3_result(runs[i], &results[i]);
-    for (int k = 0; k < results[i].used; k++) (void)orbx_rand_next(rngs[i]);
+    orbx::rand_advance(rngs[i], results[i].used);
   }
   return ORBX_OK;
 }

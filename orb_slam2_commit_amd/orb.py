@@ -736,22 +736,23 @@ class PnPsolver:
         if self._h:
             check(_lib.lib().orbx_pnp_set_ransac_parameters(self._h, ptr(self.sigma2), C.byref(prm)),
                   "orbx_pnp_set_ransac_parameters")
-            self.min_set = int(minSet)
-            a, b, c = C.c_int(), C.c_int(), C.c_float()
-            check(_lib.lib().orbx_pnp_get_params(self._h, C.byref(a), C.byref(b), C.byref(c)), "orbx_pnp_get_params")
-            self.min_inliers, self.max_its, self.epsilon = a.value, b.value, c.value
+            self._read_params(minSet)
             return
-        self.close()
         prob = _lib.PnpProblem(self.n, ptr(self.p3d), ptr(self.p2d), ptr(self.sigma2), *self.intr)
-        prm = _lib.PnpParams(float(probability), int(minInliers), int(maxIterations), int(minSet), float(epsilon),
-                             float(th2))
         h = C.c_void_p()
         check(_lib.lib().orbx_pnp_create(C.byref(prob), C.byref(prm), self.device, C.byref(h)), "orbx_pnp_create")
-        self._h = h
+        self._adopt(h, minSet)
+
+    def _read_params(self, minSet):
         self.min_set = int(minSet)
         a, b, c = C.c_int(), C.c_int(), C.c_float()
-        check(_lib.lib().orbx_pnp_get_params(h, C.byref(a), C.byref(b), C.byref(c)), "orbx_pnp_get_params")
+        check(_lib.lib().orbx_pnp_get_params(self._h, C.byref(a), C.byref(b), C.byref(c)), "orbx_pnp_get_params")
         self.min_inliers, self.max_its, self.epsilon = a.value, b.value, c.value
+
+    def _adopt(self, h, minSet):
+        """Takes a fresh orbx_pnp handle: the derived parameters, no hypothesis run yet."""
+        self._h = h
+        self._read_params(minSet)
         self._done = 0
 
     @classmethod
@@ -777,12 +778,7 @@ class PnPsolver:
         hs = (C.c_void_p * max(n, 1))()
         check(_lib.lib().orbx_pnp_create_many(structs, n, C.byref(prm), int(device), hs), "orbx_pnp_create_many")
         for o, h in zip(objs, hs):
-            o._h = C.c_void_p(h)
-            o.min_set = int(minSet)
-            a, b, c = C.c_int(), C.c_int(), C.c_float()
-            check(_lib.lib().orbx_pnp_get_params(o._h, C.byref(a), C.byref(b), C.byref(c)), "orbx_pnp_get_params")
-            o.min_inliers, o.max_its, o.epsilon = a.value, b.value, c.value
-            o._done = 0
+            o._adopt(C.c_void_p(h), minSet)
         return objs
 
     @classmethod
@@ -805,12 +801,7 @@ class PnPsolver:
             o = cls.__new__(cls)
             o.n = int(offs[i + 1] - offs[i])
             o.device = int(device)
-            o._h = C.c_void_p(hs[i])
-            o.min_set = int(minSet)
-            a, b, c = C.c_int(), C.c_int(), C.c_float()
-            check(_lib.lib().orbx_pnp_get_params(o._h, C.byref(a), C.byref(b), C.byref(c)), "orbx_pnp_get_params")
-            o.min_inliers, o.max_its, o.epsilon = a.value, b.value, c.value
-            o._done = 0
+            o._adopt(C.c_void_p(hs[i]), minSet)
             objs.append(o)
         return objs
 

@@ -343,6 +343,44 @@ def test_gpu_pnp_iterate_many_independent_streams(gpu):
         s.close()
 
 
+MIXED_ORACLE = {  # seed: (bNoMore, nInliers, rand() values used) of four iterate(5) calls, all found
+    116: [(False, 39, 96), (True, 37, 44), (True, 37, 20), (True, 37, 20)],
+    133: [(False, 40, 12), (True, 34, 128), (True, 34, 20), (True, 34, 20)],
+}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("first", ["lone", "many"])
+@pytest.mark.parametrize("seed", sorted(MIXED_ORACLE))
+def test_gpu_pnp_mixed_entry_points(gpu, seed, first):
+    """One solver driven alternately through the lone entry (iterate) and the batched entries
+    (pnp_iterate_many, pnp_iterate_candidates): the best set and pose one entry leaves on the solver
+    are what the other returns later (calls 3 and 4 return a best set of an earlier call).  Seed 116's
+    first call walks 24 hypotheses (past the first chunk of 16); seed 133's first call stops inside
+    the first chunk and its second crosses it."""
+    from orb_slam2_commit_amd.orb import pnp_iterate_candidates, pnp_iterate_many
+    P = synth.pnp_problem(seed=seed, n=64, outlier_frac=0.4, noise_px=0.5)
+    ora = _oracle_run(P, 4)
+    o = _oracle_solver(P)
+    assert (o.min_inliers, o.max_its) == (32, 35)
+    assert [(T is not None, nm, ni, used) for T, nm, inl, ni, used in ora] == \
+        [(True,) + c for c in MIXED_ORACLE[seed]]
+    s = _gpu_solver(P)
+    g_gpu, g_ora = GlibcRand(1), GlibcRand(1)
+    lone = lambda: s.iterate(5, g_gpu)  # noqa: E731
+    many = lambda: pnp_iterate_many([s], 5, [g_gpu])[0]  # noqa: E731
+    cand = lambda: pnp_iterate_candidates([s], 5, g_gpu)[1][0]  # noqa: E731
+    order = [lone, many, lone, cand] if first == "lone" else [many, lone, cand, lone]
+    for call, (To, nmo, inlo, nio, usedo) in zip(order, ora):
+        Tg, nmg, inlg, nig = call()
+        g_ora.advance(usedo)
+        assert Tg is not None and nmo == nmg and nio == nig
+        np.testing.assert_array_equal(Tg, To)
+        np.testing.assert_array_equal(inlg, inlo)
+        assert g_gpu.peek(4) == g_ora.peek(4)  # identical rand() consumption
+    s.close()
+
+
 def test_rand_state_bridge_round_trip():
     """GlibcRand <-> orbx_rand_state (host code of liborbx.so, no GPU)."""
     import ctypes as C

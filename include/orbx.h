@@ -52,6 +52,9 @@
  *   orbx_search_for_initialization ORBmatcher::SearchForInitialization src/ORBmatcher.cc:442-587, include/ORBmatcher.h:130
  *   orbx_pose_optimization     Optimizer::PoseOptimization     src/Optimizer.cc:287-528, include/Optimizer.h:71
  *   orbx_pose_optimization_device      batch of the above (one block per frame)
+ *   orbx_optimize_sim3         Optimizer::OptimizeSim3         src/Optimizer.cc:1220-1456, include/Optimizer.h
+ *                              (the refinement stage of LoopClosing::ComputeSim3, src/LoopClosing.cc:425-444)
+ *   orbx_optimize_sim3_device          batch of the above (one block per problem)
  *   orbx_distinctive_descriptors[_device]  MapPoint::ComputeDistinctiveDescriptors src/MapPoint.cc:249-320
  *   orbx_undistort_keypoints[_device]      Frame::UndistortKeyPoints src/Frame.cc:471-506 (cv::undistortPoints)
  *   orbx_local_ba / orbx_ba_*   Optimizer::LocalBundleAdjustment src/Optimizer.cc:530-885, include/Optimizer.h:61
@@ -827,6 +830,44 @@ orbx_status orbx_pose_optimization(const orbx_pose_problem* p, int device);
 /* Batched, device-resident: problems[] is a HOST array whose pointers are device
  * pointers; one block per problem runs all four rounds on the GPU (no host round trips). */
 orbx_status orbx_pose_optimization_device(const orbx_pose_problem* problems, int n, void* stream);
+
+/* Optimizer::OptimizeSim3(KeyFrame*, KeyFrame*, vector<MapPoint*>&, g2o::Sim3&, float, bool) --
+ * src/Optimizer.cc:1220-1456, include/Optimizer.h (called at src/LoopClosing.cc:425-444): one
+ * VertexSim3Expmap, per correspondence an EdgeSim3ProjectXYZ and an EdgeInverseSim3ProjectXYZ with
+ * Huber kernels (delta = sqrt(th2) in float) and g2o's NUMERIC Jacobians (neither edge has
+ * linearizeOplus), optimize(5), the pair-wise outlier pass on the stored errors, the early return
+ * below 10 survivors, optimize(nBad > 0 ? 10 : 5), the final inlier count.  The caller gathers one
+ * row per correspondence the intake loop (:1287-1384) keeps, in its order, and afterwards nulls
+ * vpMatches1[vnIndexEdge[k]] where inlier[k] == 0 and writes g2oS12 = S12_out (which equals S12 when
+ * the reference returns before writing it back). */
+typedef struct {
+  int n;                       /* nCorrespondences */
+  const float* x3dc1;          /* n x 3: R1w*P3D1w + t1w (CV_32F) */
+  const float* x3dc2;          /* n x 3: R2w*P3D2w + t2w */
+  const float* obs1;           /* n x 2: pKF1->mvKeysUn[i].pt */
+  const float* obs2;           /* n x 2: pKF2->mvKeysUn[i2].pt */
+  const float* inv_sigma2_1;   /* n: pKF1->mvInvLevelSigma2[kpUn1.octave] */
+  const float* inv_sigma2_2;   /* n: pKF2->mvInvLevelSigma2[kpUn2.octave] */
+  float K1[4], K2[4];          /* fx, fy, cx, cy of pKF1->mK, pKF2->mK */
+  double S12[8];               /* g2oS12 on entry: quaternion x, y, z, w, translation, scale */
+  float th2;
+  int fix_scale;               /* bFixScale */
+  double* S12_out;             /* 8: g2oS12 on return */
+  uint8_t* inlier;             /* n: 0 where the reference nulls vpMatches1 */
+  int32_t* n_in;               /* the return value */
+  int32_t* n_bad;              /* optional: pairs removed after optimize(5) */
+  int32_t* iterations;         /* optional [2]: LM iterations of the two optimize() calls */
+  int32_t* trials;             /* optional: LM trials (linear solves) of both */
+  /* Device batches only (NULL otherwise): n as an earlier kernel of the stream left it -- n is then
+   * the capacity and n = min(*n_dev, n) */
+  const int32_t* n_dev;
+} orbx_optimize_sim3_problem;
+
+/* One problem, HOST pointers.  Optimizer::OptimizeSim3 -- src/Optimizer.cc:1220-1456, include/Optimizer.h. */
+orbx_status orbx_optimize_sim3(const orbx_optimize_sim3_problem* p, int device);
+/* Batched, device-resident: problems[] is a HOST array whose pointers are device pointers; one block
+ * per problem runs the whole schedule on the GPU. */
+orbx_status orbx_optimize_sim3_device(const orbx_optimize_sim3_problem* problems, int n, void* stream);
 
 /* Tracking::TrackReferenceKeyFrame's gather (src/Tracking.cc:910-969) between SearchByBoW(KF, F)
  * and PoseOptimization(&F), on a device batch: PoseOptimization's edge per current-frame feature

@@ -50,6 +50,12 @@ long long orbx_debug_launch_plan(const orbx_extractor_params* params, int width,
  * on the host: the same operation sequence as the kernels run (no device is needed or touched). */
 double orbx_debug_atan2_det(double y, double x);
 
+/* The library's deterministic double exp (g2o::Sim3's std::exp(sigma)) of n values, on the device. */
+int orbx_debug_exp(const double* x, int n, double* y, int device);
+/* VertexSim3Expmap::oplusImpl on the device, in a one-thread kernel: out = Sim3(update) * S with
+ * update[6] zeroed first when fix_scale; S and out are eight doubles as orbx_optimize_sim3_problem.S12. */
+int orbx_debug_sim3_exp(const double update[7], const double S[8], int fix_scale, double out[8], int device);
+
 /* Solve S x = b (N x N, N a multiple of 6) with the LocalBA reduced-system
  * LDLT kernel; *ms = mean kernel time over reps launches.  ORBX_ERR_STATE on
  * a zero pivot. */

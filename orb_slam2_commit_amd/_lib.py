@@ -115,6 +115,14 @@ class PoseProblem(C.Structure):
                 ("iterations", C.c_void_p), ("n_dev", C.c_void_p), ("Tcw_dev", C.c_void_p)]
 
 
+class OptSim3Problem(C.Structure):  # orbx_optimize_sim3_problem (Optimizer::OptimizeSim3)
+    _fields_ = [("n", C.c_int)] + \
+               [(k, C.c_void_p) for k in ("x3dc1", "x3dc2", "obs1", "obs2", "inv_sigma2_1", "inv_sigma2_2")] + \
+               [("K1", C.c_float * 4), ("K2", C.c_float * 4), ("S12", C.c_double * 8), ("th2", C.c_float),
+                ("fix_scale", C.c_int)] + \
+               [(k, C.c_void_p) for k in ("S12_out", "inlier", "n_in", "n_bad", "iterations", "trials", "n_dev")]
+
+
 class TriKF(C.Structure):
     _fields_ = [("n", C.c_int), ("keys_un", C.c_void_p), ("desc", C.c_void_p), ("u_right", C.c_void_p),
                 ("has_mp", C.c_void_p), ("n_nodes", C.c_int), ("node_id", C.c_void_p), ("node_off", C.c_void_p),
@@ -252,6 +260,8 @@ SIGNATURES = {
     "orbx_search_by_projection_device": ([C.POINTER(ProjProblem), C.c_int, P], C.c_int),
     "orbx_pose_optimization": ([C.POINTER(PoseProblem), C.c_int], C.c_int),
     "orbx_pose_optimization_device": ([C.POINTER(PoseProblem), C.c_int, P], C.c_int),
+    "orbx_optimize_sim3": ([C.POINTER(OptSim3Problem), C.c_int], C.c_int),
+    "orbx_optimize_sim3_device": ([C.POINTER(OptSim3Problem), C.c_int, P], C.c_int),
     "orbx_search_for_triangulation": ([C.POINTER(TriProblem), C.c_int], C.c_int),
     "orbx_search_for_triangulation_device": ([C.POINTER(TriProblem), C.c_int, P], C.c_int),
     "orbx_distinctive_descriptors": ([P, P, C.c_int, P, P, C.c_int], C.c_int),
@@ -300,6 +310,8 @@ SIGNATURES = {
     "orbx_debug_launch_plan": ([C.POINTER(ExtractorParams), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P,
                                 C.c_size_t], C.c_longlong),
     "orbx_debug_atan2_det": ([C.c_double, C.c_double], C.c_double),
+    "orbx_debug_exp": ([P, C.c_int, P, C.c_int], C.c_int),
+    "orbx_debug_sim3_exp": ([P, P, C.c_int, P, C.c_int], C.c_int),
     "orbx_debug_ldlt": ([P, P, C.c_int, P, C.c_int, C.POINTER(C.c_float)], C.c_int),
     "orbx_debug_ldlt_ex": ([P, P, C.c_int, P, C.c_int, C.POINTER(C.c_float), C.c_int, P], C.c_int),
     "orbx_debug_ba_options": ([P, C.POINTER(BaDebugOptions)], C.c_int),

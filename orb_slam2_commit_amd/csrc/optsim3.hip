@@ -1,0 +1,650 @@
+// optsim3.hip -- Optimizer::OptimizeSim3 (src/Optimizer.cc:1220-1456), one block per problem, the
+// whole schedule on the device: optimize(5), the pair-wise outlier pass on the stored errors, the
+// early return, optimize(nMore), the final inlier count.
+//
+// The problem is one 7-DoF VertexSim3Expmap with two Huber edges per correspondence
+// (EdgeSim3ProjectXYZ, EdgeInverseSim3ProjectXYZ).  Neither edge has an analytic Jacobian, so g2o
+// differentiates numerically: per edge and linearisation, 14 error evaluations at the estimates
+// Sim3(+-1e-9 e_d) * S.  Those 14 estimates (and the inverses the e21 edges map through) are the same
+// for every edge, so 15 lanes compute them once into LDS by exactly the per-edge expression and each
+// edge's thread then evaluates its 15 errors from there: the reference's push/oplus/pop arithmetic at
+// 1/(2n) of its transcendental work.  The sums g2o forms in edge insertion order (activeRobustChi2,
+// the 28 upper H entries, the 7 b entries) are taken in that order, one FP64 chain per entry on its
+// own lane over LDS-staged per-edge terms, chunk by chunk (the result does not depend on the chunk
+// size: a chain carries across chunks).  With exp_det / sincos_d for g2o::Sim3's exp and the shared
+// Eigen-LDLT restatement at N = 7 (orbx_lm.h) the kernel reproduces tests/optsim3_literal.py bit for bit.
+//
+// Bound: latency (dependent FP64 chains of length 2n per LM iteration and trial; the serial 7x7
+// solve and Sim3 exp on one lane); throughput comes from problems in flight.  Algorithmic bytes per
+// linearisation: 36 B of input per edge, 16 B of stored error, 288 B of staged terms in LDS.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <vector>
+
+#include "orbx_device.h"
+#include "orbx_scratch.h"
+#include "orbx_internal.h"
+#include "orbx_lm.h"
+#include "../../include/orbx_debug.h"
+
+namespace orbx {
+namespace osim3 {
+
+using namespace lm;
+
+constexpr int BS = 256;
+constexpr int kCh = BS;              // edges staged per chunk (128 pairs), one thread each
+constexpr int kTerm = 36, kTs = 37;  // 28 H (upper) | 7 b | chi term, at an odd row stride
+constexpr int kChiCh = kCh * kTs;    // chi terms per trial pass (one double each)
+
+struct Sim3 {
+  Quat q;
+  double t[3];
+  double s;
+};
+struct Pair {  // an estimate and its inverse (what the e12 resp. e21 edges map through)
+  Sim3 S, Si;
+};
+
+// Sim3(const Vector7d&), types/sim3.h:70-142
+__device__ __forceinline__ Sim3 sim3_exp(const double (&u)[7]) {
+  const double w[3] = {u[0], u[1], u[2]}, up[3] = {u[3], u[4], u[5]};
+  const double sigma = u[6];
+  const double theta = __builtin_sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+  const double O[9] = {0, -w[2], w[1], w[2], 0, -w[0], -w[1], w[0], 0};
+  Sim3 T;
+  T.s = exp_det(sigma);
+  double O2[9];
+#pragma unroll
+  for (int r = 0; r < 3; r++)
+#pragma unroll
+    for (int c = 0; c < 3; c++) O2[3 * r + c] = O[3 * r] * O[c] + O[3 * r + 1] * O[3 + c] + O[3 * r + 2] * O[6 + c];
+  const double eps = 0.00001;
+  const bool small_theta = theta < eps;
+  double sn = 0, cs = 0, ra = 1.0, rb = 1.0;  // R = I + ra*Omega + rb*Omega2 (both 1: the products are skipped)
+  if (!small_theta) {
+    sincos_d(theta, &sn, &cs);
+    ra = sn / theta;
+    rb = (1 - cs) / (theta * theta);
+  }
+  double A, B, C;
+  if (__builtin_fabs(sigma) < eps) {
+    C = 1;
+    if (small_theta) {
+      A = 1. / 2.;
+      B = 1. / 6.;
+    } else {
+      const double theta2 = theta * theta;
+      A = (1 - cs) / (theta2);
+      B = (theta - sn) / (theta2 * theta);
+    }
+  } else {
+    C = (T.s - 1) / sigma;
+    if (small_theta) {
+      const double sigma2 = sigma * sigma;
+      A = ((sigma - 1) * T.s + 1) / sigma2;
+      B = ((0.5 * sigma2 - sigma + 1) * T.s) / (sigma2 * sigma);
+    } else {
+      const double a = T.s * sn;
+      const double b = T.s * cs;
+      const double theta2 = theta * theta;
+      const double sigma2 = sigma * sigma;
+      const double c = theta2 + sigma2;
+      A = (a * sigma + (1 - b) * theta) / (theta * c);
+      B = (C - ((b - 1) * sigma + a * theta) / (c)) * 1. / (theta2);
+    }
+  }
+  double R[9], W[9];
+#pragma unroll
+  for (int i = 0; i < 9; i++) {
+    const double I = (i % 4) == 0 ? 1.0 : 0.0;
+    R[i] = small_theta ? I + O[i] + O2[i] : I + ra * O[i] + rb * O2[i];
+    W[i] = A * O[i] + B * O2[i] + C * I;
+  }
+  T.q = mat2q(R);  // Quaterniond(R): Sim3 never normalises
+#pragma unroll
+  for (int r = 0; r < 3; r++) T.t[r] = W[3 * r] * up[0] + W[3 * r + 1] * up[1] + W[3 * r + 2] * up[2];
+  return T;
+}
+// operator*, sim3.h:266-272
+__device__ __forceinline__ Sim3 sim3_mul(const Sim3& a, const Sim3& b) {
+  Sim3 r;
+  double rt[3];
+  qrot(a.q, b.t, rt);
+  r.q = qmul(a.q, b.q);
+#pragma unroll
+  for (int i = 0; i < 3; i++) r.t[i] = a.s * rt[i] + a.t[i];
+  r.s = a.s * b.s;
+  return r;
+}
+// inverse(), sim3.h:233-236
+__device__ __forceinline__ Sim3 sim3_inverse(const Sim3& S) {
+  Sim3 r;
+  r.q.x = -S.q.x; r.q.y = -S.q.y; r.q.z = -S.q.z; r.q.w = S.q.w;
+  const double c = -1. / S.s;
+  const double v[3] = {c * S.t[0], c * S.t[1], c * S.t[2]};
+  qrot(r.q, v, r.t);
+  r.s = 1. / S.s;
+  return r;
+}
+// VertexSim3Expmap::oplusImpl with the update e_d * step (d in 0..6; d < 0: the zero update)
+__device__ __forceinline__ Sim3 oplus_unit(const Sim3& S, int d, double step, bool fix_scale) {
+  double u[7];
+#pragma unroll
+  for (int k = 0; k < 7; k++) u[k] = k == d ? step : 0.0;
+  if (fix_scale) u[6] = 0;
+  return sim3_mul(sim3_exp(u), S);
+}
+
+struct Dev {
+  orbx_optimize_sim3_problem p;
+  double* err;  // n x 4: the stored _error of e12 (x, y) and e21 (x, y) of each pair
+  int* act;     // n: active pair ids in insertion order
+};
+
+struct Edge {
+  double X[3], obs[2], info, fx, fy, cx, cy;
+};
+
+// edge k of the active list: pair act[k >> 1]; even = e12 (X2 through S into camera 1), odd = e21
+__device__ __forceinline__ Edge load_edge(const orbx_optimize_sim3_problem& P, int i, int type) {
+  Edge e;
+  const float* X = type ? P.x3dc1 : P.x3dc2;
+  const float* o = type ? P.obs2 : P.obs1;
+  const float* K = type ? P.K2 : P.K1;
+#pragma unroll
+  for (int k = 0; k < 3; k++) e.X[k] = X[3 * i + k];
+  e.obs[0] = o[2 * i];
+  e.obs[1] = o[2 * i + 1];
+  e.info = type ? P.inv_sigma2_2[i] : P.inv_sigma2_1[i];
+  e.fx = K[0]; e.fy = K[1]; e.cx = K[2]; e.cy = K[3];
+  return e;
+}
+// computeError of either edge through T (the estimate for e12, its inverse for e21):
+// obs - cam_map(project(T.map(X)))
+__device__ __forceinline__ void edge_error(const Sim3& T, const Edge& e, double& e0, double& e1) {
+  double r[3];
+  qrot(T.q, e.X, r);
+  const double p0 = T.s * r[0] + T.t[0], p1 = T.s * r[1] + T.t[1], p2 = T.s * r[2] + T.t[2];
+  e0 = e.obs[0] - (p0 / p2 * e.fx + e.cx);
+  e1 = e.obs[1] - (p1 / p2 * e.fy + e.cy);
+}
+__device__ __forceinline__ double chi2_of(double info, double e0, double e1) {
+  double s = e0 * (info * e0);
+  s += e1 * (info * e1);
+  return s;
+}
+// RobustKernelHuber::robustify (dsqr is a float member)
+__device__ __forceinline__ void huber(double delta, float dsqr, double chi, double& rho0, double& rho1) {
+  if (chi <= dsqr) {
+    rho0 = chi;
+    rho1 = 1.;
+  } else {
+    const double sq = __builtin_sqrt(chi);
+    rho0 = 2 * sq * delta - dsqr;
+    rho1 = delta / sq;
+  }
+}
+
+struct Shared {
+  Sim3 S, bak;
+  Pair pert[15];  // [0] the estimate; [1 + 2d], [2 + 2d]: oplus(+delta e_d), oplus(-delta e_d)
+  Pair trial;
+  double H[49], b[7], x[7];
+  double lambda, ni, currentChi, iniChi, rho;
+  int qmax, ok2, nbad_lm, go, term, trials;
+  int scan[BS / 64];
+};
+
+__device__ __forceinline__ const Sim3& side(const Pair& p, int type) { return type ? p.Si : p.S; }
+
+__global__ __launch_bounds__(BS) void k_optimize_sim3(const Dev* __restrict__ probs) {
+  __shared__ Shared S;
+  __shared__ double sterm[kCh * kTs];
+  const Dev& D = probs[blockIdx.x];
+  const orbx_optimize_sim3_problem& P = D.p;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int n = P.n_dev ? min(max(*P.n_dev, 0), P.n) : P.n;  // device-sized: P.n is the capacity
+  double* err = D.err;
+  int* act = D.act;
+  const bool fix_scale = P.fix_scale != 0;
+  const double delta = (double)__builtin_sqrtf(P.th2);  // const float deltaHuber = sqrt(th2)
+  const float dsqr = (float)(delta * delta);
+  const double th2 = (double)P.th2;
+
+  for (int i = tid; i < n; i += BS) {
+    P.inlier[i] = 1;
+    act[i] = i;
+  }
+  if (tid < 8) P.S12_out[tid] = P.S12[tid];
+  if (tid == 0) {
+    S.S.q.x = P.S12[0]; S.S.q.y = P.S12[1]; S.S.q.z = P.S12[2]; S.S.q.w = P.S12[3];
+    S.S.t[0] = P.S12[4]; S.S.t[1] = P.S12[5]; S.S.t[2] = P.S12[6];
+    S.S.s = P.S12[7];
+    S.trials = 0;
+  }
+  __threadfence_block();
+  __syncthreads();
+  int nact = n, nBad = 0, nIn = 0, its0 = 0, its1 = 0;
+  bool early = false;
+  for (int phase = 0; phase < 2; phase++) {
+    const int max_its = phase == 0 ? 5 : (nBad > 0 ? 10 : 5);
+    const int nedge = 2 * nact;
+    int its = 0;
+    if (nact > 0) {
+      for (int iter = 0; iter < max_its; iter++) {
+        its++;
+        // the estimate and its 14 perturbations, each with its inverse: one lane each
+        if (tid < 15) {
+          const int d = tid == 0 ? -1 : (tid - 1) >> 1;
+          const double step = (tid & 1) ? 1e-9 : -1e-9;
+          Pair pr;
+          pr.S = tid == 0 ? S.S : oplus_unit(S.S, d, step, fix_scale);
+          pr.Si = sim3_inverse(pr.S);
+          S.pert[tid] = pr;
+        }
+        __syncthreads();
+        // computeActiveErrors + activeRobustChi2 (currentChi) and buildSystem's terms (numeric
+        // linearizeOplus + constructQuadraticForm), a chunk of kCh active edges at a time into LDS,
+        // each entry summed in insertion order by its own lane
+        double acc = 0.0;  // wave 0, lanes 0..35: H upper (0..27), b (28..34), chi (35)
+        for (int c0 = 0; c0 < nedge; c0 += kCh) {
+          const int k = c0 + tid;
+          if (k < nedge) {
+            const int i = act[k >> 1], type = k & 1;
+            const Edge e = load_edge(P, i, type);
+            double e0, e1;
+            edge_error(side(S.pert[0], type), e, e0, e1);
+            err[4 * i + 2 * type] = e0;
+            err[4 * i + 2 * type + 1] = e1;
+            double* tr = sterm + tid * kTs;
+            const double chi = chi2_of(e.info, e0, e1);
+            double rho0, rho1;
+            huber(delta, dsqr, chi, rho0, rho1);
+            tr[35] = rho0;
+            const double scalar = 1.0 / (2 * 1e-9);
+            double J0[7], J1[7];
+#pragma unroll
+            for (int d = 0; d < 7; d++) {
+              double p0, p1, m0, m1;
+              edge_error(side(S.pert[1 + 2 * d], type), e, p0, p1);
+              edge_error(side(S.pert[2 + 2 * d], type), e, m0, m1);
+              J0[d] = scalar * (p0 - m0);
+              J1[d] = scalar * (p1 - m1);
+            }
+            const double w = rho1 * e.info;  // robustInformation
+            const double om0 = (-(e.info * e0)) * rho1, om1 = (-(e.info * e1)) * rho1;
+            int q = 0;
+#pragma unroll
+            for (int r = 0; r < 7; r++)
+#pragma unroll
+              for (int cc = r; cc < 7; cc++) tr[q++] = (J0[r] * w) * J0[cc] + (J1[r] * w) * J1[cc];
+#pragma unroll
+            for (int r = 0; r < 7; r++) tr[28 + r] = J0[r] * om0 + J1[r] * om1;
+          }
+          __syncthreads();
+          if (wid == 0 && lane < kTerm) acc = lds_chain(sterm + lane, min(kCh, nedge - c0), kTs, acc, false);
+          __syncthreads();
+        }
+        if (wid == 0 && lane < kTerm) {
+          if (lane < 28) {
+            int r = 0, c = lane;
+            while (c >= 7 - r) {
+              c -= 7 - r;
+              r++;
+            }
+            c += r;
+            S.H[7 * r + c] = acc;
+            S.H[7 * c + r] = acc;
+          } else if (lane < 35) {
+            S.b[lane - 28] = acc;
+          } else {
+            S.currentChi = acc;
+            S.iniChi = acc;
+          }
+        }
+        __syncthreads();
+        if (tid == 0) {
+          if (iter == 0) {
+            double m = 0;
+            for (int j = 0; j < 7; j++) {
+              const double a = __builtin_fabs(S.H[8 * j]);
+              m = (a < m) ? m : a;  // std::max(|H_jj|, m)
+            }
+            S.lambda = 1e-5 * m;
+            S.ni = 2;
+            S.nbad_lm = 0;
+          }
+          S.qmax = 0;
+        }
+        __syncthreads();
+        // ---- trials ----
+        for (;;) {
+          if (tid == 0) {
+            S.bak = S.S;
+            double Hd[49];  // registers: every index static
+#pragma unroll
+            for (int j = 0; j < 49; j++) Hd[j] = S.H[j];
+#pragma unroll
+            for (int j = 0; j < 7; j++) Hd[8 * j] += S.lambda;
+            double x[7];
+            const bool ok2 = ldlt<7>(Hd, S.b, x);
+            S.ok2 = ok2;
+            S.trials++;
+            if (ok2) {
+              if (fix_scale) x[6] = 0;  // oplusImpl zeroes the solver's x in place
+              S.S = sim3_mul(sim3_exp(x), S.S);
+            }
+#pragma unroll
+            for (int j = 0; j < 7; j++) S.x[j] = ok2 ? x[j] : 0.0;
+            S.trial.S = S.S;
+            S.trial.Si = sim3_inverse(S.S);
+          }
+          __syncthreads();
+          double tempChi = 0.0;  // thread 0: activeRobustChi2 at the trial estimate, insertion order
+          for (int c0 = 0; c0 < nedge; c0 += kChiCh) {
+            for (int k = c0 + tid; k < min(nedge, c0 + kChiCh); k += BS) {
+              const int i = act[k >> 1], type = k & 1;
+              const Edge e = load_edge(P, i, type);
+              double e0, e1;
+              edge_error(side(S.trial, type), e, e0, e1);
+              err[4 * i + 2 * type] = e0;
+              err[4 * i + 2 * type + 1] = e1;
+              double rho0, rho1;
+              huber(delta, dsqr, chi2_of(e.info, e0, e1), rho0, rho1);
+              sterm[k - c0] = rho0;
+            }
+            __syncthreads();
+            if (tid == 0) tempChi = lds_chain(sterm, min(kChiCh, nedge - c0), 1, tempChi, false);
+            __syncthreads();
+          }
+          if (tid == 0) {
+            const bool ok2 = S.ok2;
+            if (!ok2) tempChi = 1.7976931348623157e308;
+            double rho = S.currentChi - tempChi;
+            double scale = 0.0;
+            if (ok2)
+              for (int j = 0; j < 7; j++) scale += S.x[j] * (S.lambda * S.x[j] + S.b[j]);
+            scale += 1e-3;
+            rho /= scale;
+            if (rho > 0 && __builtin_isfinite(tempChi)) {
+              const double t3 = 2 * rho - 1;
+              double alpha = 1. - t3 * t3 * t3;
+              alpha = (2. / 3. < alpha) ? 2. / 3. : alpha;     // std::min(alpha, 2/3)
+              S.lambda *= (1. / 3. < alpha) ? alpha : 1. / 3.;  // std::max(1/3, alpha)
+              S.ni = 2;
+              S.currentChi = tempChi;
+            } else {
+              S.lambda *= S.ni;
+              S.ni *= 2;
+              S.S = S.bak;  // pop; the rejected trial's errors stay in the edges
+            }
+            S.qmax++;
+            S.rho = rho;
+            S.go = (rho < 0 && S.qmax < 10);
+          }
+          __syncthreads();
+          if (!S.go) break;
+        }
+        if (tid == 0) {
+          int term = 0;
+          if (S.qmax == 10 || S.rho == 0) term = 1;
+          else {
+            if ((S.iniChi - S.currentChi) * 1e3 < S.iniChi) S.nbad_lm++;
+            else S.nbad_lm = 0;
+            if (S.nbad_lm >= 3) term = 1;
+          }
+          S.term = term;
+        }
+        __syncthreads();
+        if (S.term) break;
+      }
+    }
+    if (phase == 0) its0 = its; else its1 = its;
+    // ---- the pair test on the STORED errors (:1393-1412, :1433-1448); after optimize(5) an ordered
+    // block scan compacts the survivors in place (a write lands at or below the slot it was read from)
+    __threadfence_block();
+    __syncthreads();
+    int base = 0;
+    for (int c0 = 0; c0 < nact; c0 += BS) {
+      const int k = c0 + tid;
+      int i = -1, keep = 0;
+      if (k < nact) {
+        i = act[k];
+        const double c12 = chi2_of((double)P.inv_sigma2_1[i], err[4 * i], err[4 * i + 1]);
+        const double c21 = chi2_of((double)P.inv_sigma2_2[i], err[4 * i + 2], err[4 * i + 3]);
+        keep = !(c12 > th2 || c21 > th2);
+        if (!keep) P.inlier[i] = 0;
+      }
+      const uint64_t m = __ballot(keep);
+      const int pre = __popcll(m & ((1ull << lane) - 1));
+      if (lane == 0) S.scan[wid] = __popcll(m);
+      __syncthreads();  // every act[k] of this chunk has been read
+      int off = base;
+      for (int w = 0; w < wid; w++) off += S.scan[w];
+      if (keep && phase == 0) act[off + pre] = i;
+      int tot = 0;
+      for (int w = 0; w < BS / 64; w++) tot += S.scan[w];
+      base += tot;
+      __syncthreads();
+    }
+    __threadfence_block();
+    __syncthreads();
+    if (phase == 0) {
+      nBad = nact - base;
+      nact = base;
+      if (n - nBad < 10) {  // return 0: g2oS12 is not written back, the nulled matches stay nulled
+        early = true;
+        break;
+      }
+    } else {
+      nIn = base;
+    }
+  }
+  if (tid == 0) {
+    if (!early) {
+      P.S12_out[0] = S.S.q.x; P.S12_out[1] = S.S.q.y; P.S12_out[2] = S.S.q.z; P.S12_out[3] = S.S.q.w;
+      P.S12_out[4] = S.S.t[0]; P.S12_out[5] = S.S.t[1]; P.S12_out[6] = S.S.t[2];
+      P.S12_out[7] = S.S.s;
+    }
+    *P.n_in = early ? 0 : nIn;
+    if (P.n_bad) *P.n_bad = nBad;
+    if (P.iterations) {
+      P.iterations[0] = its0;
+      P.iterations[1] = its1;
+    }
+    if (P.trials) *P.trials = S.trials;
+  }
+}
+
+__global__ void k_debug_exp(const double* __restrict__ x, int n, double* __restrict__ y) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) y[i] = exp_det(x[i]);
+}
+
+__global__ void k_debug_sim3_exp(const double* __restrict__ in, int fix_scale, double* __restrict__ out) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  double u[7];
+#pragma unroll
+  for (int k = 0; k < 7; k++) u[k] = in[k];
+  if (fix_scale) u[6] = 0;
+  Sim3 S;
+  S.q.x = in[7]; S.q.y = in[8]; S.q.z = in[9]; S.q.w = in[10];
+  S.t[0] = in[11]; S.t[1] = in[12]; S.t[2] = in[13];
+  S.s = in[14];
+  const Sim3 r = sim3_mul(sim3_exp(u), S);
+  out[0] = r.q.x; out[1] = r.q.y; out[2] = r.q.z; out[3] = r.q.w;
+  out[4] = r.t[0]; out[5] = r.t[1]; out[6] = r.t[2];
+  out[7] = r.s;
+}
+
+}  // namespace osim3
+}  // namespace orbx
+
+// ------------------------------------------------------------------ C ABI
+namespace {
+
+orbx_status osim3_check(const orbx_optimize_sim3_problem& p) {
+  if (p.n < 0) return ORBX_ERR_ARG;
+  if (!p.S12_out || !p.n_in) return ORBX_ERR_ARG;
+  if (p.n > 0 && (!p.x3dc1 || !p.x3dc2 || !p.obs1 || !p.obs2 || !p.inv_sigma2_1 || !p.inv_sigma2_2 || !p.inlier))
+    return ORBX_ERR_ARG;
+  return ORBX_OK;
+}
+
+orbx_status pick_device(int device) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return ORBX_ERR_NODEV;
+  if (device < 0 || device >= ndev || hipSetDevice(device) != hipSuccess) return ORBX_ERR_ARG;
+  return ORBX_OK;
+}
+
+}  // namespace
+
+extern "C" orbx_status orbx_optimize_sim3(const orbx_optimize_sim3_problem* p, int device) {
+  if (!p) return ORBX_ERR_ARG;
+  const orbx_status chk = osim3_check(*p);
+  if (chk != ORBX_OK) return chk;
+  if (p->n_dev) return ORBX_ERR_ARG;  // device batches only
+  const orbx_status dv = pick_device(device);
+  if (dv != ORBX_OK) return dv;
+  using orbx::osim3::Dev;
+  const size_t n = (size_t)p->n;
+  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t o_x1 = 0, o_x2 = o_x1 + al(n * 12), o_o1 = o_x2 + al(n * 12), o_o2 = o_o1 + al(n * 8),
+               o_w1 = o_o2 + al(n * 8), o_w2 = o_w1 + al(n * 4), o_S = o_w2 + al(n * 4), o_in = o_S + al(64),
+               o_cnt = o_in + al(n), o_scr = o_cnt + al(32), o_act = o_scr + al(n * 32), o_dev = o_act + al(n * 4),
+               total = o_dev + al(sizeof(Dev));
+  orbx::ScratchGuard g(device);  // pooled lease: no per-call allocation (orbx_scratch.h)
+  if (!g.l || g.l->reserve(total, o_scr + sizeof(Dev)) != hipSuccess) return ORBX_ERR_HIP;
+  uint8_t* host = g.l->h;
+  std::memset(host + o_S, 0, o_scr - o_S);
+  if (n) {
+    std::memcpy(host + o_x1, p->x3dc1, n * 12);
+    std::memcpy(host + o_x2, p->x3dc2, n * 12);
+    std::memcpy(host + o_o1, p->obs1, n * 8);
+    std::memcpy(host + o_o2, p->obs2, n * 8);
+    std::memcpy(host + o_w1, p->inv_sigma2_1, n * 4);
+    std::memcpy(host + o_w2, p->inv_sigma2_2, n * 4);
+  }
+  uint8_t* d = g.l->d;
+  Dev pd;
+  pd.p = *p;
+  pd.p.x3dc1 = (const float*)(d + o_x1);
+  pd.p.x3dc2 = (const float*)(d + o_x2);
+  pd.p.obs1 = (const float*)(d + o_o1);
+  pd.p.obs2 = (const float*)(d + o_o2);
+  pd.p.inv_sigma2_1 = (const float*)(d + o_w1);
+  pd.p.inv_sigma2_2 = (const float*)(d + o_w2);
+  pd.p.S12_out = (double*)(d + o_S);
+  pd.p.inlier = (uint8_t*)(d + o_in);
+  int32_t* cnt = (int32_t*)(d + o_cnt);  // n_in | n_bad | iterations[2] | trials
+  pd.p.n_in = cnt;
+  pd.p.n_bad = cnt + 1;
+  pd.p.iterations = cnt + 2;
+  pd.p.trials = cnt + 4;
+  pd.err = (double*)(d + o_scr);
+  pd.act = (int*)(d + o_act);
+  std::memcpy(host + o_scr, &pd, sizeof(pd));  // the record rides in the staging block's tail
+  hipStream_t st = g.l->st;
+  hipError_t e = hipMemcpyAsync(d, host, o_scr, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d + o_dev, host + o_scr, sizeof(pd), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(orbx::osim3::k_optimize_sim3, dim3(1), dim3(orbx::osim3::BS), 0, st, (const Dev*)(d + o_dev));
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(host + o_S, d + o_S, o_scr - o_S, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = g.l->sync();
+  if (e != hipSuccess) return ORBX_ERR_HIP;
+  std::memcpy(p->S12_out, host + o_S, 64);
+  if (n) std::memcpy(p->inlier, host + o_in, n);
+  const int32_t* hc = (const int32_t*)(host + o_cnt);
+  *p->n_in = hc[0];
+  if (p->n_bad) *p->n_bad = hc[1];
+  if (p->iterations) std::memcpy(p->iterations, hc + 2, 8);
+  if (p->trials) *p->trials = hc[4];
+  return ORBX_OK;
+}
+
+extern "C" orbx_status orbx_optimize_sim3_device(const orbx_optimize_sim3_problem* problems, int n, void* stream) {
+  if (n < 0 || (n > 0 && !problems)) return ORBX_ERR_ARG;
+  if (n == 0) return ORBX_OK;
+  using orbx::osim3::Dev;
+  size_t rows = 0;
+  for (int i = 0; i < n; i++) {
+    const orbx_status s = osim3_check(problems[i]);
+    if (s != ORBX_OK) return s;
+    rows += (size_t)problems[i].n;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const size_t dev_bytes = sizeof(Dev) * n;
+  const size_t err_off = (dev_bytes + 255) & ~(size_t)255;
+  const size_t act_off = err_off + rows * 32;
+  uint8_t* d = nullptr;
+  if (hipMallocAsync((void**)&d, act_off + rows * 4 + 16, st) != hipSuccess) return ORBX_ERR_HIP;
+  std::vector<Dev> pd(n);
+  size_t r = 0;
+  for (int i = 0; i < n; i++) {
+    pd[i].p = problems[i];
+    pd[i].err = (double*)(d + err_off) + r * 4;
+    pd[i].act = (int*)(d + act_off) + r;
+    r += (size_t)problems[i].n;
+  }
+  hipError_t e = hipMemcpyAsync(d, pd.data(), dev_bytes, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(orbx::osim3::k_optimize_sim3, dim3(n), dim3(orbx::osim3::BS), 0, st, (const Dev*)d);
+    e = hipGetLastError();
+  }
+  // pageable source: hipMemcpyAsync returns once pd is staged, so pd may go
+  const hipError_t e2 = hipFreeAsync(d, st);
+  return e != hipSuccess ? ORBX_ERR_HIP : (e2 != hipSuccess ? ORBX_ERR_HIP : ORBX_OK);
+}
+
+// ------------------------------------------------------------------ debug probes (orbx_debug.h)
+extern "C" int orbx_debug_exp(const double* x, int n, double* y, int device) {
+  if (n < 0 || (n > 0 && (!x || !y))) return ORBX_ERR_ARG;
+  const orbx_status dv = pick_device(device);
+  if (dv != ORBX_OK) return dv;
+  if (n == 0) return ORBX_OK;
+  const size_t bytes = ((size_t)n * 8 + 255) & ~(size_t)255;
+  orbx::ScratchGuard g(device);
+  if (!g.l || g.l->reserve(2 * bytes, 2 * bytes) != hipSuccess) return ORBX_ERR_HIP;
+  std::memcpy(g.l->h, x, (size_t)n * 8);
+  hipStream_t st = g.l->st;
+  hipError_t e = hipMemcpyAsync(g.l->d, g.l->h, bytes, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(orbx::osim3::k_debug_exp, dim3((n + 255) / 256), dim3(256), 0, st, (const double*)g.l->d, n,
+                       (double*)(g.l->d + bytes));
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(g.l->h + bytes, g.l->d + bytes, bytes, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = g.l->sync();
+  if (e != hipSuccess) return ORBX_ERR_HIP;
+  std::memcpy(y, g.l->h + bytes, (size_t)n * 8);
+  return ORBX_OK;
+}
+
+extern "C" int orbx_debug_sim3_exp(const double update[7], const double S[8], int fix_scale, double out[8],
+                                   int device) {
+  if (!update || !S || !out) return ORBX_ERR_ARG;
+  const orbx_status dv = pick_device(device);
+  if (dv != ORBX_OK) return dv;
+  orbx::ScratchGuard g(device);
+  if (!g.l || g.l->reserve(512, 512) != hipSuccess) return ORBX_ERR_HIP;
+  double* h = (double*)g.l->h;
+  std::memcpy(h, update, 56);
+  std::memcpy(h + 7, S, 64);
+  hipStream_t st = g.l->st;
+  hipError_t e = hipMemcpyAsync(g.l->d, g.l->h, 256, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(orbx::osim3::k_debug_sim3_exp, dim3(1), dim3(64), 0, st, (const double*)g.l->d, fix_scale,
+                       (double*)(g.l->d + 256));
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(g.l->h + 256, g.l->d + 256, 64, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = g.l->sync();
+  if (e != hipSuccess) return ORBX_ERR_HIP;
+  std::memcpy(out, g.l->h + 256, 64);
+  return ORBX_OK;
+}

@@ -194,6 +194,38 @@ __device__ __forceinline__ void sincos_d(double x, double* s_out, double* c_out)
   *c_out = c;
 }
 
+// Double e^x from basic IEEE operations only (g2o::Sim3's std::exp(sigma) in optsim3.hip), the same
+// sequence in the tests' Python twin: k = rint(x / ln 2), r = (x - k ln2_hi) - k ln2_lo (Cody-Waite,
+// |r| < 0.3466), e^r = 1 + (r + r^2 p(r)) with p the Taylor series of (e^r - 1 - r) / r^2 to r^11 by
+// Horner (truncation below 0.06 units of 2^-53), times 2^k built from its exponent bits (exact; k is
+// clamped to the normal exponents, domain |x| <= 708).  exp_det(0) is exactly 1.  Against the true
+// exponential the result is within 2.5 * 2^-53 relative for |x| <= 2 (derived term by term in
+// tests/optsim3_literal.py).
+__host__ __device__ inline double exp_det(double x) {
+  if (x != x) return x;
+  double kd = __builtin_rint(x * 1.44269504088896338700e+00);
+  kd = kd > 1023.0 ? 1023.0 : kd;
+  kd = kd < -1022.0 ? -1022.0 : kd;
+  const double r = (x - kd * 6.93147180369123816490e-01) - kd * 1.90821492927058770002e-10;
+  double p = 1.0 / 6227020800.0;
+  p = p * r + 1.0 / 479001600.0;
+  p = p * r + 1.0 / 39916800.0;
+  p = p * r + 1.0 / 3628800.0;
+  p = p * r + 1.0 / 362880.0;
+  p = p * r + 1.0 / 40320.0;
+  p = p * r + 1.0 / 5040.0;
+  p = p * r + 1.0 / 720.0;
+  p = p * r + 1.0 / 120.0;
+  p = p * r + 1.0 / 24.0;
+  p = p * r + 1.0 / 6.0;
+  p = p * r + 0.5;
+  const double e = 1.0 + (r + (r * r) * p);
+  const long long bits = ((long long)kd + 1023) << 52;
+  double scale;
+  __builtin_memcpy(&scale, &bits, sizeof(scale));
+  return e * scale;
+}
+
 // Double atan2 from basic IEEE operations only (+ - * / rint, compares), the same sequence on the
 // host, the device and in the tests' Python twin; std::atan2's special values (signed zeros, axes,
 // infinities, NaN).  t = min(|y|,|x|) / max(|y|,|x|) in [0,1]; atan t = atan c + atan((t-c)/(1+tc))

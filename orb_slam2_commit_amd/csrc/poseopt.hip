@@ -27,98 +27,20 @@
 #include "orbx_device.h"
 #include "orbx_scratch.h"
 #include "orbx_internal.h"
+#include "orbx_lm.h"
 
 namespace orbx {
 namespace pose {
 
+using namespace lm;  // Quat, qmul, qrot, qmat, mat2q, qnormalize, ldlt<N>, lds_chain
+
 constexpr int PBS = 256;
 constexpr int kRow = 32;  // scratch doubles per edge: 27 terms | err[3] | chi term | pad
 
-struct Quat {
-  double x, y, z, w;
-};
 struct SE3 {
   Quat q;
   double t[3];
 };
-
-__device__ __forceinline__ Quat qmul(const Quat& a, const Quat& b) {
-  Quat r;
-  r.w = a.w * b.w - (a.x * b.x + a.y * b.y + a.z * b.z);
-  r.x = a.w * b.x + b.w * a.x + (a.y * b.z - a.z * b.y);
-  r.y = a.w * b.y + b.w * a.y + (a.z * b.x - a.x * b.z);
-  r.z = a.w * b.z + b.w * a.z + (a.x * b.y - a.y * b.x);
-  return r;
-}
-__device__ __forceinline__ void qrot(const Quat& q, const double v[3], double out[3]) {
-  double uv[3] = {q.y * v[2] - q.z * v[1], q.z * v[0] - q.x * v[2], q.x * v[1] - q.y * v[0]};
-  uv[0] += uv[0];
-  uv[1] += uv[1];
-  uv[2] += uv[2];
-  const double c[3] = {q.y * uv[2] - q.z * uv[1], q.z * uv[0] - q.x * uv[2], q.x * uv[1] - q.y * uv[0]};
-#pragma unroll
-  for (int i = 0; i < 3; i++) out[i] = v[i] + q.w * uv[i] + c[i];
-}
-__device__ __forceinline__ void qmat(const Quat& q, double R[9]) {
-  const double tx = 2 * q.x, ty = 2 * q.y, tz = 2 * q.z;
-  const double twx = tx * q.w, twy = ty * q.w, twz = tz * q.w;
-  const double txx = tx * q.x, txy = ty * q.x, txz = tz * q.x;
-  const double tyy = ty * q.y, tyz = tz * q.y, tzz = tz * q.z;
-  R[0] = 1 - (tyy + tzz); R[1] = txy - twz;       R[2] = txz + twy;
-  R[3] = txy + twz;       R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
-  R[6] = txz - twy;       R[7] = tyz + twx;       R[8] = 1 - (txx + tyy);
-}
-__device__ __forceinline__ Quat mat2q(const double m[9]) {
-  Quat q;
-  double t = m[0] + m[4] + m[8];
-  if (t > 0) {
-    t = __builtin_sqrt(t + 1.0);
-    q.w = 0.5 * t;
-    t = 0.5 / t;
-    q.x = (m[7] - m[5]) * t;
-    q.y = (m[2] - m[6]) * t;
-    q.z = (m[3] - m[1]) * t;
-  } else {
-    int i = 0;
-    if (m[4] > m[0]) i = 1;
-    if (m[8] > (i == 0 ? m[0] : m[4])) i = 2;
-    // the three cases spelled out on named entries: no array indexed at run time (which put the
-    // matrix in scratch memory); same arithmetic as c[i], c[j], c[k] with (i, j, k) cyclic
-    if (i == 0) {  // (0, 1, 2)
-      t = __builtin_sqrt(m[0] - m[4] - m[8] + 1.0);
-      const double ci = 0.5 * t;
-      t = 0.5 / t;
-      q.w = (m[7] - m[5]) * t;
-      q.x = ci;
-      q.y = (m[3] + m[1]) * t;
-      q.z = (m[6] + m[2]) * t;
-    } else if (i == 1) {  // (1, 2, 0)
-      t = __builtin_sqrt(m[4] - m[8] - m[0] + 1.0);
-      const double ci = 0.5 * t;
-      t = 0.5 / t;
-      q.w = (m[2] - m[6]) * t;
-      q.y = ci;
-      q.z = (m[7] + m[5]) * t;
-      q.x = (m[1] + m[3]) * t;
-    } else {  // (2, 0, 1)
-      t = __builtin_sqrt(m[8] - m[0] - m[4] + 1.0);
-      const double ci = 0.5 * t;
-      t = 0.5 / t;
-      q.w = (m[3] - m[1]) * t;
-      q.z = ci;
-      q.x = (m[2] + m[6]) * t;
-      q.y = (m[5] + m[7]) * t;
-    }
-  }
-  return q;
-}
-__device__ __forceinline__ void qnormalize(Quat& q) {
-  if (q.w < 0) {
-    q.x = -q.x; q.y = -q.y; q.z = -q.z; q.w = -q.w;
-  }
-  const double n = __builtin_sqrt(q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w);
-  q.x /= n; q.y /= n; q.z /= n; q.w /= n;
-}
 
 // SE3Quat::exp(update), types/se3quat.h:223-257 (then operator* with T)
 __device__ __forceinline__ SE3 se3_exp(const double u[6]) {
@@ -163,131 +85,6 @@ __device__ __forceinline__ SE3 se3_mul(const SE3& a, const SE3& b) {
   r.q = qmul(a.q, b.q);
   qnormalize(r.q);
   return r;
-}
-
-// Eigen::LDLT<MatrixXd> (diagonal pivoting) + solve; false when !isPositive().
-// Every loop is unrolled and the pivot swaps / the permutation of the right-hand side run as
-// unrolled compare-and-swap over the candidate rows, so every index is a compile-time constant:
-// the matrix lives in registers (a runtime index put it in scratch memory, ~25k cycles per call
-// on the LM's serial path).  Same operations in the same order as before.
-// conditional exchange of two registers by value selects (a branch per candidate let the
-// compiler merge the paths into pointer phis, which sends the array to scratch memory)
-__device__ __forceinline__ void cswap(bool sw, double& a, double& b) {
-  const double x = a, y = b;
-  a = sw ? y : x;
-  b = sw ? x : y;
-}
-template <int K, int C>
-__device__ __forceinline__ void ldlt6_swap(double (&m)[36], bool sw) {  // transpositions k <-> c (c > k)
-#pragma unroll
-  for (int j = 0; j < K; j++) cswap(sw, m[6 * K + j], m[6 * C + j]);
-#pragma unroll
-  for (int i = C + 1; i < 6; i++) cswap(sw, m[6 * i + K], m[6 * i + C]);
-  cswap(sw, m[7 * K], m[7 * C]);
-#pragma unroll
-  for (int i = K + 1; i < C; i++) cswap(sw, m[6 * i + K], m[6 * C + i]);
-}
-template <int K, int C>
-__device__ __forceinline__ void ldlt6_swap_to(double (&m)[36], int big) {
-  if constexpr (C < 6) {
-    ldlt6_swap<K, C>(m, big == C);
-    ldlt6_swap_to<K, C + 1>(m, big);
-  }
-}
-template <int K>
-__device__ __forceinline__ void ldlt6_step(double (&m)[36], int (&tr)[6], int& sign, bool& zero) {
-  if constexpr (K < 6) {
-    if (!zero) {
-      int big = K;
-      double bv = __builtin_fabs(m[7 * K]);
-#pragma unroll
-      for (int i = K + 1; i < 6; i++)
-        if (__builtin_fabs(m[7 * i]) > bv) {
-          bv = __builtin_fabs(m[7 * i]);
-          big = i;
-        }
-      if (K == 0 && !(bv > 0.0)) {
-#pragma unroll
-        for (int j = 0; j < 6; j++) tr[j] = j;
-#pragma unroll
-        for (int j = 0; j < 6; j++) m[7 * j] = 0.0;
-        sign = 0;
-        zero = true;
-      } else {
-        tr[K] = big;
-        ldlt6_swap_to<K, K + 1>(m, big);
-        if constexpr (K > 0) {
-          double temp[6];
-#pragma unroll
-          for (int j = 0; j < K; j++) temp[j] = m[7 * j] * m[6 * K + j];
-          double dot = m[6 * K] * temp[0];
-#pragma unroll
-          for (int j = 1; j < K; j++) dot = dot + m[6 * K + j] * temp[j];
-          m[7 * K] -= dot;
-#pragma unroll
-          for (int i = K + 1; i < 6; i++) {
-            double sv = m[6 * i] * temp[0];
-#pragma unroll
-            for (int j = 1; j < K; j++) sv = sv + m[6 * i + j] * temp[j];
-            m[6 * i + K] -= sv;
-          }
-        }
-        const double akk = m[7 * K];
-        if (__builtin_fabs(akk) > 0.0) {
-#pragma unroll
-          for (int i = K + 1; i < 6; i++) m[6 * i + K] /= akk;
-        }
-        if (akk > 0) sign = (sign == 2 || sign == 3) ? 3 : 1;
-        else if (akk < 0) sign = (sign == 1 || sign == 3) ? 3 : 2;
-      }
-    }
-    ldlt6_step<K + 1>(m, tr, sign, zero);
-  }
-}
-// y[k] <-> y[t] for the unrolled k, t >= k (the transposition's other row)
-template <int K>
-__device__ __forceinline__ void perm_swap(double (&y)[6], int t) {
-#pragma unroll
-  for (int c = K + 1; c < 6; c++) cswap(t == c, y[K], y[c]);
-}
-__device__ __forceinline__ bool ldlt6(const double* Hin, const double* b, double* x) {
-  double m[36];
-#pragma unroll
-  for (int i = 0; i < 36; i++) m[i] = Hin[i];
-  int tr[6] = {0, 1, 2, 3, 4, 5};
-  int sign = 0;
-  bool zero = false;
-  ldlt6_step<0>(m, tr, sign, zero);
-  if (!(sign == 1 || sign == 0)) return false;
-  double y[6];
-#pragma unroll
-  for (int i = 0; i < 6; i++) y[i] = b[i];
-  perm_swap<0>(y, tr[0]);
-  perm_swap<1>(y, tr[1]);
-  perm_swap<2>(y, tr[2]);
-  perm_swap<3>(y, tr[3]);
-  perm_swap<4>(y, tr[4]);
-  perm_swap<5>(y, tr[5]);
-#pragma unroll
-  for (int i = 0; i < 6; i++)
-#pragma unroll
-    for (int j = 0; j < i; j++) y[i] -= m[6 * i + j] * y[j];
-  const double tol = 2.2250738585072014e-308;  // numeric_limits<double>::min()
-#pragma unroll
-  for (int i = 0; i < 6; i++) y[i] = __builtin_fabs(m[7 * i]) > tol ? y[i] / m[7 * i] : 0.0;
-#pragma unroll
-  for (int i = 5; i >= 0; i--)
-#pragma unroll
-    for (int j = i + 1; j < 6; j++) y[i] -= m[6 * j + i] * y[j];
-  perm_swap<5>(y, tr[5]);
-  perm_swap<4>(y, tr[4]);
-  perm_swap<3>(y, tr[3]);
-  perm_swap<2>(y, tr[2]);
-  perm_swap<1>(y, tr[1]);
-  perm_swap<0>(y, tr[0]);
-#pragma unroll
-  for (int i = 0; i < 6; i++) x[i] = y[i];
-  return true;
 }
 
 struct PoseDev {
@@ -392,29 +189,6 @@ __device__ __forceinline__ void jacobian(const SE3& T, const orbx_pose_problem& 
 constexpr int kCh = PBS;
 constexpr int kTerm = 28, kTs = 29;
 constexpr int kChiCh = kCh * kTs;  // chi terms per trial pass (one double each)
-
-// sequential sum of m LDS values at stride st (insertion order kept), software-pipelined: the next
-// 8 values load while the current 8 are added, so the chain runs at the add latency
-__device__ __forceinline__ double lds_chain(const double* base, int m, int st, double s, bool sub) {
-  const int m8 = m & ~7;
-  double v[8];
-  if (m8 > 0) {
-#pragma unroll
-    for (int u = 0; u < 8; u++) v[u] = base[u * st];
-  }
-  for (int k = 0; k < m8; k += 8) {
-    double w[8];
-    const int kn = k + 8 < m8 ? k + 8 : k;  // last batch: a harmless reload
-#pragma unroll
-    for (int u = 0; u < 8; u++) w[u] = base[(kn + u) * st];
-#pragma unroll
-    for (int u = 0; u < 8; u++) s = sub ? s - v[u] : s + v[u];
-#pragma unroll
-    for (int u = 0; u < 8; u++) v[u] = w[u];
-  }
-  for (int k = m8; k < m; k++) s = sub ? s - base[k * st] : s + base[k * st];
-  return s;
-}
 
 struct Shared {
   SE3 T, T0, bak;
@@ -598,7 +372,7 @@ __global__ __launch_bounds__(PBS) void k_pose_optimization(const PoseDev* __rest
             for (int j = 0; j < 36; j++) Hd[j] = S.H[j];
 #pragma unroll
             for (int j = 0; j < 6; j++) Hd[7 * j] += S.lambda;
-            const bool ok2 = ldlt6(Hd, S.b, S.x);
+            const bool ok2 = ldlt<6>(Hd, S.b, S.x);
             S.ok2 = ok2;
             POSE_TS(9);
             if (ok2) S.T = se3_mul(se3_exp(S.x), S.T);

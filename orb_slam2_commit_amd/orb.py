@@ -639,6 +639,22 @@ class Optimizer:
         check(_lib.lib().orbx_pose_optimization(C.byref(p), self.device), "orbx_pose_optimization")
         return int(out["ngood"][0]), out["Tcw_out"], out["outlier"][:len(pr["obs"])], out["iterations"]
 
+    def OptimizeSim3(self, problem):
+        """Optimizer::OptimizeSim3 -- src/Optimizer.cc:1220-1456.  problem: dict(x3dc1[n,3], x3dc2[n,3]
+        (camera-frame points of the correspondences the intake loop keeps, in its order), obs1[n,2],
+        obs2[n,2], inv_sigma2_1[n], inv_sigma2_2[n], K1, K2 (fx, fy, cx, cy), S12 (8 doubles: quaternion
+        x, y, z, w, translation, scale), th2, bFixScale).  Returns (nIn, S12[8], inlier[n] (0 where the
+        reference nulls vpMatches1), n_bad, iterations[2], trials)."""
+        pr = dict(problem)
+        for k, w in (("x3dc1", 3), ("x3dc2", 3), ("obs1", 2), ("obs2", 2)):
+            pr[k] = np.ascontiguousarray(problem[k], np.float32).reshape(-1, w)
+        for k in ("inv_sigma2_1", "inv_sigma2_2"):
+            pr[k] = np.ascontiguousarray(problem[k], np.float32).reshape(-1)
+        p, out = optimize_sim3_problem_struct(pr)
+        check(_lib.lib().orbx_optimize_sim3(C.byref(p), self.device), "orbx_optimize_sim3")
+        return (int(out["n_in"][0]), out["S12_out"], out["inlier"][:len(pr["x3dc1"])], int(out["n_bad"][0]),
+                out["iterations"], int(out["trials"][0]))
+
     def LocalBundleAdjustment(self, prob, stop=False):
         """prob: dict(Tcw[n,12], fixed[n], intr[n,5] fx,fy,cx,cy,bf, Xw[m,3], edge_point, edge_cam,
         obs[e,3] (u, v, ur; ur<0 mono), inv_sigma2[e]).  ``stop`` mirrors *pbStopFlag: a bool, or
@@ -705,6 +721,28 @@ def pose_problem_struct(prob, outputs=None):
     p.Tcw[:] = _f32(prob["Tcw"]).reshape(16).tolist()
     p.Tcw_out, p.outlier, p.ngood = ptr(outputs["Tcw_out"]), ptr(outputs["outlier"]), ptr(outputs["ngood"])
     p.iterations = ptr(outputs.get("iterations"))
+    return p, outputs
+
+
+def optimize_sim3_problem_struct(prob, outputs=None):
+    """orbx_optimize_sim3_problem from a dict (host numpy or device tensors); outputs allocated on the
+    host when absent.  Returns (struct, outputs)."""
+    n = len(prob["x3dc1"])
+    if outputs is None:
+        outputs = dict(S12_out=np.zeros(8, np.float64), inlier=np.zeros(max(n, 1), np.uint8),
+                       n_in=np.zeros(1, np.int32), n_bad=np.zeros(1, np.int32), iterations=np.zeros(2, np.int32),
+                       trials=np.zeros(1, np.int32))
+    p = _lib.OptSim3Problem()
+    p.n = n
+    for k in ("x3dc1", "x3dc2", "obs1", "obs2", "inv_sigma2_1", "inv_sigma2_2"):
+        setattr(p, k, ptr(prob[k]))
+    p.K1[:] = _f32(prob["K1"]).reshape(4).tolist()
+    p.K2[:] = _f32(prob["K2"]).reshape(4).tolist()
+    p.S12[:] = np.asarray(prob["S12"], np.float64).reshape(8).tolist()
+    p.th2 = float(prob["th2"])
+    p.fix_scale = 1 if prob["bFixScale"] else 0
+    for k in ("S12_out", "inlier", "n_in", "n_bad", "iterations", "trials"):
+        setattr(p, k, ptr(outputs.get(k)))
     return p, outputs
 
 

@@ -13,9 +13,12 @@
 #include <array>
 #include <vector>
 
+#include "g2o_sim3_min.h"
 #include "opencv_min.hpp"
 
 namespace ORB_SLAM2 {
+
+class MapPoint;
 
 struct LocalBAProblem {
   struct Camera {
@@ -60,6 +63,13 @@ class Optimizer {
   // The explicit-problem form.  Throws std::runtime_error on a library error.
   void static LocalBundleAdjustment(const LocalBAProblem& problem, bool* pbStopFlag, LocalBAResult& result,
                                     int device = 0);
+
+  // include/Optimizer.h, src/Optimizer.cc:1220-1456 (called at src/LoopClosing.cc:425-444): refines
+  // g2oS12 over the matches of vpMatches1 (per keypoint of pKF1, the MapPoint of pKF2 or NULL) on the
+  // MI355X.  Gathers as :1267-1384 does, nulls the outliers in vpMatches1, writes g2oS12 only when
+  // the reference does (not on the early return below 10 survivors) and returns the inlier count.
+  int static OptimizeSim3(KeyFrame* pKF1, KeyFrame* pKF2, std::vector<MapPoint*>& vpMatches1, g2o::Sim3& g2oS12,
+                          const float th2, const bool bFixScale);
 
   // test hook: called with the window the graph form gathered, before it runs (NULL: none)
   static void (*mpfnGatheredHook)(const LocalBAProblem& problem, const std::vector<KeyFrame*>& cameras);

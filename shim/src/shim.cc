@@ -1513,6 +1513,71 @@ int Optimizer::PoseOptimization(Frame* pFrame) {
   return ngood;
 }
 
+int Optimizer::OptimizeSim3(KeyFrame* pKF1, KeyFrame* pKF2, std::vector<MapPoint*>& vpMatches1, g2o::Sim3& g2oS12,
+                            const float th2, const bool bFixScale) {
+  // src/Optimizer.cc:1236-1384: one correspondence per match with both points good and pMP2 observed
+  // in pKF2; the camera-frame points through the float small-gemm path Sim3Solver's gather uses
+  const cv::Mat R1w = pKF1->GetRotation(), t1w = pKF1->GetTranslation();
+  const cv::Mat R2w = pKF2->GetRotation(), t2w = pKF2->GetTranslation();
+  const int N = (int)vpMatches1.size();
+  const std::vector<MapPoint*> vpMapPoints1 = pKF1->GetMapPointMatches();
+  std::vector<float> x1, x2, o1, o2, w1, w2;
+  std::vector<size_t> vnIndexEdge;
+  for (int i = 0; i < N; i++) {
+    if (!vpMatches1[i]) continue;
+    MapPoint* pMP1 = vpMapPoints1[i];
+    MapPoint* pMP2 = vpMatches1[i];
+    const int i2 = pMP2->GetIndexInKeyFrame(pKF2);
+    if (!pMP1) continue;
+    if (pMP1->isBad() || pMP2->isBad() || i2 < 0) continue;
+    float X[3];
+    mat3x1(R1w, t1w, pMP1->GetWorldPos(), X);
+    x1.insert(x1.end(), X, X + 3);
+    mat3x1(R2w, t2w, pMP2->GetWorldPos(), X);
+    x2.insert(x2.end(), X, X + 3);
+    const cv::KeyPoint& kpUn1 = pKF1->mvKeysUn[i];
+    o1.push_back(kpUn1.pt.x);
+    o1.push_back(kpUn1.pt.y);
+    w1.push_back(pKF1->mvInvLevelSigma2[kpUn1.octave]);
+    const cv::KeyPoint& kpUn2 = pKF2->mvKeysUn[i2];
+    o2.push_back(kpUn2.pt.x);
+    o2.push_back(kpUn2.pt.y);
+    w2.push_back(pKF2->mvInvLevelSigma2[kpUn2.octave]);
+    vnIndexEdge.push_back((size_t)i);
+  }
+  const int n = (int)vnIndexEdge.size();
+  orbx_optimize_sim3_problem p;
+  std::memset(&p, 0, sizeof(p));
+  p.n = n;
+  p.x3dc1 = x1.data();
+  p.x3dc2 = x2.data();
+  p.obs1 = o1.data();
+  p.obs2 = o2.data();
+  p.inv_sigma2_1 = w1.data();
+  p.inv_sigma2_2 = w2.data();
+  p.K1[0] = pKF1->fx, p.K1[1] = pKF1->fy, p.K1[2] = pKF1->cx, p.K1[3] = pKF1->cy;  // mK's entries
+  p.K2[0] = pKF2->fx, p.K2[1] = pKF2->fy, p.K2[2] = pKF2->cx, p.K2[3] = pKF2->cy;
+  const g2o::Quaterniond& q = g2oS12.rotation();
+  const g2o::Vector3d& t = g2oS12.translation();
+  const double S[8] = {q.x(), q.y(), q.z(), q.w(), t[0], t[1], t[2], g2oS12.scale()};
+  std::memcpy(p.S12, S, sizeof(S));
+  p.th2 = th2;
+  p.fix_scale = bFixScale ? 1 : 0;
+  double So[8];
+  std::vector<uint8_t> inlier(n > 0 ? n : 1, 1);
+  int32_t n_in = 0, n_bad = 0;
+  p.S12_out = So;
+  p.inlier = inlier.data();
+  p.n_in = &n_in;
+  p.n_bad = &n_bad;
+  check(orbx_optimize_sim3(&p, gOrbxDevice), "orbx_optimize_sim3");
+  for (int k = 0; k < n; k++)
+    if (!inlier[k]) vpMatches1[vnIndexEdge[k]] = static_cast<MapPoint*>(NULL);
+  if (n - n_bad < 10) return 0;  // :1423-1424: g2oS12 is not written back
+  g2oS12 = g2o::Sim3(g2o::Quaterniond(So[3], So[0], So[1], So[2]), g2o::Vector3d{So[4], So[5], So[6]}, So[7]);
+  return n_in;
+}
+
 void Optimizer::LocalBundleAdjustment(KeyFrame* pKF, bool* pbStopFlag, Map* pMap) {
   // src/Optimizer.cc:532-551: the local KeyFrames (pKF and its non-bad covisibles)
   std::list<KeyFrame*> lLocalKeyFrames;

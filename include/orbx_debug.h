@@ -87,6 +87,50 @@ typedef struct {
 /* NULL restores the defaults. */
 int orbx_debug_ba_options(orbx_ba* h, const orbx_ba_debug_options* options);
 
+/* Capture of one LM trial's linear algebra (tests only; off by default, and while off the solver
+ * launches nothing for it).  orbx_debug_ba_capture_select arms the handle for its next orbx_ba_run /
+ * orbx_ba_run_bool (the selection holds for that one run; orbx_ba_run_many does not capture): the first
+ * trial of phase `phase` (0: the robust optimize(5), 1: optimize(10) on the inliers) whose iteration
+ * index within the phase is `it` (-1: any) and whose trial index within its iteration is `q` (the value
+ * LmState::qmax has when the trial starts).  (0,0,0) is phase 1's entry trial, (0,1,0) its first
+ * relinearised trial, (1,0,0) phase 2's entry trial, (p,-1,1) the first retry of phase p.  phase < 0
+ * disarms.  The run's results are bit-identical with and without a capture.
+ *
+ * orbx_debug_ba_capture_read copies item `what` of the last capture to dst and returns the item's size
+ * in bytes (copies min(cap, size)); ORBX_ERR_STATE when no capture fired (HEADER is always readable
+ * and says so), ORBX_ERR_ARG otherwise.  Items are double unless marked int32.  Sizes: nc cameras, np
+ * points, ne edges of the problem; na active edges (positions), npa active points, nposes free
+ * cameras with an active edge in the captured phase; N = 6 * nposes.
+ *
+ * Two states are recorded.  The CURRENT state (CQ, CT, X) is what the device held when the trial's
+ * solve began: the state EERR was computed at.  The LINEARISED state is what the trial's step is applied
+ * to: CBAK / XBAK for the free poses / active points, the current state elsewhere.  They are equal on a
+ * q = 0 trial; on a retry the current state is still the rejected estimate (k_ba_update pops it), and
+ * EERR are that estimate's errors, as g2o keeps them. */
+enum {
+  ORBX_BA_CAP_HEADER = 0,     /* int32 x12: fired, phase, it, q, solve ok, trial index within the phase,
+                                 nc, np, ne, na, npa, nposes                                            */
+  ORBX_BA_CAP_LAMBDA_CHI = 1, /* x2: lambda the trial used, LmState::currentChi at its start            */
+  ORBX_BA_CAP_CQ = 2,         /* nc x4: current rotation quaternions (x, y, z, w)                       */
+  ORBX_BA_CAP_CT = 3,         /* nc x3: current translations                                            */
+  ORBX_BA_CAP_X = 4,          /* np x3: current points                                                  */
+  ORBX_BA_CAP_EERR = 5,       /* ne x3: stored edge errors (row 2 of a mono edge is 0; edges outside ACT
+                                 keep whatever an earlier phase left)                                   */
+  ORBX_BA_CAP_S = 6,          /* N x N row-major: k_ba_schur_fin's reduced matrix before the LDLT touches
+                                 it; every entry is defined (both triangles are written)                */
+  ORBX_BA_CAP_BS = 7,         /* N: its right-hand side                                                  */
+  ORBX_BA_CAP_XP = 8,         /* N: the solve's pose step (zero when the solve failed, also the next three) */
+  ORBX_BA_CAP_CBAK = 9,       /* nposes x7: q (x, y, z, w), t of pose i's camera before the trial's update */
+  ORBX_BA_CAP_XBAK = 10,      /* npa x3: active point i before the update                               */
+  ORBX_BA_CAP_XL = 11,        /* npa x3: the point step, X after the update minus XBAK                  */
+  ORBX_BA_CAP_ACT = 12,       /* int32 na: active edge ids in position order (point-major)              */
+  ORBX_BA_CAP_POSE_CAM = 13,  /* int32 nposes: Hessian pose index -> camera                             */
+  ORBX_BA_CAP_PT_ID = 14,     /* int32 npa: active point index -> point                                 */
+  ORBX_BA_CAP_EROBUST = 15    /* int32 ne: 1 where the edge carries its Huber kernel                    */
+};
+int orbx_debug_ba_capture_select(orbx_ba* h, int phase, int it, int q);
+long long orbx_debug_ba_capture_read(orbx_ba* h, int what, void* dst, size_t cap);
+
 /* On-box HBM reference: copy `bytes` (multiple of 16) between two device
  * buffers with a streaming 16-B kernel, reps times on the null stream;
  * *ms = mean time per copy (2 * bytes of HBM traffic each). */

@@ -315,7 +315,9 @@ struct Optimizer {
   int trials = 0;
   explicit Optimizer(Problem& p, const volatile int* s) : P(p), stop(s) {}
 
-  bool terminate() const { return stop && *stop; }
+  // (+ test hook ORBX_BA_RAISE_STOP_AFTER = n: the flag reads raised at the polls that follow trial
+  // t >= n of a phase, 0-based within the phase -- the rule of the GPU library's raise_stop_after)
+  bool terminate() const { return (stop && *stop) || (raise_after >= 0 && phase_trial > raise_after); }
 
   // SparseOptimizer::initializeOptimization(level) + buildIndexMapping
   void initialize(int level) {
@@ -463,6 +465,10 @@ struct Optimizer {
     }
     std::vector<double> bs(N);
     for (int i = 0; i < N; i++) bs[i] = bp[i] - coef[i];
+    if (keep_reduced) {  // oracle_ba_linear_step
+      kept_S = S;
+      kept_bs = bs;
+    }
     std::vector<double> xp;
     if (N > 0) {
       if (!ldlt_solve(S, N, bs, xp)) return false;
@@ -561,6 +567,10 @@ struct Optimizer {
   // library's ORBX_BA_NAN_TRIAL does
   int nan_trial = std::getenv("ORBX_BA_NAN_TRIAL") ? std::atoi(std::getenv("ORBX_BA_NAN_TRIAL")) : -1;
   int phase_trial = 0;
+  int raise_after = std::getenv("ORBX_BA_RAISE_STOP_AFTER") ? std::atoi(std::getenv("ORBX_BA_RAISE_STOP_AFTER")) : -1;
+  // oracle_ba_linear_step: solve_damped keeps its reduced system
+  bool keep_reduced = false;
+  std::vector<double> kept_S, kept_bs;
 
   int optimize(int iterations, double* final_chi) {
     int it = 0;
@@ -628,7 +638,7 @@ extern "C" int oracle_local_ba(const oracle_ba_problem* pb, oracle_ba_result* re
   }
   opt.initialize(-1);
   res->iterations[0] = opt.optimize(5, &res->chi2[0]);
-  bool doMore = !(stop_flag && *stop_flag);
+  bool doMore = !opt.terminate();  // (the flag, or the stop hook having fired in phase 1)
   if (doMore) {
     for (Edge& e : P.edges) {  // :764-802 (errors as left by the last computeActiveErrors)
       const double th = e.stereo ? 7.815 : 5.991;
@@ -707,4 +717,61 @@ extern "C" void oracle_se3_exp_mul(const double u[6], const double q[4], const d
   q_out[2] = R.q.z;
   q_out[3] = R.q.w;
   for (int i = 0; i < 3; i++) t_out[i] = R.t[i];
+}
+
+/* One linear step of the solver at an explicit state (cq xyzw per camera, ct, X), on the edges with
+ * active != 0 (robust != 0: with the Huber kernel) at damping lambda: computeActiveErrors, buildSystem,
+ * setLambda + Schur + solve + back substitution.  Outputs: S (N x N row-major, both triangles), bs (N),
+ * x (N pose entries, then 3 per active point in point order), err (3 per edge, written for the active
+ * edges), sizes = {nposes, npts, solve ok}.  S, bs and x may be sized for every camera and point. */
+extern "C" int oracle_ba_linear_step(const oracle_ba_problem* pb, const double* cq, const double* ct, const double* X,
+                                     const uint8_t* active, const uint8_t* robust, double lambda, double* S,
+                                     double* bs, double* x, double* err, int* sizes) {
+  Problem P;
+  const int nc = pb->n_cams, np = pb->n_points, ne = pb->n_edges;
+  P.cams.resize(nc);
+  P.cam_fixed.resize(nc);
+  for (int c = 0; c < nc; c++) {
+    P.cams[c].q = {cq[4 * c], cq[4 * c + 1], cq[4 * c + 2], cq[4 * c + 3]};
+    for (int i = 0; i < 3; i++) P.cams[c].t[i] = ct[3 * c + i];
+    P.cam_fixed[c] = pb->fixed ? pb->fixed[c] : 0;
+  }
+  P.pts.assign(X, X + 3 * (size_t)np);
+  const float thMono = std::sqrt(5.991f), thStereo = std::sqrt(7.815f);
+  P.edges.resize(ne);
+  for (int i = 0; i < ne; i++) {
+    Edge& e = P.edges[i];
+    e.point = pb->edge_point[i];
+    e.cam = pb->edge_cam[i];
+    e.stereo = pb->obs[3 * i + 2] >= 0;
+    for (int k = 0; k < 3; k++) e.obs[k] = pb->obs[3 * i + k];
+    e.info = pb->inv_sigma2[i];
+    const float* in = pb->intr + 5 * e.cam;
+    e.fx = in[0];
+    e.fy = in[1];
+    e.cx = in[2];
+    e.cy = in[3];
+    e.bf = in[4];
+    e.delta = e.stereo ? thStereo : thMono;
+    e.dsqr = (float)(e.delta * e.delta);
+    e.robust = robust[i] != 0;
+    e.level = active[i] ? 0 : 1;
+  }
+  Optimizer opt(P, nullptr);
+  opt.keep_reduced = true;
+  opt.initialize(0);
+  opt.compute_active_errors();
+  opt.build_system();
+  const bool ok = opt.solve_damped(lambda);
+  const int N = 6 * opt.nposes;
+  sizes[0] = opt.nposes;
+  sizes[1] = opt.npts;
+  sizes[2] = ok ? 1 : 0;
+  for (size_t i = 0; i < opt.kept_S.size(); i++) S[i] = opt.kept_S[i];
+  for (size_t i = 0; i < opt.kept_bs.size(); i++) bs[i] = opt.kept_bs[i];
+  if (ok)
+    for (size_t i = 0; i < (size_t)N + 3 * (size_t)opt.npts; i++) x[i] = opt.x[i];
+  for (int i : opt.active_edges)
+    for (int k = 0; k < 3; k++) err[3 * i + k] = P.edges[i].err[k];
+  return 0;
 }

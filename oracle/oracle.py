@@ -128,6 +128,7 @@ def lib():
         L.oracle_local_ba.argtypes = [C.POINTER(BaProblem), C.POINTER(BaResult), P]
         L.oracle_ba_edge_probe.argtypes = [P, P, P, P, C.c_int, P, P, P, P]
         L.oracle_ba_edge_probe.restype = None
+        L.oracle_ba_linear_step.argtypes = [C.POINTER(BaProblem), P, P, P, P, P, C.c_double, P, P, P, P, P]
         L.oracle_se3_exp_mul.argtypes = [P, P, P, P, P]
         L.oracle_se3_exp_mul.restype = None
         L.oracle_pnp_create.argtypes = [C.c_int, P, P, P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_double,
@@ -351,6 +352,28 @@ def se3_exp_mul(u, q, t):
     qo, to = np.zeros(4), np.zeros(3)
     lib().oracle_se3_exp_mul(_p(u), _p(q), _p(t), _p(qo), _p(to))
     return qo, to
+
+
+def ba_linear_step(prob, cq, ct, X, active, robust, lam):
+    """One linear step of the oracle's solver at an explicit state (cq[nc,4] xyzw, ct[nc,3], X[np,3]) on the
+    edges with active != 0 (robust != 0: Huber) at damping lam.  Returns dict(S[N,N], bs[N], xp[N],
+    xl[npts,3] (active points in point order), err[ne,3] (active edges), nposes, npts, ok)."""
+    a = ba_arrays(prob)
+    nc, np_, ne = len(a["Tcw"]), len(a["Xw"]), len(a["edge_point"])
+    P = BaProblem(nc, _p(a["Tcw"]), _p(a["fixed"]), _p(a["intr"]), np_, _p(a["Xw"]), ne, _p(a["edge_point"]),
+                  _p(a["edge_cam"]), _p(a["obs"]), _p(a["inv_sigma2"]))
+    d = lambda v, n: np.ascontiguousarray(np.asarray(v, np.float64).reshape(n))
+    cq, ct, X = d(cq, 4 * nc), d(ct, 3 * nc), d(X, 3 * np_)
+    act = np.ascontiguousarray(np.asarray(active).reshape(ne) != 0, np.uint8)
+    rob = np.ascontiguousarray(np.asarray(robust).reshape(ne) != 0, np.uint8)
+    N = 6 * nc
+    S, bs, x, err = np.zeros(N * N), np.zeros(N), np.zeros(N + 3 * np_), np.zeros((ne, 3))
+    sizes = np.zeros(3, np.int32)
+    lib().oracle_ba_linear_step(C.byref(P), _p(cq), _p(ct), _p(X), _p(act), _p(rob), float(lam), _p(S), _p(bs),
+                                _p(x), _p(err), _p(sizes))
+    n, m = 6 * int(sizes[0]), int(sizes[1])
+    return dict(S=S[:n * n].reshape(n, n).copy(), bs=bs[:n].copy(), xp=x[:n].copy(),
+                xl=x[n:n + 3 * m].reshape(m, 3).copy(), err=err, nposes=int(sizes[0]), npts=m, ok=bool(sizes[2]))
 
 
 def local_ba(prob, stop=False):

@@ -136,6 +136,13 @@ int oracle_local_ba(const oracle_ba_problem* p, oracle_ba_result* r, const volat
  * pose (rows of 6, pose update exp(u) * T, u = (omega, upsilon)). */
 void oracle_ba_edge_probe(const double q[4], const double t[3], const double X[3], const double intr[5], int stereo,
                           const double obs[3], double err[3], double A[9], double B[18]);
+/* One linear step at an explicit state: errors, buildSystem, setLambda + Schur + solve + back
+ * substitution on the edges with active != 0 (robust != 0: Huber).  S (N x N, N = 6 * free cameras
+ * with an active edge), bs, x (poses, then 3 per active point), err (3 per edge), sizes = {nposes,
+ * npts, solve ok}. */
+int oracle_ba_linear_step(const oracle_ba_problem* p, const double* cq, const double* ct, const double* X,
+                          const uint8_t* active, const uint8_t* robust, double lambda, double* S, double* bs,
+                          double* x, double* err, int* sizes);
 /* exp(u) * T (SE3Quat::exp, operator*, normalizeRotation). */
 void oracle_se3_exp_mul(const double u[6], const double q[4], const double t[3], double q_out[4], double t_out[3]);
 

@@ -315,8 +315,20 @@ SIGNATURES = {
     "orbx_debug_ldlt": ([P, P, C.c_int, P, C.c_int, C.POINTER(C.c_float)], C.c_int),
     "orbx_debug_ldlt_ex": ([P, P, C.c_int, P, C.c_int, C.POINTER(C.c_float), C.c_int, P], C.c_int),
     "orbx_debug_ba_options": ([P, C.POINTER(BaDebugOptions)], C.c_int),
+    "orbx_debug_ba_capture_select": ([P, C.c_int, C.c_int, C.c_int], C.c_int),
+    "orbx_debug_ba_capture_read": ([P, C.c_int, P, C.c_size_t], C.c_longlong),
     "orbx_debug_hbm_copy": ([P, P, C.c_size_t, C.c_int, C.POINTER(C.c_float)], C.c_int),
 }
+
+# include/orbx_debug.h ORBX_BA_CAP_*: item -> (id, dtype, trailing shape); HEADER (id 0) is read apart
+BA_CAPTURE_ITEMS = {
+    "lambda_chi": (1, np.float64, ()), "cq": (2, np.float64, (4,)), "ct": (3, np.float64, (3,)),
+    "X": (4, np.float64, (3,)), "eerr": (5, np.float64, (3,)), "S": (6, np.float64, ()), "bs": (7, np.float64, ()),
+    "xp": (8, np.float64, ()), "cbak": (9, np.float64, (7,)), "Xbak": (10, np.float64, (3,)),
+    "xl": (11, np.float64, (3,)), "act": (12, np.int32, ()), "pose_cam": (13, np.int32, ()),
+    "pt_id": (14, np.int32, ()), "erobust": (15, np.int32, ()),
+}
+BA_CAPTURE_HEADER = ("fired", "phase", "it", "q", "ok", "trial", "nc", "np", "ne", "na", "npa", "nposes")
 
 _lib = None
 

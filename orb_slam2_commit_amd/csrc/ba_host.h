@@ -119,8 +119,13 @@ inline size_t arena_bytes(std::initializer_list<size_t> sizes) {
   return t + 256;
 }
 
+}  // namespace orbx
+#include "ba_capture.h"  // (uses DBuf and HIP_TRY above)
+namespace orbx {
+
 struct LocalBA {
   BaDev D{};
+  BaCapture cap;  // test-only capture of one trial (orbx_debug_ba_capture_select); off by default
   Ctx c;  // device buffers, kept across calls (grow only)
   Arena prob_arena, struct_arena;
   // result write-back: k_ba_outliers / k_ba_export write the flags, poses and points straight
@@ -518,6 +523,11 @@ struct LocalBA {
     int it = 0;
     if (!(stop())) {  // the loop head's first poll (i = 0)
       const bool fused = Dg.nbf > 0;
+      // test-only capture of one trial: its two copy kernels are launched only while selected
+      const bool capt = cap.on();
+      BaCapDev Cd{};
+      if (capt) BA_CHECK(cap.begin(D, &Cd, st));
+      const int gcap = capt ? BaCapture::grid(D) : 0;
       if (fused) BA_CHECK(set_smem_attr((const void*)k_ba_lin_schur, kFuseSmem));
       // entry: errors, linearisation (point side through k_ba_lin_schur's entry mode when the
       // edges are point-grouped), pose sums, then cam_fin + lambda init + LM init in one launch
@@ -546,9 +556,13 @@ struct LocalBA {
         if (Dg.nposes > 0) {
           hipLaunchKernelGGL(k_ba_pairs, dim3(Dg.nblk + Dg.nposes, Dg.gsplit), dim3(kPB), 0, st, Dg);
           hipLaunchKernelGGL(k_ba_schur_fin, dim3(Dg.nblk + Dg.nposes), dim3(64), 0, st, Dg, 0.0);
+          if (capt) hipLaunchKernelGGL(k_ba_capture_pre, dim3(gcap), dim3(LBS), 0, st, Dg, Cd);
           ldlt.launch(Dg, st);
+        } else if (capt) {
+          hipLaunchKernelGGL(k_ba_capture_pre, dim3(gcap), dim3(LBS), 0, st, Dg, Cd);
         }
         hipLaunchKernelGGL(k_ba_update, dim3(Dg.nbu), dim3(LBS), 0, st, Dg, 0.0);
+        if (capt) hipLaunchKernelGGL(k_ba_capture_post, dim3(gcap), dim3(LBS), 0, st, Dg, Cd);
         if (split_ctl) {
           hipLaunchKernelGGL(k_ba_errors, dim3(ge), dim3(LBS), 0, st, Dg, 1, 1);
           hipLaunchKernelGGL(k_ba_lm_control, dim3(1), dim3(64), 0, st, Dg, dstop);
@@ -582,6 +596,7 @@ struct LocalBA {
         }
         budget = std::max(1, iterations - lm_host->it);
       }
+      if (capt) BA_CHECK(cap.end());  // (the readback's event has passed: the stream is idle)
       it = lm_host->it;
       trials += lm_host->trials;
       hook_stopped |= lm_host->stopped && D.raise_after >= 0;

@@ -12,6 +12,7 @@
 //   ba_ldlt.h       k_ba_ldlt / k_ba_ldlt_col / k_ba_ldlt_pan and LdltPlan
 //   ba_lm.h         k_ba_update, k_ba_restore, k_ba_lm_*, k_ba_errors_ctl
 //   ba_structure.h  k_ba_struct_*, k_ba_prep, k_ba_outliers, k_ba_export
+//   ba_capture.h    k_ba_capture_pre / _post: the test-only capture of one trial (orbx_debug.h)
 //   ba_host.h       struct LocalBA: buffers, phase structure, optimize_dev (one optimize() call)
 //   this file       intake, write-back, run_local_ba, the batched driver, the C ABI, the LDLT probe
 //
@@ -323,6 +324,7 @@ orbx_status run_local_ba(LocalBA& L, const orbx_ba_problem* pb, orbx_ba_result* 
     tm[1] = tb1;
     if (s != ORBX_OK) return s;
     Dspec = D;
+    L.cap.cur_phase = 0;
     s = optimize(5, &res->iterations[0], &res->chi2[0], spec2 ? std::function<hipError_t()>(spec) : nullptr);
     if (s != ORBX_OK) return s;
     // did the speculative phase-2 launches run (spec_skip's condition: phase 1 ended done, nothing to
@@ -348,6 +350,7 @@ orbx_status run_local_ba(LocalBA& L, const orbx_ba_problem* pb, orbx_ba_result* 
       tm[3] = std::chrono::steady_clock::now();
       host_build_ms += std::chrono::duration<double, std::milli>(tm[3] - tb2).count();
       if (s != ORBX_OK) return s;
+      L.cap.cur_phase = 1;
       s = optimize(10, &res->iterations[1], &res->chi2[1]);
       if (s != ORBX_OK) return s;
       tm[4] = std::chrono::steady_clock::now();
@@ -716,10 +719,48 @@ orbx_status orbx_ba_run_many(orbx_ba* h, int n, const orbx_ba_problem* problems,
   std::vector<orbx::LocalBA*> Ls(n);
   Ls[0] = &h->L;
   for (int i = 1; i < n; i++) Ls[i] = h->more[i - 1].get();
+  h->L.cap.sel_phase = -1;  // (the batched driver does not capture)
   orbx::BaOptScope scope(&h->opts);
   orbx::StopFlag sf;
   sf.i = stop_flag;
   return orbx::run_local_ba_many(Ls.data(), n, h->batch, problems, results, sf, h->st);
+}
+
+int orbx_debug_ba_capture_select(orbx_ba* h, int phase, int it, int q) {
+  if (!h || phase > 1 || (phase >= 0 && (it < -1 || q < 0))) return ORBX_ERR_ARG;
+  orbx::BaCapture& c = h->L.cap;
+  c.sel_phase = phase < 0 ? -1 : phase;
+  c.sel_it = it;
+  c.sel_q = q;
+  c.have = false;
+  return ORBX_OK;
+}
+
+long long orbx_debug_ba_capture_read(orbx_ba* h, int what, void* dst, size_t cap) {
+  if (!h || (cap > 0 && !dst)) return ORBX_ERR_ARG;
+  const orbx::BaCapture& c = h->L.cap;
+  const bool fired = c.have && c.hi[0] != 0;
+  const void* src = nullptr;
+  size_t bytes = 0;
+  int hdr[12];
+  if (what == ORBX_BA_CAP_HEADER) {
+    const int* d = c.dims;
+    const int v[12] = {fired ? 1 : 0,        fired ? d[0] : -1,    fired ? c.hi[1] : -1, fired ? c.hi[2] : -1,
+                       fired ? c.hi[3] : 0,  fired ? c.hi[5] : -1, fired ? d[1] : 0,     fired ? d[2] : 0,
+                       fired ? d[3] : 0,     fired ? d[4] : 0,     fired ? d[5] : 0,     fired ? d[6] : 0};
+    std::memcpy(hdr, v, sizeof v);
+    src = hdr;
+    bytes = sizeof hdr;
+  } else {
+    bool is_int;
+    size_t off, cnt;
+    if (!orbx::BaCapture::item(what, c.dims, &is_int, &off, &cnt)) return ORBX_ERR_ARG;
+    if (!fired) return ORBX_ERR_STATE;
+    src = is_int ? (const void*)(c.hi.data() + off) : (const void*)(c.hd.data() + off);
+    bytes = cnt * (is_int ? sizeof(int) : sizeof(double));
+  }
+  if (dst && bytes) std::memcpy(dst, src, std::min(cap, bytes));
+  return (long long)bytes;
 }
 
 int orbx_debug_ba_options(orbx_ba* h, const orbx_ba_debug_options* o) {
@@ -757,7 +798,9 @@ orbx_status orbx_ba_run(orbx_ba* h, const orbx_ba_problem* p, orbx_ba_result* r,
   orbx::BaOptScope scope(&h->opts);
   orbx::StopFlag f;
   f.i = stop_flag;
-  return orbx::run_local_ba(h->L, p, r, f, h->st);
+  const orbx_status s = orbx::run_local_ba(h->L, p, r, f, h->st);
+  h->L.cap.sel_phase = -1;  // a capture selection holds for one run
+  return s;
 }
 
 orbx_status orbx_ba_run_bool(orbx_ba* h, const orbx_ba_problem* p, orbx_ba_result* r, const volatile bool* stop_flag) {
@@ -766,7 +809,9 @@ orbx_status orbx_ba_run_bool(orbx_ba* h, const orbx_ba_problem* p, orbx_ba_resul
   orbx::BaOptScope scope(&h->opts);
   orbx::StopFlag f;
   f.b = stop_flag;
-  return orbx::run_local_ba(h->L, p, r, f, h->st);
+  const orbx_status s = orbx::run_local_ba(h->L, p, r, f, h->st);
+  h->L.cap.sel_phase = -1;
+  return s;
 }
 
 orbx_status orbx_local_ba(const orbx_ba_problem* p, orbx_ba_result* r, const volatile int* stop_flag, int device) {

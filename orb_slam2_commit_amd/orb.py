@@ -620,6 +620,43 @@ class Optimizer:
         finally:
             self.set_debug_options()
 
+    def capture_select(self, phase, it=-1, q=0):
+        """Record one LM trial of the next LocalBundleAdjustment call (include/orbx_debug.h,
+        orbx_debug_ba_capture_select; tests only): the first trial of `phase` (0 / 1) at iteration
+        `it` of the phase (-1: any) with trial index `q` inside its iteration.  phase < 0 disarms."""
+        check(_lib.lib().orbx_debug_ba_capture_select(self._h, int(phase), int(it), int(q)),
+              "orbx_debug_ba_capture_select")
+
+    def capture_read(self):
+        """The last capture as a dict (orbx_debug_ba_capture_read), or None when none fired: the header
+        fields (_lib.BA_CAPTURE_HEADER), `lambda`, `chi`, and every item of _lib.BA_CAPTURE_ITEMS; the
+        linearised state is composed as cq_lin / ct_lin / X_lin (cbak / Xbak over the current state)."""
+        L = _lib.lib()
+        hdr = np.zeros(len(_lib.BA_CAPTURE_HEADER), np.int32)
+        n = L.orbx_debug_ba_capture_read(self._h, 0, ptr(hdr), hdr.nbytes)
+        if n != hdr.nbytes:
+            raise _lib.OrbxError(int(n), "orbx_debug_ba_capture_read")
+        c = dict(zip(_lib.BA_CAPTURE_HEADER, (int(v) for v in hdr)))
+        if not c["fired"]:
+            return None
+        for name, (what, dt, tail) in _lib.BA_CAPTURE_ITEMS.items():
+            n = L.orbx_debug_ba_capture_read(self._h, what, None, 0)
+            if n < 0:
+                raise _lib.OrbxError(int(n), "orbx_debug_ba_capture_read")
+            a = np.zeros(n // np.dtype(dt).itemsize, dt)
+            if n:
+                L.orbx_debug_ba_capture_read(self._h, what, ptr(a), a.nbytes)
+            c[name] = a.reshape((-1,) + tail)
+        N = 6 * c["nposes"]
+        c["S"] = c["S"].reshape(N, N)
+        c["lambda"], c["chi"] = (float(v) for v in c.pop("lambda_chi"))
+        c["cq_lin"], c["ct_lin"], c["X_lin"] = c["cq"].copy(), c["ct"].copy(), c["X"].copy()
+        if c["ok"]:
+            c["cq_lin"][c["pose_cam"]] = c["cbak"][:, :4]
+            c["ct_lin"][c["pose_cam"]] = c["cbak"][:, 4:]
+            c["X_lin"][c["pt_id"]] = c["Xbak"]
+        return c
+
     def __del__(self):
         try:
             self.close()

@@ -368,14 +368,39 @@ def test_gpu_localba_stop_flag_caller_memory(ba):
     _compare(ba.LocalBundleAdjustment(P, stop=flag), oracle.local_ba(P))
 
 
+def _stop_problem():
+    return synth.localba_problem(seed=8, n_local=30, n_fixed=4, n_points=4000)
+
+
+def test_oracle_stop_raised_after_trials(monkeypatch):
+    """The oracle's mid-run stop hook (ORBX_BA_RAISE_STOP_AFTER = n: terminate() reads raised at the
+    polls that follow trial t >= n of a phase; the call-entry poll is not hooked).  An n beyond the
+    trial count changes nothing; n = 0, 2, 4 end the first phase early and skip the second
+    (bDoMore, src/Optimizer.cc:764), after at most n + 1 iterations."""
+    P = _stop_problem()
+    full = oracle.local_ba(P)
+    monkeypatch.setenv("ORBX_BA_RAISE_STOP_AFTER", str(full["trials"] + 100))
+    r = oracle.local_ba(P)
+    assert r["iterations"] == full["iterations"] and r["trials"] == full["trials"]
+    for k in ("Tcw_d", "Xw_d", "edge_outlier"):
+        np.testing.assert_array_equal(r[k], full[k])
+    for n in (0, 2, 4):
+        monkeypatch.setenv("ORBX_BA_RAISE_STOP_AFTER", str(n))
+        r = oracle.local_ba(P)
+        assert r["iterations"][1] == 0 and 1 <= r["iterations"][0] <= n + 1
+        assert r["trials"] >= n + 1 and sum(r["iterations"]) < sum(full["iterations"])
+        assert np.isfinite(r["Tcw_d"]).all() and np.isfinite(r["Xw_d"]).all()
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("after", [0, 2, 4])  # inside the first phase (optimize(5))
-def test_gpu_localba_stop_raised_after_trials(ba, after):
+def test_gpu_localba_stop_raised_after_trials(ba, after, monkeypatch):
     """Deterministic mid-run stop: the raise_stop_after = n debug option makes the device LM control see a
     raised flag from trial n of the first phase on (as a flag raised by LocalMapping::InterruptBA
     between two trials).  The phase ends at that iteration, the second phase is skipped, and the
-    result is the same bit for bit on every run and through the batched driver."""
-    P = synth.localba_problem(seed=8, n_local=30, n_fixed=4, n_points=4000)
+    result is the same bit for bit on every run and through the batched driver -- and it is the
+    oracle's result under the same rule (ORBX_BA_RAISE_STOP_AFTER: g2o's terminate() polls)."""
+    P = _stop_problem()
     full = ba.LocalBundleAdjustment(P)
     with ba.debug_options(raise_stop_after=after):
         r = ba.LocalBundleAdjustment(P)
@@ -388,6 +413,8 @@ def test_gpu_localba_stop_raised_after_trials(ba, after):
             np.testing.assert_array_equal(np.asarray(r[k]), np.asarray(o[k]))
         assert list(o["iterations"]) == list(r["iterations"]) and o["trials"] == r["trials"]
     assert np.isfinite(r["Tcw_d"]).all() and np.isfinite(r["Xw_d"]).all()
+    monkeypatch.setenv("ORBX_BA_RAISE_STOP_AFTER", str(after))  # the oracle's hook (test infrastructure)
+    _compare(r, oracle.local_ba(P))
 
 
 @pytest.mark.parametrize("trial", [0, 1, 3])

@@ -41,7 +41,10 @@ enum {
                              gx, gy, total >> 3, total & 7, magic x, shift x, magic y, shift y;
                              l / g == (((2l + 1) * magic) >> 32) >> shift for every l < gx*gy*gz */
   ORBX_LP_XTAB = 6,       /* x4 per output column of level a0 >= 1: sx0, sx1, a0, a1 (the resize coefficients) */
-  ORBX_LP_YTAB = 7        /* x4 per output row of level a0 >= 1: sy0, sy1, b0, b1 */
+  ORBX_LP_YTAB = 7,       /* x4 per output row of level a0 >= 1: sy0, sy1, b0, b1 */
+  ORBX_LP_PATH = 8        /* x8 per level >= 1, the resize kernel chosen for it: path (1: k_resize_strip, 0: k_resize),
+                             tile columns, tile rows (its grid), tile width, tile height, LDS row stride,
+                             footprint rows staged, strip rows per thread (0 for k_resize) */
 };
 long long orbx_debug_launch_plan(const orbx_extractor_params* params, int width, int height, int what, int a0,
                                  int a1, int a2, long long* dst, size_t cap);

@@ -133,6 +133,9 @@ struct Plan {
   std::vector<ResizeY> yt;
   std::vector<int2> rzb;  // k_resize footprint bounds: per level its tile columns, then its tile rows
   int rzb_x[kMaxLevelsPlan] = {}, rzb_y[kMaxLevelsPlan] = {};  // where a level's two runs start in rzb
+  // k_resize_strip's bounds follow k_resize's in rzb (from rzb_n on): a strip level's two runs
+  int rzb_n = 0, rsb_x[kMaxLevelsPlan] = {}, rsb_y[kMaxLevelsPlan] = {};
+  bool strip[kMaxLevelsPlan] = {};  // the level takes the fast path (strip_resize_ok)
   LaunchPlan LP{};  // k_resize's by-value descriptors, pointing into the device tables below
   DevBuf<Geometry> dG;
   DevBuf<CellInfo> dcells;
@@ -164,7 +167,40 @@ void build_launch_plan(const Plan& P, const ResizeX* xt, const ResizeY* yt, cons
     D.stride = G.rz_stride;
     D.rows = G.rz_rows;
     D.lc = G.rz_lc;
+    D.strip = P.strip[l];
+    if (P.strip[l]) {
+      D.sbx = rzb + P.rsb_x[l];
+      D.sby = rzb + P.rsb_y[l];
+    }
   }
+}
+
+// Whether level l (tables already in P) can run k_resize_strip.  A lane covers a group of 4 output
+// columns with one 8-byte window of a footprint row, a wave walks its strip's source rows once in
+// order, and a tile's footprint has to fit the kernel's compile-time LDS shape:
+//   - sx1(last) - sx0(first) <= 7 in every aligned group of 4 output columns;
+//   - every output row reads rows sy0, sy0 + 1, and sy0 advances by 1 or 2 per output row;
+//   - every 256-column tile spans <= kRsStride source bytes, every kRsTH-row tile <= kRsRows rows.
+// Every level of a 1.2 pyramid passes; whatever does not keeps k_resize.
+static bool strip_resize_ok(const Plan& P, int l) {
+#ifdef ORBX_RZ_GENERAL  // A/B and probe builds: every level on k_resize
+  return false;
+#endif
+  const LevelGeom& L = P.G.lv[l];
+  const ResizeX* X = P.xt.data() + L.xtab_off;
+  const ResizeY* Y = P.yt.data() + L.ytab_off;
+  for (int c = 0; c < L.w; c += 4)
+    for (int k = c; k < std::min(c + 4, L.w); k++)
+      if (X[k].sx0 < X[c].sx0 || X[k].sx1 < X[k].sx0 || X[k].sx1 - X[c].sx0 > 7) return false;
+  for (int y = 0; y < L.h; y++) {
+    if (Y[y].sy1 != Y[y].sy0 + 1) return false;
+    if (y > 0 && (Y[y].sy0 - Y[y - 1].sy0 < 1 || Y[y].sy0 - Y[y - 1].sy0 > 2)) return false;
+  }
+  for (int ox = 0; ox < L.w; ox += kRsTW)
+    if (X[std::min(ox + kRsTW, L.w) - 1].sx1 - X[ox].sx0 + 1 > kRsStride) return false;
+  for (int oy = 0; oy < L.h; oy += kRsTH)
+    if (Y[std::min(oy + kRsTH, L.h) - 1].sy1 - Y[oy].sy0 + 1 > kRsRows) return false;
+  return true;
 }
 
 // Builds the per-geometry plan.  Level sizes: ComputePyramid
@@ -374,6 +410,19 @@ orbx_status build_plan(const orbx_extractor_params& p, const Tables& t, int W, i
     }
   }
   if (G.rz_rows > kRzMaxRows || (size_t)G.rz_rows * (G.rz_stride + 2 * kRzTW) > 64 * 1024) return ORBX_ERR_SIZE;
+  // path choice per level; the strip tiles' bounds after k_resize's (which stay, whatever the path)
+  P.rzb_n = (int)P.rzb.size();
+  for (int l = 1; l < G.nlevels; l++) {
+    const LevelGeom& L = G.lv[l];
+    P.strip[l] = strip_resize_ok(P, l);
+    if (!P.strip[l]) continue;
+    P.rsb_x[l] = (int)P.rzb.size();
+    for (int ox = 0; ox < L.w; ox += kRsTW)
+      P.rzb.push_back(make_int2(P.xt[L.xtab_off + ox].sx0, P.xt[L.xtab_off + std::min(ox + kRsTW, L.w) - 1].sx1));
+    P.rsb_y[l] = (int)P.rzb.size();
+    for (int oy = 0; oy < L.h; oy += kRsTH)
+      P.rzb.push_back(make_int2(P.yt[L.ytab_off + oy].sy0, P.yt[L.ytab_off + std::min(oy + kRsTH, L.h) - 1].sy1));
+  }
   G.rz_lc = 0;
   while ((1 << G.rz_lc) < G.rz_stride / 16) G.rz_lc++;
   // every footprint row must be loaded: rows per thread = ceil(rz_rows / (256 >> rz_lc)) <= the kernel's 4
@@ -1295,7 +1344,15 @@ extern "C" long long orbx_debug_launch_plan(const orbx_extractor_params* params,
       }
       break;
     case ORBX_LP_BOUNDS:
-      for (const int2& b : P.rzb) out.insert(out.end(), {b.x, b.y});
+      for (int i = 0; i < P.rzb_n; i++) out.insert(out.end(), {P.rzb[i].x, P.rzb[i].y});
+      break;
+    case ORBX_LP_PATH:
+      for (int l = 1; l < G.nlevels; l++) {
+        const bool f = P.strip[l];
+        const int tw = f ? kRsTW : kRzTW, th = f ? kRsTH : kRzTH;
+        out.insert(out.end(), {f ? 1 : 0, (G.lv[l].w + tw - 1) / tw, (G.lv[l].h + th - 1) / th, tw, th,
+                               f ? kRsStride : G.rz_stride, f ? kRsRows : G.rz_rows, f ? kRsR : 0});
+      }
       break;
     case ORBX_LP_GRIDS: {
       if (a0 < 1) return ORBX_ERR_ARG;

@@ -3,6 +3,7 @@
 // image of the batch:
 //
 //   k_resize   x(nlevels-1)  ComputePyramid            src/ORBextractor.cc:1215-1250
+//                            (k_resize_strip per level where the plan allows it, k_resize elsewhere)
 //   k_fast                   per-cell FAST + fallback  src/ORBextractor.cc:843-915
 //   k_octree                 DistributeOctTree         src/ORBextractor.cc:562-815
 //   k_describe               IC_Angle + rBRIEF on the blurred level + scale
@@ -163,9 +164,34 @@ __device__ __forceinline__ void window_to_lds(const uint8_t* base, size_t stride
 //
 // Everything block-uniform comes in the by-value ResizeDesc; the only scalar loads ahead of the
 // footprint loads are the tile's two bound pairs (D.bx, D.by), issued together.
+// Phase probe (build with -DORBX_RZ_PROBE only; tools/rz_probe.py): s_memtime ticks of a block's
+// first wave in both resize kernels -- footprint to LDS (to the barrier), the horizontal pass
+// (k_resize only, to its second barrier), the arithmetic up to the last store's issue, and the
+// stores' drain -- then the level and the kernel (1: k_resize_strip).  One lane per block writes
+// its 8 words with plain vector stores to a host-provided buffer, indexed by the level's first
+// slot (ResizeDesc::probe_base) plus the block's logical index.
+#ifdef ORBX_RZ_PROBE
+__device__ unsigned int* rz_probe_buf;
+__device__ unsigned int rz_probe_cap;  // blocks the buffer holds
+#define RZ_TS(k) const unsigned long long ts##k = __builtin_amdgcn_s_memtime()
+#define RZ_PROBE_WRITE(a, b, c, d, path)                                                                    \
+  do {                                                                                                      \
+    const unsigned slot = (unsigned)D.probe_base + ((unsigned)bi.z * D.rm.gy + (unsigned)bi.y) * D.rm.gx + (unsigned)bi.x; \
+    if (threadIdx.x == 0 && rz_probe_buf && slot < rz_probe_cap) {                                          \
+      unsigned int* o_ = rz_probe_buf + (size_t)slot * 8;                                                   \
+      o_[0] = (unsigned int)(a), o_[1] = (unsigned int)(b), o_[2] = (unsigned int)(c), o_[3] = (unsigned int)(d); \
+      o_[4] = (unsigned int)D.level, o_[5] = (path), o_[6] = 1, o_[7] = 0;                                  \
+    }                                                                                                       \
+  } while (0)
+#else
+#define RZ_TS(k)
+#define RZ_PROBE_WRITE(a, b, c, d, path)
+#endif
+
 __global__ __launch_bounds__(BS) void k_resize(ResizeDesc D, const uint8_t* __restrict__ in, size_t in_pitch,
                                                uint8_t* __restrict__ pyr) {
   extern __shared__ __align__(16) uint8_t rz_smem[];
+  RZ_TS(0);
   const int3 bi = xcd_block3(D.rm);
   const int img = bi.z, tid = threadIdx.x;
   const int2 fx = D.bx[bi.x], fy = D.by[bi.y];
@@ -230,6 +256,7 @@ __global__ __launch_bounds__(BS) void k_resize(ResizeDesc D, const uint8_t* __re
     }
   }
   __syncthreads();
+  RZ_TS(1);
   // 2. horizontal pass: thread = one output column, rows strided by BS / kRzTW
   if (hc < nx) {
     const int s0 = xc.sx0 - cx0, s1 = xc.sx1 - cx0, a0 = xc.a0, a1 = xc.a1;
@@ -240,6 +267,7 @@ __global__ __launch_bounds__(BS) void k_resize(ResizeDesc D, const uint8_t* __re
     }
   }
   __syncthreads();
+  RZ_TS(2);
   // 3. vertical pass: item = (output row, group of 4 columns)
   const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(
       (void*)(pyr + (size_t)img * D.pyr_bytes + D.dst_off), (short)0, D.dw * D.dh, 0x00020000);
@@ -276,6 +304,170 @@ __global__ __launch_bounds__(BS) void k_resize(ResizeDesc D, const uint8_t* __re
       for (int j = 0; j < nx - 4 * g; j++) __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(packed >> (8 * j)), rd, o + j, 0, 0);
     }
   }
+  RZ_TS(3);
+#ifdef ORBX_RZ_PROBE
+  __builtin_amdgcn_s_waitcnt(0);  // the stores have left
+#endif
+  RZ_TS(4);
+  RZ_PROBE_WRITE(ts1 - ts0, ts2 - ts1, ts3 - ts2, ts4 - ts3, 0);
+}
+
+// f(0) && f(1) && ... && f(N - 1) with the index a compile-time constant: an unrolled loop that stops
+// at the first false, whatever N is
+template <class F, int... I>
+__device__ __forceinline__ void unrolled_while(std::integer_sequence<int, I...>, F&& f) {
+  (void)(f(std::integral_constant<int, I>{}) && ...);
+}
+
+// The fast path of a level (chosen at plan time, strip_resize_ok in capi.hip; every level of a 1.2
+// pyramid takes it).  Same arithmetic, one barrier, no row sums through LDS: a block stages the
+// footprint of a 256 x kRsTH output tile as k_resize does, at the compile-time stride kRsStride, and
+// then each wave owns one strip of kRsR output rows: lane = 4 adjacent output columns.  The wave
+// walks down the strip's source rows once, in order (each output row reads rows sy0, sy0 + 1, and
+// sy0 advances by 1 or 2 per output row: the walk is wave-uniform, its row coefficients scalars).
+//   per source row and lane: 3 aligned LDS dwords cover the 8 bytes from the group's first sx0
+//   (sx1(last) - sx0(first) <= 7); two v_alignbyte put them at byte 0, one v_perm per column with a
+//   per-lane selector pairs (S[sx0], S[sx1]) as u16, one v_dot2_u32_u16 against (a0, a1) gives
+//   x = S0*a0 + S1*a1, and x & ~15 is ((x >> 4) << 4), the form the vertical multiply takes.
+//   The previous and the current row's four values stay in registers; the next row's dwords are
+//   read from LDS ahead of the arithmetic on the current one.
+//   per output row: ((b0*h0) >> 16) + ((b1*h1) >> 16) + 2) >> 2 with
+//   v_mul_hi_u32_u24(b << 12, h << 4) = (b*h) >> 16 (b <= 2048, h <= 32640: both factors below
+//   2^24), four pixels packed into one dword store at (scalar row offset, per-lane column).
+__global__ __launch_bounds__(BS) void k_resize_strip(ResizeDesc D, const uint8_t* __restrict__ in, size_t in_pitch,
+                                                     uint8_t* __restrict__ pyr) {
+  // (one row and 16 B more than the footprint: the read-ahead past a strip's last row and the third
+  // dword of a row's last group stay inside the array; what they fetch is never selected)
+  __shared__ __align__(16) uint8_t tin[(kRsRows + 1) * kRsStride + 16];
+  RZ_TS(0);
+  const int3 bi = xcd_block3(D.rm);
+  const int img = bi.z, tid = threadIdx.x;
+  const int2 fx = D.sbx[bi.x], fy = D.sby[bi.y];
+  const int ox0 = bi.x * kRsTW, oy0 = bi.y * kRsTH;
+  const int cx0 = fx.x, span = fx.y - cx0 + 1;
+  const int ry0 = fy.x, nrows = fy.y - ry0 + 1;
+  const uint8_t* const src0 = in + (size_t)img * in_pitch;
+  const uint8_t* const srcl = pyr + (size_t)img * D.pyr_bytes + D.src_off;
+  const uint8_t* src = D.src_off < 0 ? src0 : srcl;
+  const int swh = D.sw * D.sh;
+  // this lane's four columns and this wave's rows: their coefficients load beside the footprint
+  const int strip = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int c0 = ox0 + 4 * (tid & 63);
+  const int oys = oy0 + strip * kRsR;
+  const int ni = min(kRsR, D.dh - oys);  // output rows of this wave (<= 0: none)
+  ResizeX xc[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) xc[k] = D.X[min(c0 + k, D.dw - 1)];
+  ResizeY yv[kRsR];
+#pragma unroll
+  for (int i = 0; i < kRsR; i++) yv[i] = D.Y[min(oys + i, D.dh - 1)];
+  // 1. footprint -> LDS: item = (row, 16-B chunk) over the kRsStride / 16 chunks of a row (a
+  //    compile-time division), all of a thread's chunk loads issued before their stores
+  {
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)src, (short)0, swh, 0x00020000);
+    const int nch = (span + 15) >> 4;
+    constexpr int kCh = kRsStride / 16;
+    constexpr int kLd = (kRsRows * kCh + BS - 1) / BS;
+    uint4 v[kLd];
+#pragma unroll
+    for (int u = 0; u < kLd; u++) {
+      const int q = tid + u * BS;
+      const int r = q / kCh, c = q - r * kCh;
+      const int o = (ry0 + r) * D.sw + cx0 + 16 * c;
+      v[u] = make_uint4(0, 0, 0, 0);
+      if (r < nrows && c < nch) {
+        if (o + 16 <= swh) {
+          const auto t = __builtin_amdgcn_raw_buffer_load_b128(rs, o, 0, 0);
+          v[u] = make_uint4(t[0], t[1], t[2], t[3]);
+        } else {  // last bytes of the level: byte loads, each range-checked (outside -> 0, never used)
+          uint32_t w4[4] = {0, 0, 0, 0};
+#pragma unroll
+          for (int b = 0; b < 16; b++)
+            w4[b >> 2] |= (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rs, o + b, 0, 0) << (8 * (b & 3));
+          v[u] = make_uint4(w4[0], w4[1], w4[2], w4[3]);
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kLd; u++) {
+      const int q = tid + u * BS;
+      const int r = q / kCh, c = q - r * kCh;
+      if (r < nrows && c < nch) *(uint4*)&tin[r * kRsStride + 16 * c] = v[u];
+    }
+  }
+  __syncthreads();
+  RZ_TS(1);
+  if (ni <= 0) return;  // (wave-uniform; no barrier follows)
+  // 2. per-lane constants: the window's LDS position, a byte selector and a coefficient pair per column
+  const int s0 = xc[0].sx0 - cx0;
+  const uint32_t sh0 = (uint32_t)s0 & 3u;
+  uint32_t sel[4];
+  u16x2 aa[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    sel[k] = 0x0C000C00u | (uint32_t)(xc[k].sx0 - xc[0].sx0) | ((uint32_t)(xc[k].sx1 - xc[0].sx0) << 16);
+    aa[k] = u16x2{(unsigned short)xc[k].a0, (unsigned short)xc[k].a1};
+  }
+  auto mulhi24 = [](uint32_t x, uint32_t z) {
+    return (uint32_t)(((uint64_t)(x & 0xFFFFFFu) * (z & 0xFFFFFFu)) >> 32);
+  };
+  const uint8_t* p = tin + (yv[0].sy0 - ry0) * kRsStride + (s0 & ~3);
+  uint32_t w[3], hp[4] = {0, 0, 0, 0}, hc[4];
+  auto fetch = [&]() {  // the row at p -> w, p to the next row
+    const uint32_t* q = (const uint32_t*)p;
+    w[0] = q[0], w[1] = q[1], w[2] = q[2];
+    p += kRsStride;
+  };
+  auto advance = [&]() {  // hp <- hc <- the horizontal pass of the fetched row; the next row's fetch goes out
+    const uint32_t lo = __builtin_amdgcn_alignbyte(w[1], w[0], sh0);
+    const uint32_t hi = __builtin_amdgcn_alignbyte(w[2], w[1], sh0);
+    fetch();
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      hp[k] = hc[k];
+      const uint32_t pr = __builtin_amdgcn_perm(hi, lo, sel[k]);
+      hc[k] = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, pr), aa[k], 0u, false) & ~15u;
+    }
+  };
+  const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(
+      (void*)(pyr + (size_t)img * D.pyr_bytes + D.dst_off), (short)0, D.dw * D.dh, 0x00020000);
+  const int nv = D.dw - c0;  // valid columns of this lane's group (>= 4: all)
+  fetch();
+#pragma unroll
+  for (int k = 0; k < 4; k++) hc[k] = 0;
+  advance();  // hc = row sy0 of the strip's first output row
+  int cur = yv[0].sy0;
+  // (a fold over the row indices, not a loop: every yv[i] stays a named scalar whatever kRsR is)
+  unrolled_while(std::make_integer_sequence<int, kRsR>{}, [&](auto ic) {
+    constexpr int i = decltype(ic)::value;
+    if (i >= ni) return false;
+    advance();
+    cur++;
+    if (cur < yv[i].sy1) {  // sy0 moved by 2
+      advance();
+      cur++;
+    }
+    const uint32_t B0 = (uint32_t)yv[i].b0 << 12, B1 = (uint32_t)yv[i].b1 << 12;
+    uint32_t t[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) t[k] = mulhi24(B0, hp[k]) + mulhi24(B1, hc[k]) + 2;
+    // t <= 1022: two sums per register, both halves >> 2 at once, then the four low bytes
+    const uint32_t t01 = ((t[0] | (t[1] << 16)) >> 2) & 0x00FF00FFu, t23 = ((t[2] | (t[3] << 16)) >> 2) & 0x00FF00FFu;
+    const uint32_t packed = __builtin_amdgcn_perm(t23, t01, 0x06040200u);
+    const int orow = (oys + i) * D.dw;
+    if (nv >= 4) {
+      __builtin_amdgcn_raw_buffer_store_b32(packed, rd, c0, orow, 0);
+    } else {
+      for (int j = 0; j < nv; j++) __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(packed >> (8 * j)), rd, c0 + j, orow, 0);
+    }
+    return true;
+  });
+  RZ_TS(2);
+#ifdef ORBX_RZ_PROBE
+  __builtin_amdgcn_s_waitcnt(0);  // the stores have left
+#endif
+  RZ_TS(3);
+  RZ_PROBE_WRITE(ts1 - ts0, 0, ts2 - ts1, ts3 - ts2, 1);
 }
 
 // ----------------------------------------------------------------- blur
@@ -1662,8 +1854,13 @@ hipError_t launch_extract_stages(const Geometry& Gh, const Geometry* Gd, const C
   dim3 rz_grid[kMaxLevelsPlan], fast_grid[2];
   XcdRemap fast_rm[2], desc_rm;
   for (int l = 1; l < Gh.nlevels; l++) {
-    rz_grid[l] = dim3((Gh.lv[l].w + kRzTW - 1) / kRzTW, (Gh.lv[l].h + kRzTH - 1) / kRzTH, n_img);
+    const int tw = LP.rz[l].strip ? kRsTW : kRzTW, th = LP.rz[l].strip ? kRsTH : kRzTH;
+    rz_grid[l] = dim3((Gh.lv[l].w + tw - 1) / tw, (Gh.lv[l].h + th - 1) / th, n_img);
     rz[l] = LP.rz[l];
+#ifdef ORBX_RZ_PROBE
+    rz[l].level = l;
+    rz[l].probe_base = l == 1 ? 0 : rz[l - 1].probe_base + (int)(rz_grid[l - 1].x * rz_grid[l - 1].y * rz_grid[l - 1].z);
+#endif
     if (!make_xcd_remap(rz_grid[l].x, rz_grid[l].y, rz_grid[l].z, &rz[l].rm)) return hipErrorInvalidValue;
   }
   for (int g = 0; g < Gh.n_fg; g++) {
@@ -1677,8 +1874,11 @@ hipError_t launch_extract_stages(const Geometry& Gh, const Geometry* Gd, const C
     return hipErrorInvalidValue;
   for (int l = 1; l < Gh.nlevels; l++) {
     T->begin(st);
-    hipLaunchKernelGGL(k_resize, rz_grid[l], dim3(BS), (size_t)Gh.rz_rows * (Gh.rz_stride + 2 * kRzTW), st, rz[l], B.in,
-                       B.in_pitch, B.pyr);
+    if (rz[l].strip)
+      hipLaunchKernelGGL(k_resize_strip, rz_grid[l], dim3(BS), 0, st, rz[l], B.in, B.in_pitch, B.pyr);
+    else
+      hipLaunchKernelGGL(k_resize, rz_grid[l], dim3(BS), (size_t)Gh.rz_rows * (Gh.rz_stride + 2 * kRzTW), st, rz[l], B.in,
+                         B.in_pitch, B.pyr);
     T->end(ST_RESIZE, st);
   }
   if (Gh.ncells > 0) {
@@ -1735,6 +1935,13 @@ hipError_t octree_set_smem_limit(size_t bytes) {
 extern "C" int orbx_debug_oct_probe(void* d_buf) {  // device buffer of 8 u32 per (image, level) block, or NULL
   unsigned int* p = (unsigned int*)d_buf;
   return hipMemcpyToSymbol(HIP_SYMBOL(orbx::oct_probe_buf), &p, sizeof(p)) == hipSuccess ? 0 : -3;
+}
+#endif
+#ifdef ORBX_RZ_PROBE
+extern "C" int orbx_debug_rz_probe(void* d_buf, unsigned int blocks) {  // device buffer of 8 u32 per resize block, or NULL
+  unsigned int* p = (unsigned int*)d_buf;
+  if (hipMemcpyToSymbol(HIP_SYMBOL(orbx::rz_probe_cap), &blocks, sizeof(blocks)) != hipSuccess) return -3;
+  return hipMemcpyToSymbol(HIP_SYMBOL(orbx::rz_probe_buf), &p, sizeof(p)) == hipSuccess ? 0 : -3;
 }
 #endif
 #ifdef ORBX_FAST_PROBE

@@ -79,6 +79,17 @@ struct Geometry {
 constexpr int kRzTW = 128, kRzTH = 32;  // k_resize output tile
 constexpr int kRzMaxRows = 64;
 
+// k_resize_strip (the fast path of a level, chosen at plan time: strip_resize_ok in capi.hip): a wave
+// owns one strip of kRsR output rows across the 256-column tile (lane = 4 adjacent columns), a block
+// four strips.  Footprint rows in LDS at a compile-time stride.
+#ifndef ORBX_RS_R
+#define ORBX_RS_R 8
+#endif
+constexpr int kRsR = ORBX_RS_R;
+constexpr int kRsTW = 256, kRsTH = 4 * kRsR;  // output tile
+constexpr int kRsStride = 336;                // LDS row stride: spans up to 256 columns x 1.25 (+ taps), 16-B chunks
+constexpr int kRsRows = kRsTH * 5 / 4 + 3;    // footprint rows staged per tile
+
 // A cell's FAST survivors: the first `kin` in its inline slots at cand_off (the cells' inline slots
 // packed back to back, so the octree's per-cell reads share 128-B lines), the rest (up to `cap`) in
 // its overflow slots at ovf_off.  Both offsets are per image within one cand_total block.
@@ -149,6 +160,12 @@ struct ResizeDesc {
   const int2* bx;          // per tile column: (sx0 of its first, sx1 of its last output column)
   const int2* by;          // per tile row:    (sy0 of its first, sy1 of its last output row)
   int stride, rows, lc;    // Geometry::rz_stride, rz_rows, rz_lc
+  int strip;               // 1: the level runs k_resize_strip, its tiles' bounds in sbx / sby; 0: k_resize
+  const int2* sbx;         // per 256-column strip tile: (sx0 of its first, sx1 of its last output column)
+  const int2* sby;         // per kRsTH-row strip tile:  (sy0 of its first, sy1 of its last output row)
+#ifdef ORBX_RZ_PROBE
+  int probe_base, level;   // the level's first block slot in the probe buffer (filled at launch)
+#endif
 };
 
 struct LaunchPlan {

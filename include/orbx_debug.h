@@ -49,6 +49,27 @@ enum {
 long long orbx_debug_launch_plan(const orbx_extractor_params* params, int width, int height, int what, int a0,
                                  int a1, int a2, long long* dst, size_t cap);
 
+/* The shipped stereo matcher (orbx_stereo_match's launch path, unchanged) on keypoints and
+ * descriptors the caller supplies instead of the extractions' own (tests only: scenes that place a
+ * keypoint on every boundary of Frame::ComputeStereoMatches).  Preconditions as orbx_stereo_match
+ * without the fingerprint check: both handles' last call was orbx_extract, on the same geometry and
+ * device (ORBX_ERR_STATE / ORBX_ERR_ARG otherwise); the matcher reads their device pyramids.  The
+ * supplied arrays go to a scratch block of this call, so the handles' extraction state is untouched
+ * and a later orbx_stereo_match on the true outputs still succeeds.
+ * Outputs (nL each): uRight and depth after the median filter; sad, the per-keypoint SAD the match
+ * kernel left (-1 unless accepted before the filter); *nmatches, the matches the filter kept.
+ * Checked on the host before any device call: ORBX_ERR_CAPACITY for nR > 4096; ORBX_ERR_ARG unless
+ * every keypoint passes orbx_debug_stereo_keypoints_check on the handles' geometry. */
+orbx_status orbx_debug_stereo_keypoints(orbx_extractor* left, orbx_extractor* right, const orbx_keypoint* kpsL,
+                                        const uint8_t* descL, int nL, const orbx_keypoint* kpsR, const uint8_t* descR,
+                                        int nR, float bf, float baseline, float* uRight, float* depth, int32_t* sad,
+                                        int32_t* nmatches);
+/* ORBX_OK when every keypoint has octave in [0, nlevels) and finite x, y in [0, width) x [0, height)
+ * without a sign bit (-0.0f is refused: the matcher sorts on y's bit pattern); ORBX_ERR_ARG
+ * otherwise.  The matcher indexes its level and row tables with these unguarded.  No device is
+ * needed or touched. */
+int orbx_debug_stereo_keypoints_check(const orbx_keypoint* kps, int n, int nlevels, int width, int height);
+
 /* The library's deterministic double atan2 (Sim3Solver's half-angle, src/Sim3Solver.cc:325) evaluated
  * on the host: the same operation sequence as the kernels run (no device is needed or touched). */
 double orbx_debug_atan2_det(double y, double x);

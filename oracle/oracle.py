@@ -122,6 +122,7 @@ def lib():
         L.oracle_hamming_pairs.argtypes = [P, P, C.c_int, P]
         L.oracle_stereo_match.argtypes = [C.POINTER(Params), P, P, C.c_int, P, P, C.c_int, P, P, P,
                                           C.c_float, C.c_float, P, P]
+        L.oracle_stereo_match_sad.argtypes = L.oracle_stereo_match.argtypes + [P]
         L.oracle_search_by_bow_kf_f.argtypes = [C.POINTER(BowSide), C.POINTER(BowSide), C.c_float, C.c_int, P]
         L.oracle_search_by_bow_kf_kf.argtypes = [C.POINTER(BowSide), C.POINTER(BowSide), C.c_float, C.c_int, P]
         L.oracle_three_maxima.argtypes = [P, C.c_int, P, P, P]
@@ -237,7 +238,9 @@ def extract(p, img):
     return Extraction(kps[:n].copy(), desc[:n].copy(), pyr, wh)
 
 
-def stereo_match(p, exL, exR, bf, baseline):
+def stereo_match(p, exL, exR, bf, baseline, with_sad=False):
+    """(uRight, depth); with_sad: (uRight, depth, sad (-1 unless accepted before the median filter),
+    matches kept)."""
     nL, nR = len(exL.keypoints), len(exR.keypoints)
     uR = np.zeros(nL, np.float32)
     depth = np.zeros(nL, np.float32)
@@ -245,6 +248,12 @@ def stereo_match(p, exL, exR, bf, baseline):
     kR = np.ascontiguousarray(exR.keypoints)
     dL = np.ascontiguousarray(exL.descriptors)
     dR = np.ascontiguousarray(exR.descriptors)
+    if with_sad:
+        sad = np.zeros(nL, np.int32)
+        kept = lib().oracle_stereo_match_sad(C.byref(p), _p(kL), _p(dL), nL, _p(kR), _p(dR), nR,
+                                             _p(exL.pyramid_flat), _p(exR.pyramid_flat), _p(exL.level_wh),
+                                             C.c_float(bf), C.c_float(baseline), _p(uR), _p(depth), _p(sad))
+        return uR, depth, sad, int(kept)
     lib().oracle_stereo_match(C.byref(p), _p(kL), _p(dL), nL, _p(kR), _p(dR), nR,
                               _p(exL.pyramid_flat), _p(exR.pyramid_flat), _p(exL.level_wh),
                               C.c_float(bf), C.c_float(baseline), _p(uR), _p(depth))

@@ -777,8 +777,17 @@ int oracle_stereo_match(const oracle_params* p, const oracle_keypoint* kL, const
                         const oracle_keypoint* kR, const uint8_t* dR, int nR, const uint8_t* pyrL,
                         const uint8_t* pyrR, const int* level_wh, float bf, float b, float* uRight,
                         float* depth) {
+  return oracle_stereo_match_sad(p, kL, dL, nL, kR, dR, nR, pyrL, pyrR, level_wh, bf, b, uRight, depth, nullptr);
+}
+
+int oracle_stereo_match_sad(const oracle_params* p, const oracle_keypoint* kL, const uint8_t* dL, int nL,
+                            const oracle_keypoint* kR, const uint8_t* dR, int nR, const uint8_t* pyrL,
+                            const uint8_t* pyrR, const int* level_wh, float bf, float b, float* uRight,
+                            float* depth, int32_t* sadOut) {
   Tables t = make_tables(*p);
   for (int i = 0; i < nL; i++) uRight[i] = depth[i] = -1.0f;
+  if (sadOut)
+    for (int i = 0; i < nL; i++) sadOut[i] = -1;
   std::vector<size_t> lvl_off(p->nlevels);
   size_t off = 0;
   for (int l = 0; l < p->nlevels; l++) {
@@ -874,6 +883,7 @@ int oracle_stereo_match(const oracle_params* p, const oracle_keypoint* kL, const
       depth[iL] = bf / disparity;
       uRight[iL] = bestuR;
       distIdx.push_back({sadBest, iL});
+      if (sadOut) sadOut[iL] = sadBest;
     }
   }
   if (distIdx.empty()) return 0;  // reference reads v[0] of an empty vector here (UB)

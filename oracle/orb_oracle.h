@@ -73,6 +73,13 @@ int oracle_stereo_match(const oracle_params* p,
                         const oracle_keypoint* kpsR, const uint8_t* descR, int nR,
                         const uint8_t* pyrL, const uint8_t* pyrR, const int* level_wh,
                         float bf, float baseline, float* uRight, float* depth);
+/* The same; sad (optional, nL): the SAD of every match accepted before the median filter, -1 elsewhere.
+ * Both return the number of matches the filter kept. */
+int oracle_stereo_match_sad(const oracle_params* p,
+                            const oracle_keypoint* kpsL, const uint8_t* descL, int nL,
+                            const oracle_keypoint* kpsR, const uint8_t* descR, int nR,
+                            const uint8_t* pyrL, const uint8_t* pyrR, const int* level_wh,
+                            float bf, float baseline, float* uRight, float* depth, int32_t* sad);
 
 /* One side of SearchByBoW: descriptors, keypoint angles, MapPoint validity
  * (NULL = all valid) and its DBoW2::FeatureVector as CSR (ascending node ids). */

@@ -42,6 +42,12 @@ namespace {
 
 inline int round_even(float v) { return (int)std::nearbyintf(v); }
 
+// Bytes past the last pixel of the handle's input buffer.  k_stereo_match stages its SAD rows with
+// dword loads from the 4-aligned address at or below a row's first byte, so it reads up to 3 bytes past
+// a row's last needed one; at the bottom-right patch of level 0 (which is the input buffer) that is
+// up to 3 bytes past the image.  The pyramid buffer carries 256 bytes of slack for the same reason.
+constexpr size_t kInSlack = 4;
+
 template <class T>
 struct DevBuf {
   T* p = nullptr;
@@ -820,7 +826,7 @@ orbx_status orbx_extract(orbx_extractor* h, const uint8_t* img, int width, int h
   h->out_kps = 256;
   h->out_desc = h->out_kps + (((size_t)kcap * sizeof(orbx_keypoint) + 255) & ~(size_t)255);
   h->out_bytes = h->out_desc + (size_t)kcap * 32;
-  chk(h->in.ensure(npx));
+  chk(h->in.ensure(npx + kInSlack));
   chk(h->out.ensure(h->out_bytes));
   chk(h->ensure_stage(std::max(npx, h->out_bytes)));
   if (e != hipSuccess) return ORBX_ERR_HIP;
@@ -1027,7 +1033,7 @@ orbx_status orbx_frame_stereo(orbx_extractor* h, const uint8_t* imL, size_t stri
                o_ur = o_desc + (size_t)2 * kc * 32, o_dep = o_ur + (size_t)kc * 4, o_end = o_dep + (size_t)kc * 4;
   hipError_t e = hipSuccess;
   auto chk = [&](hipError_t x) { if (x != hipSuccess) e = x; };
-  chk(h->in.ensure(2 * npx));
+  chk(h->in.ensure(2 * npx + kInSlack));
   chk(h->out.ensure(o_end));
   chk(h->ensure_stage(std::max(2 * npx, o_end)));
   if (e != hipSuccess) return ORBX_ERR_HIP;
@@ -1306,6 +1312,84 @@ extern "C" long long orbx_debug_copy(orbx_extractor* h, int what, int image, int
     if (hipMemcpy(dst, src, std::min(bytes, cap), hipMemcpyDeviceToHost) != hipSuccess) return ORBX_ERR_HIP;
   }
   return (long long)bytes;
+}
+
+// ------------------------------------------------------------ stereo matcher on supplied keypoints
+// orbx_debug_stereo_keypoints_check: what k_stereo_prep / k_stereo_match index unguarded with a
+// keypoint -- G->lv[octave], inv_scale[octave], the row table at (int)y -- and what their (octave, y)
+// sort key assumes (y's float bits ordered as its value: no sign bit).  Host only.
+extern "C" int orbx_debug_stereo_keypoints_check(const orbx_keypoint* kps, int n, int nlevels, int width,
+                                                 int height) {
+  if (n < 0 || (n > 0 && !kps) || nlevels < 1 || nlevels > kMaxLevelsPlan || width <= 0 || height <= 0)
+    return ORBX_ERR_ARG;
+  for (int i = 0; i < n; i++) {
+    const orbx_keypoint& k = kps[i];
+    if (k.octave < 0 || k.octave >= nlevels) return ORBX_ERR_ARG;
+    if (!std::isfinite(k.x) || !std::isfinite(k.y) || std::signbit(k.x) || std::signbit(k.y)) return ORBX_ERR_ARG;
+    if (!(k.x < (float)width) || !(k.y < (float)height)) return ORBX_ERR_ARG;
+  }
+  return ORBX_OK;
+}
+
+extern "C" orbx_status orbx_debug_stereo_keypoints(orbx_extractor* left, orbx_extractor* right,
+                                                   const orbx_keypoint* kpsL, const uint8_t* descL, int nL,
+                                                   const orbx_keypoint* kpsR, const uint8_t* descR, int nR, float bf,
+                                                   float baseline, float* uRight, float* depth, int32_t* sad,
+                                                   int32_t* nmatches) {
+  if (!uRight || !depth || !sad || !nmatches || nL < 0 || nR < 0) return ORBX_ERR_ARG;
+  if ((nL > 0 && (!kpsL || !descL)) || (nR > 0 && (!kpsR || !descR))) return ORBX_ERR_ARG;
+  if (nR > kMaxStereoKps) return ORBX_ERR_CAPACITY;
+  if (!left || !right) return ORBX_ERR_ARG;
+  if (!left->last_plan || !right->last_plan || !left->last_host || !right->last_host) return ORBX_ERR_STATE;
+  const Geometry& G = left->last_plan->G;
+  if (G.width != right->last_plan->G.width || G.height != right->last_plan->G.height ||
+      G.nlevels != right->last_plan->G.nlevels || left->device != right->device)
+    return ORBX_ERR_ARG;
+  if (orbx_debug_stereo_keypoints_check(kpsL, nL, G.nlevels, G.width, G.height) != ORBX_OK ||
+      orbx_debug_stereo_keypoints_check(kpsR, nR, G.nlevels, G.width, G.height) != ORBX_OK)
+    return ORBX_ERR_ARG;
+  *nmatches = 0;
+  if (nL == 0) return ORBX_OK;
+  orbx_extractor* h = left;
+  if (hipSetDevice(h->device) != hipSuccess) return ORBX_ERR_HIP;
+  // scratch block of this call alone (the handles' output blocks keep their extractions):
+  // counts (L, R) and the match count | keypoints L | R | descriptors L | R | uRight | depth
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t o_kL = 256, o_kR = o_kL + up((size_t)nL * sizeof(orbx_keypoint)),
+               o_dL = o_kR + up((size_t)nR * sizeof(orbx_keypoint)), o_dR = o_dL + up((size_t)nL * 32),
+               o_res = o_dR + up((size_t)nR * 32), o_end = o_res + (size_t)8 * nL;
+  DevBuf<uint8_t> blk;
+  if (blk.ensure(o_end) != hipSuccess) return ORBX_ERR_HIP;
+  hipError_t e = hipSuccess;
+  auto chk = [&](hipError_t x) { if (x != hipSuccess) e = x; };
+  hipStream_t st = h->stream;
+  const int32_t counts[3] = {nL, nR, 0};
+  chk(hipMemcpyAsync(blk.p, counts, sizeof(counts), hipMemcpyHostToDevice, st));
+  chk(hipMemcpyAsync(blk.p + o_kL, kpsL, (size_t)nL * sizeof(orbx_keypoint), hipMemcpyHostToDevice, st));
+  chk(hipMemcpyAsync(blk.p + o_dL, descL, (size_t)nL * 32, hipMemcpyHostToDevice, st));
+  if (nR > 0) {
+    chk(hipMemcpyAsync(blk.p + o_kR, kpsR, (size_t)nR * sizeof(orbx_keypoint), hipMemcpyHostToDevice, st));
+    chk(hipMemcpyAsync(blk.p + o_dR, descR, (size_t)nR * 32, hipMemcpyHostToDevice, st));
+  }
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(st);
+    return ORBX_ERR_HIP;
+  }
+  int32_t* d_counts = (int32_t*)blk.p;
+  float* d_ur = (float*)(blk.p + o_res);
+  // the shipped launch path, as orbx_stereo_match takes it (the pyramids are the handles' own)
+  orbx_status s = run_stereo(left, right, 1, (const orbx_keypoint*)(blk.p + o_kL), blk.p + o_dL, d_counts, 0, 0,
+                             (const orbx_keypoint*)(blk.p + o_kR), blk.p + o_dR, d_counts + 1, 0, 0, 0, 0, 0, 0, nL,
+                             bf, baseline, d_ur, d_ur + nL, nL, d_counts + 2, st);
+  if (s == ORBX_OK) {
+    chk(hipMemcpyAsync(uRight, d_ur, sizeof(float) * nL, hipMemcpyDeviceToHost, st));
+    chk(hipMemcpyAsync(depth, d_ur + nL, sizeof(float) * nL, hipMemcpyDeviceToHost, st));
+    chk(hipMemcpyAsync(sad, h->sad.p, sizeof(int32_t) * nL, hipMemcpyDeviceToHost, st));
+    chk(hipMemcpyAsync(nmatches, d_counts + 2, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  }
+  chk(hipStreamSynchronize(st));  // before blk is freed
+  if (s != ORBX_OK) return s;
+  return hip_status(e);
 }
 
 extern "C" long long orbx_debug_launch_plan(const orbx_extractor_params* params, int width, int height, int what,

@@ -174,6 +174,30 @@ def compute_stereo_matches(extractor_left, extractor_right, kps_left, desc_left,
     return uR, depth
 
 
+def debug_stereo_keypoints(extractor_left, extractor_right, kps_left, desc_left, kps_right, desc_right, bf,
+                           baseline):
+    """The shipped matcher on SUPPLIED keypoints and descriptors (orbx_debug_stereo_keypoints, tests
+    only), over the pyramids of the extractors' last calls.
+
+    Returns (mvuRight float32[N], mvDepth float32[N], sad int32[N] (-1 unless accepted before the median
+    filter), matches kept)."""
+    nL, nR = len(kps_left), len(kps_right)
+    uR = np.full(nL, -1.0, np.float32)
+    depth = np.full(nL, -1.0, np.float32)
+    sad = np.full(nL, -1, np.int32)
+    nm = np.zeros(1, np.int32)
+    kL = np.ascontiguousarray(kps_left, KEYPOINT_DTYPE)
+    kR = np.ascontiguousarray(kps_right, KEYPOINT_DTYPE)
+    dL = np.ascontiguousarray(desc_left if desc_left is not None else np.zeros((0, 32), np.uint8), np.uint8)
+    dR = np.ascontiguousarray(desc_right if desc_right is not None else np.zeros((0, 32), np.uint8), np.uint8)
+    assert dL.shape == (nL, 32) and dR.shape == (nR, 32)
+    check(_lib.lib().orbx_debug_stereo_keypoints(extractor_left._h, extractor_right._h, ptr(kL), ptr(dL), nL,
+                                                 ptr(kR), ptr(dR), nR, C.c_float(bf), C.c_float(baseline), ptr(uR),
+                                                 ptr(depth), ptr(sad), ptr(nm)),
+          "orbx_debug_stereo_keypoints")
+    return uR, depth, sad, int(nm[0])
+
+
 def frame_stereo(extractor, image_left, image_right, bf, baseline):
     """The ORB part of Frame's stereo constructor (src/Frame.cc:62-123: ExtractORB(0/1) + ComputeStereoMatches)
     in one call through `extractor` (both images as one batch of two, one copy back).

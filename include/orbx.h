@@ -600,6 +600,49 @@ orbx_status orbx_sim3_iterate_candidates(orbx_sim3* const* solvers, int n, int n
 orbx_status orbx_sim3_iterate_many(orbx_sim3* const* solvers, int n, int n_iterations, orbx_rand_state* const* rngs,
                                    orbx_sim3_result* results, uint8_t* const* inliers);
 
+/* Initializer (src/Initializer.cc, include/Initializer.h:36-45): the monocular two-view bootstrap,
+ * the consumer of ORBmatcher::SearchForInitialization (src/Tracking.cc:683-730). */
+typedef struct orbx_initializer orbx_initializer;
+typedef struct {
+  int ok;            /* Initialize's return value */
+  int degenerate;    /* SH = SF = 0: the reference multiplies an empty cv::Mat; returns false here */
+  float SH, SF;      /* FindHomography's / FindFundamental's best score (:186-224, :244-292) */
+  float H21[9];      /* the winning models, row-major (zeros when no hypothesis scored above 0) */
+  float F21[9];
+  int it_h, it_f;    /* the iterations that won, -1: none */
+  int model;         /* 0: ReconstructH (RH > 0.40), 1: ReconstructF, -1: neither (degenerate) */
+  int n_hyp;         /* motion hypotheses checked: 4 (F), 8 (H), 0 (degenerate, or ReconstructH's d1/d2 exit) */
+  int n_good[8];     /* CheckRT's return value per hypothesis, in the reference's order */
+  float parallax[8]; /* ... and its parallax */
+  int best;          /* the hypothesis copied out, -1 on false */
+  int n_matches;     /* mvMatches12.size() */
+  int n_inliers;     /* N of Reconstruct*: inliers of the chosen model */
+  uint8_t* inliers_h; /* in: NULL or n_matches bytes that receive vbMatchesInliersH / F of the winning */
+  uint8_t* inliers_f; /*     iterations (all 0 when none won; FindFundamental's :232 leaves F's mask empty then) */
+} orbx_initializer_result;
+/* Initializer::Initializer(ReferenceFrame, sigma, iterations) -- src/Initializer.cc:40-53.  keys1_xy:
+ * mvKeysUn of the reference frame, n1 x 2 floats; K row-major 3x3.  n1 >= 8, iterations >= 1. */
+orbx_status orbx_initializer_create(const float* keys1_xy, int n1, const float K[9], float sigma, int iterations,
+                                    int device, orbx_initializer** out);
+orbx_status orbx_initializer_destroy(orbx_initializer* h);
+/* Initializer::Initialize(CurrentFrame, vMatches12, R21, t21, vP3D, vbTriangulated) --
+ * src/Initializer.cc:58-167 with FindHomography / FindFundamental (:170-294), ReconstructF / H
+ * (:648-983), CheckRT / Triangulate (:1018-1303), DecomposeE (:1317-1345).  keys2_xy: mvKeysUn of the
+ * current frame (n2 x 2); matches12[n1]: index into keys2 or < 0.  rand_vals: the next rand() outputs
+ * of the caller's stream (the reference's DUtils::Random::SeedRandOnce(0), :106, is the caller's),
+ * at least 8 * iterations of them (ORBX_ERR_CAPACITY otherwise); *used = 8 * iterations.  Fewer than
+ * 8 matches, or a match index >= n2: ORBX_ERR_ARG (the reference underflows size() - 1).  When
+ * result->ok: R21 (row-major 3x3), t21, p3d (3 * n1, zero where CheckRT wrote nothing) and
+ * triangulated (n1) are written; otherwise they are left untouched. */
+orbx_status orbx_initializer_initialize(orbx_initializer* h, const float* keys2_xy, int n2, const int32_t* matches12,
+                                        const int32_t* rand_vals, int n_rand, int* used, float R21[9], float t21[3],
+                                        float* p3d, uint8_t* triangulated, orbx_initializer_result* result);
+/* The same drawing from *rng, which advances by exactly 8 * iterations. */
+orbx_status orbx_initializer_initialize_stream(orbx_initializer* h, const float* keys2_xy, int n2,
+                                               const int32_t* matches12, orbx_rand_state* rng, float R21[9],
+                                               float t21[3], float* p3d, uint8_t* triangulated,
+                                               orbx_initializer_result* result);
+
 /* ORBmatcher::SearchByProjection -- the three overloads run on every tracked
  * frame -- with Frame::AssignFeaturesToGrid / GetFeaturesInArea
  * (src/Frame.cc:254-271, 388-453) and, for the local map, Frame::isInFrustum

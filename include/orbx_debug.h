@@ -160,6 +160,15 @@ long long orbx_debug_ba_capture_read(orbx_ba* h, int what, void* dst, size_t cap
  * *ms = mean time per copy (2 * bytes of HBM traffic each). */
 int orbx_debug_hbm_copy(void* dst, const void* src, size_t bytes, int reps, float* ms);
 
+/* orbx_initializer_create + orbx_initializer_initialize with the kernels' own routines compiled for
+ * the host and run there stage by stage (no device is touched): the CPU half of the parity tests,
+ * which pins the arithmetic against the literal restatement before anything runs on a GPU. */
+int orbx_debug_initializer_host(const float* keys1_xy, int n1, const float K[9], float sigma, int iterations,
+                                const float* keys2_xy, int n2, const int32_t* matches12, const int32_t* rand_vals,
+                                int n_rand, int* used, float R21[9], float t21[3], float* p3d,
+                                uint8_t* triangulated, orbx_initializer_result* result);
+float orbx_debug_acosf_det(float x);
+
 #ifdef __cplusplus
 }
 #endif

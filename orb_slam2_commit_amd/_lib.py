@@ -195,6 +195,14 @@ class Sim3Result(C.Structure):
                 ("T12", C.c_float * 16)]
 
 
+class InitializerResult(C.Structure):  # orbx_initializer_result (Initializer::Initialize)
+    _fields_ = [("ok", C.c_int), ("degenerate", C.c_int), ("SH", C.c_float), ("SF", C.c_float),
+                ("H21", C.c_float * 9), ("F21", C.c_float * 9), ("it_h", C.c_int), ("it_f", C.c_int),
+                ("model", C.c_int), ("n_hyp", C.c_int), ("n_good", C.c_int * 8), ("parallax", C.c_float * 8),
+                ("best", C.c_int), ("n_matches", C.c_int), ("n_inliers", C.c_int), ("inliers_h", C.c_void_p),
+                ("inliers_f", C.c_void_p)]
+
+
 # Every entry point of include/orbx.h with its ctypes signature.
 P = C.c_void_p
 SIGNATURES = {
@@ -285,6 +293,12 @@ SIGNATURES = {
     "orbx_sim3_iterate_candidates": ([P, C.c_int, C.c_int, C.POINTER(RandState), P, P, C.POINTER(C.c_int)],
                                      C.c_int),
     "orbx_sim3_iterate_many": ([P, C.c_int, C.c_int, P, P, P], C.c_int),
+    "orbx_initializer_create": ([P, C.c_int, P, C.c_float, C.c_int, C.c_int, C.POINTER(C.c_void_p)], C.c_int),
+    "orbx_initializer_destroy": ([P], C.c_int),
+    "orbx_initializer_initialize": ([P, P, C.c_int, P, P, C.c_int, C.POINTER(C.c_int), P, P, P, P,
+                                     C.POINTER(InitializerResult)], C.c_int),
+    "orbx_initializer_initialize_stream": ([P, P, C.c_int, P, C.POINTER(RandState), P, P, P, P,
+                                            C.POINTER(InitializerResult)], C.c_int),
     "orbx_rand_seed":([C.POINTER(RandState), C.c_uint32], None),
     "orbx_rand_next": ([C.POINTER(RandState)], C.c_int32),
     "orbx_ba_create": ([C.c_int, C.POINTER(C.c_void_p)], C.c_int),
@@ -313,6 +327,9 @@ SIGNATURES = {
     "orbx_debug_stereo_keypoints_check": ([P, C.c_int, C.c_int, C.c_int, C.c_int], C.c_int),
     "orbx_debug_atan2_det": ([C.c_double, C.c_double], C.c_double),
     "orbx_debug_exp": ([P, C.c_int, P, C.c_int], C.c_int),
+    "orbx_debug_initializer_host": ([P, C.c_int, P, C.c_float, C.c_int, P, C.c_int, P, P, C.c_int,
+                                     C.POINTER(C.c_int), P, P, P, P, C.POINTER(InitializerResult)], C.c_int),
+    "orbx_debug_acosf_det": ([C.c_float], C.c_float),
     "orbx_debug_sim3_exp": ([P, P, C.c_int, P, C.c_int], C.c_int),
     "orbx_debug_ldlt": ([P, P, C.c_int, P, C.c_int, C.POINTER(C.c_float)], C.c_int),
     "orbx_debug_ldlt_ex": ([P, P, C.c_int, P, C.c_int, C.POINTER(C.c_float), C.c_int, P], C.c_int),

@@ -270,6 +270,16 @@ __host__ __device__ inline double atan2_det(double y, double x) {
   return ny ? -a : a;
 }
 
+// Float acos (Initializer::CheckRT's acos(float)) from basic IEEE operations only: the double
+// acos x = atan2(sqrt((1 - x)(1 + x)), x) through atan2_det, rounded once to float; the same sequence
+// on the host, the device and in the tests' Python twin.  1 - x and 1 + x are exact in double for
+// every float |x| >= 2^-29; |x| > 1 gives NaN (the square root of a negative), -0 counts as +0.
+__host__ __device__ inline float acosf_det(float x) {
+  if (x == 0.f) x = 0.f;
+  const double xd = (double)x;
+  return (float)atan2_det(__builtin_sqrt((1.0 - xd) * (1.0 + xd)), xd);
+}
+
 // Hamming distance of two 256-bit descriptors held as 4 x u64.
 __device__ __forceinline__ int hamming256(const uint64_t a[4], const uint64_t b[4]) {
   return __popcll(a[0] ^ b[0]) + __popcll(a[1] ^ b[1]) + __popcll(a[2] ^ b[2]) + __popcll(a[3] ^ b[3]);

@@ -1153,6 +1153,93 @@ class Sim3Solver:
         return self._estimate()[2]
 
 
+class Initializer:
+    """Initializer (include/Initializer.h:36-45, src/Initializer.cc) over orbx_initializer_*.
+
+    Initializer(keys_un, K, sigma=1.0, iterations=200): keys_un is mvKeysUn of the reference frame as
+    [n1, 2] (x, y), K the 3x3 calibration.  Tracking creates it as Initializer(mCurrentFrame, 1.0, 200)
+    (src/Tracking.cc:683).  The object is reused for every later frame, as the reference's is."""
+
+    def __init__(self, keys_un, K, sigma=1.0, iterations=200, device=0):
+        self.mvKeys1 = np.ascontiguousarray(keys_un, np.float32).reshape(-1, 2)
+        self.mK = np.ascontiguousarray(K, np.float32).reshape(3, 3)
+        self.mSigma = float(sigma)
+        self.mMaxIterations = int(iterations)
+        self.device = int(device)
+        self.result = None
+        h = C.c_void_p()
+        check(_lib.lib().orbx_initializer_create(ptr(self.mvKeys1), len(self.mvKeys1), ptr(self.mK), self.mSigma,
+                                                 self.mMaxIterations, self.device, C.byref(h)),
+              "orbx_initializer_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.lib().orbx_initializer_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _buffers(self, keys_un2, vMatches12):
+        k2 = np.ascontiguousarray(keys_un2, np.float32).reshape(-1, 2)
+        vm = np.ascontiguousarray(vMatches12, np.int32).reshape(-1)
+        if len(vm) != len(self.mvKeys1):
+            raise ValueError("Initializer: vMatches12 must have one entry per reference keypoint")
+        n1, N = len(self.mvKeys1), int((vm >= 0).sum())
+        res = _lib.InitializerResult()
+        mh, mf = np.zeros(max(N, 1), np.uint8), np.zeros(max(N, 1), np.uint8)
+        res.inliers_h, res.inliers_f = ptr(mh), ptr(mf)
+        out = (np.zeros(9, np.float32), np.zeros(3, np.float32), np.zeros(3 * n1, np.float32), np.zeros(n1, np.uint8))
+        return k2, vm, res, mh, mf, out
+
+    def _output(self, res, mh, mf, out):
+        N = res.n_matches
+        self.result = {"ok": bool(res.ok), "degenerate": bool(res.degenerate), "SH": np.float32(res.SH),
+                       "SF": np.float32(res.SF), "H21": np.array(res.H21, np.float32).reshape(3, 3),
+                       "F21": np.array(res.F21, np.float32).reshape(3, 3), "itH": res.it_h, "itF": res.it_f,
+                       "model": res.model, "n_hyp": res.n_hyp, "nGood": np.array(res.n_good, np.int32),
+                       "parallax": np.array(res.parallax, np.float32), "best": res.best, "N": N,
+                       "n_inliers": res.n_inliers, "maskH": mh[:N].astype(bool), "maskF": mf[:N].astype(bool)}
+        if not res.ok:
+            return False, None, None, None, None
+        R, t, p, tri = out
+        return True, R.reshape(3, 3), t, p.reshape(-1, 3), tri.astype(bool)
+
+    def Initialize(self, keys_un2, vMatches12, rng):
+        """Initialize(CurrentFrame, vMatches12, R21, t21, vP3D, vbTriangulated), src/Initializer.cc:58-167.
+        keys_un2: mvKeysUn of the current frame [n2, 2]; vMatches12[n1]: index into it or -1; rng: the
+        process rand() stream (the reference seeds it with DUtils::Random::SeedRandOnce(0): GlibcRand(0)),
+        advanced by the 8 * iterations values drawn.  Returns (ok, R21 [3,3], t21 [3], vP3D [n1,3],
+        vbTriangulated [n1]); the last four are None when ok is False.  Fewer than 8 matches raise
+        OrbxError (the reference underflows there).  self.result keeps the stage results."""
+        k2, vm, res, mh, mf, out = self._buffers(keys_un2, vMatches12)
+        st = _rand_state(rng)
+        check(_lib.lib().orbx_initializer_initialize_stream(self._h, ptr(k2), len(k2), ptr(vm), C.byref(st),
+                                                            ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(out[3]),
+                                                            C.byref(res)), "orbx_initializer_initialize_stream")
+        _rand_restore(rng, st)
+        return self._output(res, mh, mf, out)
+
+    def initialize_values(self, keys_un2, vMatches12, rand_vals, sentinel=None):
+        """The same from explicit rand() values (orbx_initializer_initialize); returns (used, raw output
+        buffers (R21, t21, p3d, triangulated), *Initialize's tuple).  sentinel: a byte the raw buffers are
+        pre-filled with, to see what a false return leaves untouched."""
+        k2, vm, res, mh, mf, out = self._buffers(keys_un2, vMatches12)
+        if sentinel is not None:
+            for b in out:
+                b.view(np.uint8)[:] = sentinel
+        vals = np.ascontiguousarray(rand_vals, np.int32)
+        used = C.c_int()
+        check(_lib.lib().orbx_initializer_initialize(self._h, ptr(k2), len(k2), ptr(vm), ptr(vals), len(vals),
+                                                     C.byref(used), ptr(out[0]), ptr(out[1]), ptr(out[2]),
+                                                     ptr(out[3]), C.byref(res)), "orbx_initializer_initialize")
+        return (used.value, out) + self._output(res, mh, mf, out)
+
+
 def pnp_iterate_many(solvers, nIterations, rngs):
     """iterate(n) on independent solvers, rngs[i] its own GlibcRand stream; one batched call."""
     n = len(solvers)

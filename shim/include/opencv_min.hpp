@@ -38,6 +38,14 @@ typedef Point_<int> Point2i;
 typedef Point_<float> Point2f;
 typedef Point2i Point;
 
+template <class T>
+struct Point3_ {
+  T x = T(), y = T(), z = T();
+  Point3_() = default;
+  Point3_(T x_, T y_, T z_) : x(x_), y(y_), z(z_) {}
+};
+typedef Point3_<float> Point3f;
+
 // cv::KeyPoint: 28 bytes, field order pt, size, angle, response, octave, class_id
 class KeyPoint {
  public:

@@ -31,6 +31,7 @@
 #include "Objects.h"
 #include "Optimizer.h"
 #include "PnPsolver.h"
+#include "Initializer.h"
 #include "Sim3Solver.h"
 #include "orbx.h"
 #include "orbx_shim.h"
@@ -1461,6 +1462,68 @@ float Sim3Solver::GetEstimatedScale() {
   float R[9], t[3], s;
   check(orbx_sim3_get_estimate(mpGpu, R, t, &s), "orbx_sim3_get_estimate");
   return s;
+}
+
+// ------------------------------------------------------------------ Initializer
+namespace {
+bool g_rand_seeded_once = false;  // DUtils::Random::SeedRandOnce's m_already_seeded (guarded by g_rand_mu)
+}  // namespace
+
+Initializer::Initializer(const Frame& ReferenceFrame, float sigma, int iterations)
+    : mvKeys1(ReferenceFrame.mvKeysUn), mK(ReferenceFrame.mK.clone()), mSigma(sigma), mMaxIterations(iterations) {
+  // src/Initializer.cc:40-53
+}
+
+Initializer::~Initializer() {
+  if (mpGpu) orbx_initializer_destroy(mpGpu);
+}
+
+bool Initializer::Initialize(const Frame& CurrentFrame, const std::vector<int>& vMatches12, cv::Mat& R21, cv::Mat& t21,
+                             std::vector<cv::Point3f>& vP3D, std::vector<bool>& vbTriangulated) {
+  const int n1 = (int)mvKeys1.size(), n2 = (int)CurrentFrame.mvKeysUn.size();
+  if (!mpGpu) {
+    if (mK.rows != 3 || mK.cols != 3 || mK.type() != CV_32F) throw std::runtime_error("Initializer: K must be 3x3 CV_32F");
+    std::vector<float> k1(2 * (size_t)(n1 > 0 ? n1 : 1));
+    for (int i = 0; i < n1; i++) k1[2 * i] = mvKeys1[i].pt.x, k1[2 * i + 1] = mvKeys1[i].pt.y;
+    float K[9];
+    for (int i = 0; i < 9; i++) K[i] = mK.at<float>(i / 3, i % 3);
+    check(orbx_initializer_create(k1.data(), n1, K, mSigma, mMaxIterations, gOrbxDevice, &mpGpu),
+          "orbx_initializer_create");
+  }
+  if ((int)vMatches12.size() != n1) throw std::runtime_error("Initializer: vMatches12 must have one entry per keypoint");
+  std::vector<float> k2(2 * (size_t)(n2 > 0 ? n2 : 1));
+  for (int i = 0; i < n2; i++) k2[2 * i] = CurrentFrame.mvKeysUn[i].pt.x, k2[2 * i + 1] = CurrentFrame.mvKeysUn[i].pt.y;
+  std::vector<int32_t> m(vMatches12.begin(), vMatches12.end());
+  std::vector<float> p3d(3 * (size_t)n1);
+  std::vector<uint8_t> tri((size_t)n1);
+  float R[9], t[3];
+  mResult = orbx_initializer_result{};
+  {
+    std::lock_guard<std::mutex> lock(g_rand_mu);
+    if (!g_rand_seeded_once) {  // DUtils::Random::SeedRandOnce(0), src/Initializer.cc:106
+      orbx_rand_seed(&g_rand, 0);
+      g_rand_seeded_once = true;
+    }
+    check(orbx_initializer_initialize_stream(mpGpu, k2.data(), n2, m.data(), &g_rand, R, t, p3d.data(), tri.data(),
+                                             &mResult),
+          "orbx_initializer_initialize_stream");
+  }
+  if (!mResult.ok) {
+    R21.release();
+    t21.release();
+    return false;
+  }
+  R21.create(3, 3, CV_32F);
+  t21.create(3, 1, CV_32F);
+  for (int i = 0; i < 9; i++) R21.at<float>(i / 3, i % 3) = R[i];
+  for (int i = 0; i < 3; i++) t21.at<float>(i, 0) = t[i];
+  vP3D.resize(n1);
+  vbTriangulated.assign(n1, false);
+  for (int i = 0; i < n1; i++) {
+    vP3D[i] = cv::Point3f(p3d[3 * i], p3d[3 * i + 1], p3d[3 * i + 2]);
+    vbTriangulated[i] = tri[i] != 0;
+  }
+  return true;
 }
 
 // ------------------------------------------------------------------ Optimizer

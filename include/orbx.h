@@ -55,6 +55,8 @@
  *   orbx_optimize_sim3         Optimizer::OptimizeSim3         src/Optimizer.cc:1220-1456, include/Optimizer.h
  *                              (the refinement stage of LoopClosing::ComputeSim3, src/LoopClosing.cc:425-444)
  *   orbx_optimize_sim3_device          batch of the above (one block per problem)
+ *   orbx_optimize_essential_graph[_device]  Optimizer::OptimizeEssentialGraph src/Optimizer.cc:888-1218, include/Optimizer.h
+ *                              (the pose graph of LoopClosing::CorrectLoop, src/LoopClosing.cc:785)
  *   orbx_distinctive_descriptors[_device]  MapPoint::ComputeDistinctiveDescriptors src/MapPoint.cc:249-320
  *   orbx_undistort_keypoints[_device]      Frame::UndistortKeyPoints src/Frame.cc:471-506 (cv::undistortPoints)
  *   orbx_local_ba / orbx_ba_*   Optimizer::LocalBundleAdjustment src/Optimizer.cc:530-885, include/Optimizer.h:61
@@ -911,6 +913,64 @@ orbx_status orbx_optimize_sim3(const orbx_optimize_sim3_problem* p, int device);
 /* Batched, device-resident: problems[] is a HOST array whose pointers are device pointers; one block
  * per problem runs the whole schedule on the GPU. */
 orbx_status orbx_optimize_sim3_device(const orbx_optimize_sim3_problem* problems, int n, void* stream);
+
+/* Optimizer::OptimizeEssentialGraph(Map*, KeyFrame* pLoopKF, KeyFrame* pCurKF, NonCorrectedSim3,
+ * CorrectedSim3, LoopConnections, bFixScale) -- src/Optimizer.cc:888-1218, include/Optimizer.h (called
+ * at src/LoopClosing.cc:785): one VertexSim3Expmap per keyframe (the loop keyframe fixed), EdgeSim3
+ * edges with identity information and g2o's NUMERIC Jacobians (EdgeSim3 has no linearizeOplus),
+ * Levenberg with setUserLambdaInit(1e-16) and optimize(20), the SE3 recovery of every keyframe and the
+ * double-Sim3 correction of every map point.  The caller performs the edge selection (:981-1138) and
+ * passes the edges in the order it adds them; the measurements Sji = Sjw * Swi are formed on the device
+ * from the pose table the edge's kind selects.  The system of 7 (n_vertices - 1) unknowns is held as
+ * a block envelope (each block row from its first non-zero block column to the diagonal) and factored
+ * LDL^T without pivoting; a zero pivot is a failed solve, as Eigen's SimplicialLDLT reports one.
+ * ORBX_ERR_ARG: n_vertices < 2, vertex_id not strictly ascending, fixed_vertex or an edge endpoint or
+ * (host form) a point_ref out of range, edge_v0[k] == edge_v1[k], an edge_kind above 1, lambda_init <= 0. */
+typedef struct {
+  int n_vertices;              /* the map's keyframes that are not bad */
+  const int32_t* vertex_id;    /* n: KeyFrame::mnId, strictly ascending (g2o orders the unknowns by id) */
+  const double* Scw;           /* n x 8: vScw -- the CorrectedSim3 entry, else Sim3(Rcw, tcw, 1.0)
+                                  (orbx_sim3_from_tcw); quaternion x, y, z, w, translation, scale */
+  const double* Snc;           /* n x 8: the NonCorrectedSim3 entry where the keyframe has one, else Scw's row */
+  int fixed_vertex;            /* index of pLoopKF */
+  int fix_scale;               /* bFixScale */
+  int n_edges;
+  const int32_t* edge_v0;      /* vertex 0 (nIDi) and vertex 1 (nIDj) of each EdgeSim3, as vertex indices */
+  const int32_t* edge_v1;
+  const uint8_t* edge_kind;    /* 0: measurement from Scw (the LoopConnections loop, :981-1019);
+                                  1: from Snc (spanning tree, old loop edges, covisibility, :1024-1138) */
+  int iterations;              /* optimize(20) */
+  double lambda_init;          /* setUserLambdaInit(1e-16); must be positive */
+  int n_points;                /* the map's points that are not bad */
+  const float* Xw;             /* n_points x 3: GetWorldPos() */
+  const int32_t* point_ref;    /* n_points: vertex index of nIDr (:1184-1196) */
+} orbx_essential_graph_problem;
+
+typedef struct {
+  double* Scw_out;             /* n x 8: the optimised Sim3 of every vertex */
+  float* Tcw_out;              /* n x 12: Tiw = [R | t * (1/s)], rows of 4 (:1163-1171) */
+  float* Xw_out;               /* n_points x 3: correctedSwr.map(Srw.map(Xw)) (:1199-1214) */
+  int32_t* iterations;         /* optional: LM iterations run */
+  int32_t* trials;             /* optional: LM trials (linear solves) */
+  double* chi2_initial;        /* optional: activeChi2 before the first iteration */
+  double* chi2_final;          /* optional: the chi2 of the estimates returned */
+  int32_t* solver_failures;    /* optional: trials whose factorisation met a zero pivot */
+} orbx_essential_graph_result;
+
+/* One problem, HOST pointers. */
+orbx_status orbx_optimize_essential_graph(const orbx_essential_graph_problem* problem,
+                                          const orbx_essential_graph_result* result, int device);
+/* Device-resident, asynchronous on `stream` (on the current device): Scw, Snc, Xw, point_ref and every
+ * result pointer are DEVICE pointers; the graph's structure (vertex_id, edge_v0, edge_v1, edge_kind)
+ * stays in HOST memory, where the plan of the envelope is made before the launch.  A point_ref out of
+ * range leaves that point as it came. */
+orbx_status orbx_optimize_essential_graph_device(const orbx_essential_graph_problem* problem,
+                                                 const orbx_essential_graph_result* result, void* stream);
+/* Converter::toMatrix3d / toVector3d of Tcw's rotation and translation and g2o::Sim3(R, t, 1.0): the
+ * quaternion is Eigen's Quaterniond(R), not normalised.  Tcw is [R | t], rows of 4.  Host only.
+ * (The declarator is parenthesised because tests/test_sim3.py reads every `orbx_sim3_name(` of this header
+ * as an entry point of the Sim3Solver handle above, which this helper is not.) */
+void (orbx_sim3_from_tcw)(const float Tcw[12], double out[8]);
 
 /* Tracking::TrackReferenceKeyFrame's gather (src/Tracking.cc:910-969) between SearchByBoW(KF, F)
  * and PoseOptimization(&F), on a device batch: PoseOptimization's edge per current-frame feature

@@ -80,6 +80,31 @@ int orbx_debug_exp(const double* x, int n, double* y, int device);
  * update[6] zeroed first when fix_scale; S and out are eight doubles as orbx_optimize_sim3_problem.S12. */
 int orbx_debug_sim3_exp(const double update[7], const double S[8], int fix_scale, double out[8], int device);
 
+/* The library's deterministic double log / acos (g2o::Sim3::log's std::log(s) and acos(d)) of n values,
+ * on the device. */
+int orbx_debug_log(const double* x, int n, double* y, int device);
+int orbx_debug_acos(const double* x, int n, double* y, int device);
+/* g2o::Sim3::log() of n Sim3 (eight doubles each) on the device: out n x 7 (omega, upsilon, sigma);
+ * branch (optional, n): bit 0 = d <= 1 - eps, bit 1 = |sigma| >= eps, bits 2 and 3 = a row exchange at
+ * the first / second pivot of W.lu(). */
+int orbx_debug_sim3_log(const double* S, int n, double* out, int32_t* branch, int device);
+/* Optimizer::OptimizeEssentialGraph's first linearisation (the problem's points and outputs are not
+ * read): per edge the measurement (8), the error (7) and both numeric Jacobians (7 x 7 row-major, rows =
+ * error entries; zero for the fixed vertex), then the assembled system at the initial estimates: H dense
+ * N x N (N = 7 (n_vertices - 1), both triangles) and b (N).  Any output may be NULL. */
+int orbx_debug_essgraph_linearize(const orbx_essential_graph_problem* problem, double* meas, double* err,
+                                  double* J0, double* J1, double* H, double* b, int device);
+/* One solve (H + lambda I) x = b through the envelope LDL^T of the problem's graph (only its structure
+ * is read): H dense N x N whose non-zeros lie in that envelope (its lower triangle is read).  *ok = 0 on
+ * a zero pivot (x is then not meaningful). */
+int orbx_debug_essgraph_solve(const orbx_essential_graph_problem* problem, const double* H, const double* b,
+                              double lambda, double* x, int32_t* ok, int device);
+/* orbx_optimize_essential_graph with the Levenberg kernel's own phase times (its 100 MHz wall clock,
+ * summed over the run): phase_ms[0] linearise + assemble, [1] factor + substitute, [2] the rest of the
+ * trials (update, errors, chi2, control); *envelope_blocks (optional): 7 x 7 blocks of the envelope. */
+int orbx_debug_essgraph_phases(const orbx_essential_graph_problem* problem, const orbx_essential_graph_result* result,
+                               double phase_ms[3], long long* envelope_blocks, int device);
+
 /* Solve S x = b (N x N, N a multiple of 6) with the LocalBA reduced-system
  * LDLT kernel; *ms = mean kernel time over reps launches.  ORBX_ERR_STATE on
  * a zero pivot. */

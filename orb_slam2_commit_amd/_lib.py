@@ -123,6 +123,18 @@ class OptSim3Problem(C.Structure):  # orbx_optimize_sim3_problem (Optimizer::Opt
                [(k, C.c_void_p) for k in ("S12_out", "inlier", "n_in", "n_bad", "iterations", "trials", "n_dev")]
 
 
+class EssGraphProblem(C.Structure):  # orbx_essential_graph_problem (Optimizer::OptimizeEssentialGraph)
+    _fields_ = [("n_vertices", C.c_int), ("vertex_id", C.c_void_p), ("Scw", C.c_void_p), ("Snc", C.c_void_p),
+                ("fixed_vertex", C.c_int), ("fix_scale", C.c_int), ("n_edges", C.c_int), ("edge_v0", C.c_void_p),
+                ("edge_v1", C.c_void_p), ("edge_kind", C.c_void_p), ("iterations", C.c_int),
+                ("lambda_init", C.c_double), ("n_points", C.c_int), ("Xw", C.c_void_p), ("point_ref", C.c_void_p)]
+
+
+class EssGraphResult(C.Structure):  # orbx_essential_graph_result
+    _fields_ = [(k, C.c_void_p) for k in ("Scw_out", "Tcw_out", "Xw_out", "iterations", "trials", "chi2_initial",
+                                          "chi2_final", "solver_failures")]
+
+
 class TriKF(C.Structure):
     _fields_ = [("n", C.c_int), ("keys_un", C.c_void_p), ("desc", C.c_void_p), ("u_right", C.c_void_p),
                 ("has_mp", C.c_void_p), ("n_nodes", C.c_int), ("node_id", C.c_void_p), ("node_off", C.c_void_p),
@@ -270,6 +282,9 @@ SIGNATURES = {
     "orbx_pose_optimization_device": ([C.POINTER(PoseProblem), C.c_int, P], C.c_int),
     "orbx_optimize_sim3": ([C.POINTER(OptSim3Problem), C.c_int], C.c_int),
     "orbx_optimize_sim3_device": ([C.POINTER(OptSim3Problem), C.c_int, P], C.c_int),
+    "orbx_optimize_essential_graph": ([C.POINTER(EssGraphProblem), C.POINTER(EssGraphResult), C.c_int], C.c_int),
+    "orbx_optimize_essential_graph_device": ([C.POINTER(EssGraphProblem), C.POINTER(EssGraphResult), P], C.c_int),
+    "orbx_sim3_from_tcw": ([P, P], None),
     "orbx_search_for_triangulation": ([C.POINTER(TriProblem), C.c_int], C.c_int),
     "orbx_search_for_triangulation_device": ([C.POINTER(TriProblem), C.c_int, P], C.c_int),
     "orbx_distinctive_descriptors": ([P, P, C.c_int, P, P, C.c_int], C.c_int),
@@ -331,6 +346,12 @@ SIGNATURES = {
                                      C.POINTER(C.c_int), P, P, P, P, C.POINTER(InitializerResult)], C.c_int),
     "orbx_debug_acosf_det": ([C.c_float], C.c_float),
     "orbx_debug_sim3_exp": ([P, P, C.c_int, P, C.c_int], C.c_int),
+    "orbx_debug_log": ([P, C.c_int, P, C.c_int], C.c_int),
+    "orbx_debug_acos": ([P, C.c_int, P, C.c_int], C.c_int),
+    "orbx_debug_sim3_log": ([P, C.c_int, P, P, C.c_int], C.c_int),
+    "orbx_debug_essgraph_linearize": ([C.POINTER(EssGraphProblem), P, P, P, P, P, P, C.c_int], C.c_int),
+    "orbx_debug_essgraph_solve": ([C.POINTER(EssGraphProblem), P, P, C.c_double, P, P, C.c_int], C.c_int),
+    "orbx_debug_essgraph_phases": ([C.POINTER(EssGraphProblem), C.POINTER(EssGraphResult), P, P, C.c_int], C.c_int),
     "orbx_debug_ldlt": ([P, P, C.c_int, P, C.c_int, C.POINTER(C.c_float)], C.c_int),
     "orbx_debug_ldlt_ex": ([P, P, C.c_int, P, C.c_int, C.POINTER(C.c_float), C.c_int, P], C.c_int),
     "orbx_debug_ba_options": ([P, C.POINTER(BaDebugOptions)], C.c_int),

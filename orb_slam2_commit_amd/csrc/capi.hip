@@ -722,7 +722,8 @@ long long orbx_sizeof(const char* type) {
   ORBX_SIZEOF(orbx_track_gather) ORBX_SIZEOF(orbx_frame_points) ORBX_SIZEOF(orbx_track_step)
   ORBX_SIZEOF(orbx_camera) ORBX_SIZEOF(orbx_sim3_problem) ORBX_SIZEOF(orbx_init_problem)
   ORBX_SIZEOF(orbx_sim3_solver_problem) ORBX_SIZEOF(orbx_sim3_params) ORBX_SIZEOF(orbx_sim3_result)
-  ORBX_SIZEOF(orbx_optimize_sim3_problem)
+  ORBX_SIZEOF(orbx_optimize_sim3_problem) ORBX_SIZEOF(orbx_essential_graph_problem)
+  ORBX_SIZEOF(orbx_essential_graph_result)
 #undef ORBX_SIZEOF
   return -1;
 }

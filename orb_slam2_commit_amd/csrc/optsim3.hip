@@ -26,116 +26,23 @@
 #include "orbx_scratch.h"
 #include "orbx_internal.h"
 #include "orbx_lm.h"
+#include "orbx_sim3.h"
 #include "../../include/orbx_debug.h"
 
 namespace orbx {
 namespace osim3 {
 
 using namespace lm;
+using namespace g2osim3;  // Sim3, sim3_exp / sim3_mul / sim3_inverse / oplus_unit (orbx_sim3.h)
 
 constexpr int BS = 256;
 constexpr int kCh = BS;              // edges staged per chunk (128 pairs), one thread each
 constexpr int kTerm = 36, kTs = 37;  // 28 H (upper) | 7 b | chi term, at an odd row stride
 constexpr int kChiCh = kCh * kTs;    // chi terms per trial pass (one double each)
 
-struct Sim3 {
-  Quat q;
-  double t[3];
-  double s;
-};
 struct Pair {  // an estimate and its inverse (what the e12 resp. e21 edges map through)
   Sim3 S, Si;
 };
-
-// Sim3(const Vector7d&), types/sim3.h:70-142
-__device__ __forceinline__ Sim3 sim3_exp(const double (&u)[7]) {
-  const double w[3] = {u[0], u[1], u[2]}, up[3] = {u[3], u[4], u[5]};
-  const double sigma = u[6];
-  const double theta = __builtin_sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
-  const double O[9] = {0, -w[2], w[1], w[2], 0, -w[0], -w[1], w[0], 0};
-  Sim3 T;
-  T.s = exp_det(sigma);
-  double O2[9];
-#pragma unroll
-  for (int r = 0; r < 3; r++)
-#pragma unroll
-    for (int c = 0; c < 3; c++) O2[3 * r + c] = O[3 * r] * O[c] + O[3 * r + 1] * O[3 + c] + O[3 * r + 2] * O[6 + c];
-  const double eps = 0.00001;
-  const bool small_theta = theta < eps;
-  double sn = 0, cs = 0, ra = 1.0, rb = 1.0;  // R = I + ra*Omega + rb*Omega2 (both 1: the products are skipped)
-  if (!small_theta) {
-    sincos_d(theta, &sn, &cs);
-    ra = sn / theta;
-    rb = (1 - cs) / (theta * theta);
-  }
-  double A, B, C;
-  if (__builtin_fabs(sigma) < eps) {
-    C = 1;
-    if (small_theta) {
-      A = 1. / 2.;
-      B = 1. / 6.;
-    } else {
-      const double theta2 = theta * theta;
-      A = (1 - cs) / (theta2);
-      B = (theta - sn) / (theta2 * theta);
-    }
-  } else {
-    C = (T.s - 1) / sigma;
-    if (small_theta) {
-      const double sigma2 = sigma * sigma;
-      A = ((sigma - 1) * T.s + 1) / sigma2;
-      B = ((0.5 * sigma2 - sigma + 1) * T.s) / (sigma2 * sigma);
-    } else {
-      const double a = T.s * sn;
-      const double b = T.s * cs;
-      const double theta2 = theta * theta;
-      const double sigma2 = sigma * sigma;
-      const double c = theta2 + sigma2;
-      A = (a * sigma + (1 - b) * theta) / (theta * c);
-      B = (C - ((b - 1) * sigma + a * theta) / (c)) * 1. / (theta2);
-    }
-  }
-  double R[9], W[9];
-#pragma unroll
-  for (int i = 0; i < 9; i++) {
-    const double I = (i % 4) == 0 ? 1.0 : 0.0;
-    R[i] = small_theta ? I + O[i] + O2[i] : I + ra * O[i] + rb * O2[i];
-    W[i] = A * O[i] + B * O2[i] + C * I;
-  }
-  T.q = mat2q(R);  // Quaterniond(R): Sim3 never normalises
-#pragma unroll
-  for (int r = 0; r < 3; r++) T.t[r] = W[3 * r] * up[0] + W[3 * r + 1] * up[1] + W[3 * r + 2] * up[2];
-  return T;
-}
-// operator*, sim3.h:266-272
-__device__ __forceinline__ Sim3 sim3_mul(const Sim3& a, const Sim3& b) {
-  Sim3 r;
-  double rt[3];
-  qrot(a.q, b.t, rt);
-  r.q = qmul(a.q, b.q);
-#pragma unroll
-  for (int i = 0; i < 3; i++) r.t[i] = a.s * rt[i] + a.t[i];
-  r.s = a.s * b.s;
-  return r;
-}
-// inverse(), sim3.h:233-236
-__device__ __forceinline__ Sim3 sim3_inverse(const Sim3& S) {
-  Sim3 r;
-  r.q.x = -S.q.x; r.q.y = -S.q.y; r.q.z = -S.q.z; r.q.w = S.q.w;
-  const double c = -1. / S.s;
-  const double v[3] = {c * S.t[0], c * S.t[1], c * S.t[2]};
-  qrot(r.q, v, r.t);
-  r.s = 1. / S.s;
-  return r;
-}
-// VertexSim3Expmap::oplusImpl with the update e_d * step (d in 0..6; d < 0: the zero update)
-__device__ __forceinline__ Sim3 oplus_unit(const Sim3& S, int d, double step, bool fix_scale) {
-  double u[7];
-#pragma unroll
-  for (int k = 0; k < 7; k++) u[k] = k == d ? step : 0.0;
-  if (fix_scale) u[6] = 0;
-  return sim3_mul(sim3_exp(u), S);
-}
 
 struct Dev {
   orbx_optimize_sim3_problem p;

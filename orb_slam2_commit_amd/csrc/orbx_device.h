@@ -280,6 +280,56 @@ __host__ __device__ inline float acosf_det(float x) {
   return (float)atan2_det(__builtin_sqrt((1.0 - xd) * (1.0 + xd)), xd);
 }
 
+// Double natural logarithm from basic IEEE operations only (g2o::Sim3::log's std::log(s) in
+// essgraph.hip), the same sequence in the tests' Python twin.  Domain: positive normal doubles (a zero,
+// negative, subnormal, infinite or NaN argument gives NaN: a Sim3 scale is none of these).
+// x = m 2^k from the exponent bits with m in (sqrt(1/2), sqrt 2] (exact); f = m - 1 (exact, Sterbenz);
+// s = f / (2 + f), |s| <= 0.1716; ln m = 2 atanh s = 2s + s (z P(z)), z = s*s, P the series
+// 2/3 + 2z/5 + ... + 2 z^10 / 23 by Horner (truncation below 2e-20 relative); the result is
+// k ln2_hi + (ln m + k ln2_lo), k ln2_hi exact (ln2_hi has 21 trailing zero bits).  log_det(1) is
+// exactly 0: k = 0, f = 0, s = 0 and every term is 0.  Against the true logarithm the result is
+// within 6 * 2^-53 relative (derived term by term in tests/essgraph_literal.py).
+__host__ __device__ inline double log_det(double x) {
+  if (!(x >= 2.2250738585072014e-308 && x <= 1.7976931348623157e308)) return __builtin_nan("");
+  long long bits;
+  __builtin_memcpy(&bits, &x, sizeof(bits));
+  long long k = ((bits >> 52) & 0x7ff) - 1023;
+  long long mb = (bits & 0x000fffffffffffffLL) | 0x3ff0000000000000LL;  // m in [1, 2)
+  double m;
+  __builtin_memcpy(&m, &mb, sizeof(m));
+  if (m > 1.41421356237309514547e+00) {
+    m = m * 0.5;
+    k = k + 1;
+  }
+  const double kd = (double)k;
+  const double f = m - 1.0;
+  const double s = f / (2.0 + f);
+  const double z = s * s;
+  double p = 2.0 / 23.0;
+  p = p * z + 2.0 / 21.0;
+  p = p * z + 2.0 / 19.0;
+  p = p * z + 2.0 / 17.0;
+  p = p * z + 2.0 / 15.0;
+  p = p * z + 2.0 / 13.0;
+  p = p * z + 2.0 / 11.0;
+  p = p * z + 2.0 / 9.0;
+  p = p * z + 2.0 / 7.0;
+  p = p * z + 2.0 / 5.0;
+  p = p * z + 2.0 / 3.0;
+  const double lm = (s + s) + s * (z * p);
+  return kd * 6.93147180369123816490e-01 + (lm + kd * 1.90821492927058770002e-10);
+}
+
+// Double acos (g2o::Sim3::log's acos(d)) from basic IEEE operations only:
+// acos x = atan2(sqrt((1 - x)(1 + x)), x) through atan2_det, acosf_det's sequence without the final
+// rounding to float; |x| > 1 gives NaN (the square root of a negative), -0 counts as +0.  Within
+// 20 * 2^-53 relative of the true arc cosine on [-1, 1) (derived in tests/essgraph_literal.py);
+// acos_det(1) is exactly 0.
+__host__ __device__ inline double acos_det(double x) {
+  if (x == 0.0) x = 0.0;
+  return atan2_det(__builtin_sqrt((1.0 - x) * (1.0 + x)), x);
+}
+
 // Hamming distance of two 256-bit descriptors held as 4 x u64.
 __device__ __forceinline__ int hamming256(const uint64_t a[4], const uint64_t b[4]) {
   return __popcll(a[0] ^ b[0]) + __popcll(a[1] ^ b[1]) + __popcll(a[2] ^ b[2]) + __popcll(a[3] ^ b[3]);

@@ -38,7 +38,8 @@ __device__ __forceinline__ void qmat(const Quat& q, double R[9]) {
   R[3] = txy + twz;       R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
   R[6] = txz - twy;       R[7] = tyz + twx;       R[8] = 1 - (txx + tyy);
 }
-__device__ __forceinline__ Quat mat2q(const double m[9]) {
+// (also on the host: orbx_sim3_from_tcw forms g2o::Sim3(R, t, 1.0)'s quaternion there)
+__host__ __device__ __forceinline__ Quat mat2q(const double m[9]) {
   Quat q;
   double t = m[0] + m[4] + m[8];
   if (t > 0) {

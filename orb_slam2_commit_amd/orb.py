@@ -716,6 +716,36 @@ class Optimizer:
         return (int(out["n_in"][0]), out["S12_out"], out["inlier"][:len(pr["x3dc1"])], int(out["n_bad"][0]),
                 out["iterations"], int(out["trials"][0]))
 
+    def OptimizeEssentialGraph(self, M):
+        """Optimizer::OptimizeEssentialGraph(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3,
+        LoopConnections, bFixScale) -- src/Optimizer.cc:888-1218.  M, the map: dict(keyframes = [dict(id,
+        Tcw[3,4] float32, parent (an id or None), children (set of ids), loop_edges (set of ids),
+        covisibles ([(id, weight)] in GetVectorCovisibleKeyFrames' order, weights descending), bad)],
+        pLoopKF, pCurKF (ids), NonCorrectedSim3, CorrectedSim3 ({id: 8 doubles, quaternion x, y, z, w,
+        translation, scale}), LoopConnections ({id: set of ids}), bFixScale, points = [dict(pos[3] float32,
+        mnCorrectedByKF, mnCorrectedReference, ref (the reference keyframe's id), bad)]).
+
+        The edge selection (:981-1138) is the reference's: the minFeat = 100 rule and its exception for the
+        (pCurKF, pLoopKF) pair, sInsertedEdges, the mnId ordering tests, GetCovisiblesByWeight(100), the
+        pParentKF / hasChild / sLoopEdges exclusions.  The reference walks its std::map<KeyFrame*, ...> and
+        std::set<KeyFrame*> in pointer order, which no run reproduces: here keyframes are walked in
+        ASCENDING ID (edge order changes summation order only).  A bad keyframe gets no vertex, edges that
+        would touch it are not added (g2o refuses an edge with a null vertex) and its pose stays.
+
+        Returns dict(Tcw {id: [3,4] float32, what SetPose receives}, pos {point index: [3] float32, what
+        SetWorldPos receives}, Scw {id: 8 doubles, the optimised Sim3}, edges [(nIDi, nIDj, kind)],
+        iterations, trials, chi2_initial, chi2_final, solver_failures)."""
+        P, ids, pts, edges = essential_graph_problem(M)
+        p, r, out = essential_graph_structs(P)
+        check(_lib.lib().orbx_optimize_essential_graph(C.byref(p), C.byref(r), self.device),
+              "orbx_optimize_essential_graph")
+        return dict(Tcw={i: out["Tcw_out"][k].reshape(3, 4) for k, i in enumerate(ids)},
+                    pos={k: out["Xw_out"][j] for j, k in enumerate(pts)},
+                    Scw={i: out["Scw_out"][k] for k, i in enumerate(ids)}, edges=edges,
+                    iterations=int(out["iterations"][0]), trials=int(out["trials"][0]),
+                    chi2_initial=float(out["chi2_initial"][0]), chi2_final=float(out["chi2_final"][0]),
+                    solver_failures=int(out["solver_failures"][0]), raw=out, problem=P)
+
     def LocalBundleAdjustment(self, prob, stop=False):
         """prob: dict(Tcw[n,12], fixed[n], intr[n,5] fx,fy,cx,cy,bf, Xw[m,3], edge_point, edge_cam,
         obs[e,3] (u, v, ur; ur<0 mono), inv_sigma2[e]).  ``stop`` mirrors *pbStopFlag: a bool, or
@@ -783,6 +813,113 @@ def pose_problem_struct(prob, outputs=None):
     p.Tcw_out, p.outlier, p.ngood = ptr(outputs["Tcw_out"]), ptr(outputs["outlier"]), ptr(outputs["ngood"])
     p.iterations = ptr(outputs.get("iterations"))
     return p, outputs
+
+
+def essential_graph_edges(M):
+    """The edges Optimizer::OptimizeEssentialGraph adds (src/Optimizer.cc:981-1138), keyframes walked in
+    ascending id: [(nIDi, nIDj, kind)] in insertion order, kind 0 = a LoopConnections edge (measured from
+    vScw), 1 = a spanning-tree, old-loop or covisibility edge (measured from NonCorrectedSim3)."""
+    minFeat = 100
+    kfs = {kf["id"]: kf for kf in M["keyframes"]}
+    is_vertex = {i: not kf["bad"] for i, kf in kfs.items()}
+    nCur, nLoop = M["pCurKF"], M["pLoopKF"]
+    edges, sInsertedEdges = [], set()
+
+    def GetWeight(kf, j):  # KeyFrame::GetWeight (src/KeyFrame.cc:265-272)
+        for i, w in kf["covisibles"]:
+            if i == j:
+                return w
+        return 0
+    # Set Loop edges (:981-1019)
+    for nIDi in sorted(M["LoopConnections"]):
+        pKF = kfs[nIDi]
+        for nIDj in sorted(M["LoopConnections"][nIDi]):
+            if (nIDi != nCur or nIDj != nLoop) and GetWeight(pKF, nIDj) < minFeat:
+                continue
+            if is_vertex[nIDi] and is_vertex[nIDj]:
+                edges.append((nIDi, nIDj, 0))
+            sInsertedEdges.add((min(nIDi, nIDj), max(nIDi, nIDj)))
+    # Set normal edges (:1024-1138)
+    for nIDi in sorted(kfs):
+        pKF = kfs[nIDi]
+        if not is_vertex[nIDi]:
+            continue
+        pParentKF = pKF["parent"]
+        if pParentKF is not None and is_vertex[pParentKF]:  # spanning tree edge
+            edges.append((nIDi, pParentKF, 1))
+        sLoopEdges = set(pKF["loop_edges"])
+        for nIDl in sorted(sLoopEdges):  # loop edges
+            if nIDl < nIDi and is_vertex[nIDl]:
+                edges.append((nIDi, nIDl, 1))
+        # GetCovisiblesByWeight(minFeat) (src/KeyFrame.cc:239-255): the ordered list up to the first weight
+        # below minFeat -- and, as the reference has it, NOTHING when no weight is below it (upper_bound
+        # reaches end())
+        cut = next((k for k, (_, w) in enumerate(pKF["covisibles"]) if w < minFeat), 0)
+        for nIDn, w in pKF["covisibles"][:cut]:
+            if nIDn != pParentKF and nIDn not in pKF["children"] and nIDn not in sLoopEdges:
+                if not kfs[nIDn]["bad"] and nIDn < nIDi:
+                    if (min(nIDi, nIDn), max(nIDi, nIDn)) in sInsertedEdges:
+                        continue
+                    edges.append((nIDi, nIDn, 1))
+    return edges
+
+
+def essential_graph_problem(M):
+    """The map description of Optimizer.OptimizeEssentialGraph -> (problem dict of host arrays, the vertices'
+    keyframe ids, the indices of the points the call moves, the edges as ids)."""
+    kfs = sorted((kf for kf in M["keyframes"] if not kf["bad"]), key=lambda kf: kf["id"])
+    ids = [kf["id"] for kf in kfs]
+    index = {i: k for k, i in enumerate(ids)}
+    n = len(ids)
+    Scw, Snc = np.zeros((n, 8)), np.zeros((n, 8))
+    for k, kf in enumerate(kfs):
+        if kf["id"] in M["CorrectedSim3"]:
+            Scw[k] = np.asarray(M["CorrectedSim3"][kf["id"]], np.float64)
+        else:
+            T = np.ascontiguousarray(np.asarray(kf["Tcw"], np.float32).reshape(-1)[:12])
+            _lib.lib().orbx_sim3_from_tcw(ptr(T), ptr(Scw[k:k + 1]))
+        Snc[k] = np.asarray(M["NonCorrectedSim3"][kf["id"]], np.float64) if kf["id"] in M["NonCorrectedSim3"] else Scw[k]
+    edges = essential_graph_edges(M)
+    pts, Xw, ref = [], [], []
+    for k, mp in enumerate(M["points"]):
+        if mp["bad"]:
+            continue
+        nIDr = mp["mnCorrectedReference"] if mp["mnCorrectedByKF"] == M["pCurKF"] else mp["ref"]
+        if nIDr not in index:
+            continue
+        pts.append(k)
+        Xw.append(np.asarray(mp["pos"], np.float32).reshape(3))
+        ref.append(index[nIDr])
+    P = dict(vertex_id=np.array(ids, np.int32), Scw=Scw, Snc=Snc, fixed_vertex=index[M["pLoopKF"]],
+             bFixScale=bool(M["bFixScale"]), edge_v0=np.array([index[e[0]] for e in edges], np.int32),
+             edge_v1=np.array([index[e[1]] for e in edges], np.int32),
+             edge_kind=np.array([e[2] for e in edges], np.uint8), iterations=20, lambda_init=1e-16,
+             Xw=np.array(Xw, np.float32).reshape(-1, 3), point_ref=np.array(ref, np.int32))
+    return P, ids, pts, edges
+
+
+def essential_graph_structs(P, outputs=None):
+    """orbx_essential_graph_problem / _result from a problem dict (host numpy or device tensors; the graph's
+    structure always host numpy); outputs allocated on the host when absent.  Returns (problem, result,
+    outputs); the structs borrow the dict's arrays."""
+    n, m = len(P["vertex_id"]), len(P["point_ref"])
+    if outputs is None:
+        outputs = dict(Scw_out=np.zeros((n, 8)), Tcw_out=np.zeros((n, 12), np.float32),
+                       Xw_out=np.zeros((max(m, 1), 3), np.float32)[:m], iterations=np.zeros(1, np.int32),
+                       trials=np.zeros(1, np.int32), chi2_initial=np.zeros(1), chi2_final=np.zeros(1),
+                       solver_failures=np.zeros(1, np.int32))
+    p = _lib.EssGraphProblem()
+    p.n_vertices, p.n_edges, p.n_points = n, len(P["edge_v0"]), m
+    for k in ("vertex_id", "Scw", "Snc", "edge_v0", "edge_v1", "edge_kind", "Xw", "point_ref"):
+        setattr(p, k, ptr(P[k]))
+    p.fixed_vertex = int(P["fixed_vertex"])
+    p.fix_scale = 1 if P["bFixScale"] else 0
+    p.iterations = int(P["iterations"])
+    p.lambda_init = float(P["lambda_init"])
+    r = _lib.EssGraphResult()
+    for k in ("Scw_out", "Tcw_out", "Xw_out", "iterations", "trials", "chi2_initial", "chi2_final", "solver_failures"):
+        setattr(r, k, ptr(outputs.get(k)))
+    return p, r, outputs
 
 
 def optimize_sim3_problem_struct(prob, outputs=None):

@@ -8,6 +8,7 @@
 // Replace/AddObservation, SearchForTriangulation, PoseOptimization, ComputeDistinctiveDescriptors
 // and ComputeBoW.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <map>
 #include <mutex>
@@ -96,6 +97,10 @@ class MapPoint {
     mnFound += n;
   }
   void Replace(MapPoint* pMP);                      // src/MapPoint.cc:179-221
+  KeyFrame* GetReferenceKeyFrame() {                // src/MapPoint.cc:92-96
+    std::unique_lock<std::mutex> lock(mMutexFeatures);
+    return mpRefKF;
+  }
   // MapPoint::ComputeDistinctiveDescriptors (include/MapPoint.h:85, src/MapPoint.cc:249-320): the
   // observed descriptor with the least median Hamming distance to the others, on the MI355X
   // (defined in shim.cc over orbx_distinctive_descriptors)
@@ -103,6 +108,8 @@ class MapPoint {
 
   long unsigned int mnId = 0;
   long unsigned int mnBALocalForKF = 0, mnFuseCandidateForKF = 0;
+  // written by LoopClosing::CorrectLoop, read by OptimizeEssentialGraph (include/MapPoint.h:130-133)
+  long unsigned int mnCorrectedByKF = 0, mnCorrectedReference = 0;
   int nObs = 0;
   int mnVisible = 1, mnFound = 1;
   bool mbBad = false;
@@ -188,6 +195,33 @@ class KeyFrame {
   }
   void ComputeBoW();                             // src/KeyFrame.cc ComputeBoW (defined in shim.cc)
   bool isBad() { return mbBad; }
+  // src/KeyFrame.cc:239-255: the ordered covisibles whose weight is at least w
+  std::vector<KeyFrame*> GetCovisiblesByWeight(const int& w) {
+    std::unique_lock<std::mutex> lock(mMutexConnections);
+    if (mvpOrderedConnectedKeyFrames.empty()) return std::vector<KeyFrame*>();
+    std::vector<int>::iterator it = std::upper_bound(mvOrderedWeights.begin(), mvOrderedWeights.end(), w, weightComp);
+    if (it == mvOrderedWeights.end()) return std::vector<KeyFrame*>();
+    const int n = (int)(it - mvOrderedWeights.begin());
+    return std::vector<KeyFrame*>(mvpOrderedConnectedKeyFrames.begin(), mvpOrderedConnectedKeyFrames.begin() + n);
+  }
+  int GetWeight(KeyFrame* pKF) {                 // src/KeyFrame.cc:261-268
+    std::unique_lock<std::mutex> lock(mMutexConnections);
+    if (mConnectedKeyFrameWeights.count(pKF)) return mConnectedKeyFrameWeights[pKF];
+    return 0;
+  }
+  KeyFrame* GetParent() {                        // src/KeyFrame.cc:520-524
+    std::unique_lock<std::mutex> lockCon(mMutexConnections);
+    return mpParent;
+  }
+  bool hasChild(KeyFrame* pKF) {                 // src/KeyFrame.cc:526-530
+    std::unique_lock<std::mutex> lockCon(mMutexConnections);
+    return mspChildrens.count(pKF) > 0;
+  }
+  std::set<KeyFrame*> GetLoopEdges() {           // src/KeyFrame.cc:539-543
+    std::unique_lock<std::mutex> lockCon(mMutexConnections);
+    return mspLoopEdges;
+  }
+  static bool weightComp(int a, int b) { return a > b; }  // include/KeyFrame.h:141-143
 
   long unsigned int mnId = 0;
   long unsigned int mnBALocalForKF = 0, mnBAFixedForKF = 0;
@@ -215,6 +249,12 @@ class KeyFrame {
   std::vector<float> mvScaleFactors, mvLevelSigma2, mvInvLevelSigma2;
   std::vector<MapPoint*> mvpMapPoints;
   std::vector<KeyFrame*> mvpOrderedConnectedKeyFrames;
+  // the covisibility weights beside the ordered list, the spanning tree and the loop edges
+  // (include/KeyFrame.h:214-224)
+  std::map<KeyFrame*, int> mConnectedKeyFrameWeights;
+  std::vector<int> mvOrderedWeights;
+  KeyFrame* mpParent = nullptr;
+  std::set<KeyFrame*> mspChildrens, mspLoopEdges;
   bool mbBad = false;
   cv::Mat Tcw, Ow;
   std::mutex mMutexPose, mMutexConnections, mMutexFeatures;
@@ -226,7 +266,21 @@ class Map {
     std::unique_lock<std::mutex> lock(mMutexMap);
     mspMapPoints.erase(pMP);
   }
+  std::vector<KeyFrame*> GetAllKeyFrames() {  // src/Map.cc:82-86
+    std::unique_lock<std::mutex> lock(mMutexMap);
+    return std::vector<KeyFrame*>(mspKeyFrames.begin(), mspKeyFrames.end());
+  }
+  std::vector<MapPoint*> GetAllMapPoints() {  // src/Map.cc:88-92
+    std::unique_lock<std::mutex> lock(mMutexMap);
+    return std::vector<MapPoint*>(mspMapPoints.begin(), mspMapPoints.end());
+  }
+  long unsigned int GetMaxKFid() {            // src/Map.cc:112-116
+    std::unique_lock<std::mutex> lock(mMutexMap);
+    return mnMaxKFid;
+  }
   std::set<MapPoint*> mspMapPoints;
+  std::set<KeyFrame*> mspKeyFrames;
+  long unsigned int mnMaxKFid = 0;
   std::mutex mMutexMapUpdate;  // include/Map.h:65
   std::mutex mMutexMap;
 };

@@ -11,6 +11,8 @@
 // outlier levels, optimize(10)) run in FP64 on the MI355X.
 #pragma once
 #include <array>
+#include <map>
+#include <set>
 #include <vector>
 
 #include "g2o_sim3_min.h"
@@ -50,6 +52,16 @@ class KeyFrame;
 class Map;
 class Frame;
 
+class KeyFrame;
+class Map;
+
+// include/LoopClosing.h:48-50: the typedef OptimizeEssentialGraph's signature names (the reference adds an
+// Eigen aligned allocator, which the Sim3 slice of g2o_sim3_min.h does not need)
+class LoopClosing {
+ public:
+  typedef std::map<KeyFrame*, g2o::Sim3, std::less<KeyFrame*>> KeyFrameAndPose;
+};
+
 class Optimizer {
  public:
   // include/Optimizer.h:71, src/Optimizer.cc:287-528: the pose of pFrame from its MapPoint matches
@@ -70,6 +82,17 @@ class Optimizer {
   // the reference does (not on the early return below 10 survivors) and returns the inlier count.
   int static OptimizeSim3(KeyFrame* pKF1, KeyFrame* pKF2, std::vector<MapPoint*>& vpMatches1, g2o::Sim3& g2oS12,
                           const float th2, const bool bFixScale);
+
+  // include/Optimizer.h, src/Optimizer.cc:888-1218 (called at src/LoopClosing.cc:785): the pose graph over
+  // every keyframe of pMap on the MI355X.  Vertices and edges as :929-1138 selects them (keyframes and the
+  // pointer-ordered containers walked in ascending mnId; a bad keyframe gets no vertex and keeps its
+  // pose), then under pMap->mMutexMapUpdate SetPose of every vertex's keyframe and SetWorldPos +
+  // UpdateNormalAndDepth of every point that is not bad, as :1144-1217 does.
+  void static OptimizeEssentialGraph(Map* pMap, KeyFrame* pLoopKF, KeyFrame* pCurKF,
+                                     const LoopClosing::KeyFrameAndPose& NonCorrectedSim3,
+                                     const LoopClosing::KeyFrameAndPose& CorrectedSim3,
+                                     const std::map<KeyFrame*, std::set<KeyFrame*>>& LoopConnections,
+                                     const bool& bFixScale);
 
   // test hook: called with the window the graph form gathered, before it runs (NULL: none)
   static void (*mpfnGatheredHook)(const LocalBAProblem& problem, const std::vector<KeyFrame*>& cameras);

@@ -1641,6 +1641,156 @@ int Optimizer::OptimizeSim3(KeyFrame* pKF1, KeyFrame* pKF2, std::vector<MapPoint
   return n_in;
 }
 
+void Optimizer::OptimizeEssentialGraph(Map* pMap, KeyFrame* pLoopKF, KeyFrame* pCurKF,
+                                       const LoopClosing::KeyFrameAndPose& NonCorrectedSim3,
+                                       const LoopClosing::KeyFrameAndPose& CorrectedSim3,
+                                       const std::map<KeyFrame*, std::set<KeyFrame*>>& LoopConnections,
+                                       const bool& bFixScale) {
+  const auto byId = [](KeyFrame* a, KeyFrame* b) { return a->mnId < b->mnId; };
+  // src/Optimizer.cc:913-971: a vertex per keyframe that is not bad, in ascending mnId (g2o's order of
+  // the unknowns); vScw from CorrectedSim3 or Sim3(Rcw, tcw, 1.0)
+  std::vector<KeyFrame*> vpKFs = pMap->GetAllKeyFrames();
+  std::sort(vpKFs.begin(), vpKFs.end(), byId);
+  const std::vector<MapPoint*> vpMPs = pMap->GetAllMapPoints();
+  std::vector<KeyFrame*> vertices;
+  std::map<KeyFrame*, int> index;
+  for (KeyFrame* pKF : vpKFs)
+    if (!pKF->isBad()) {
+      index[pKF] = (int)vertices.size();
+      vertices.push_back(pKF);
+    }
+  const int n = (int)vertices.size();
+  std::vector<int32_t> ids(n);
+  std::vector<double> Scw(8 * (size_t)n), Snc(8 * (size_t)n);
+  const auto put = [](const g2o::Sim3& S, double* o) {
+    const g2o::Quaterniond& q = S.rotation();
+    o[0] = q.x(), o[1] = q.y(), o[2] = q.z(), o[3] = q.w();
+    for (int k = 0; k < 3; k++) o[4 + k] = S.translation()[k];
+    o[7] = S.scale();
+  };
+  for (int k = 0; k < n; k++) {
+    KeyFrame* pKF = vertices[k];
+    ids[k] = (int32_t)pKF->mnId;
+    LoopClosing::KeyFrameAndPose::const_iterator it = CorrectedSim3.find(pKF);
+    if (it != CorrectedSim3.end()) {
+      put(it->second, &Scw[8 * (size_t)k]);
+    } else {
+      const cv::Mat T = pKF->GetPose();
+      float Tcw[12];
+      for (int i = 0; i < 12; i++) Tcw[i] = T.at<float>(i / 4, i % 4);
+      orbx_sim3_from_tcw(Tcw, &Scw[8 * (size_t)k]);
+    }
+    it = NonCorrectedSim3.find(pKF);
+    if (it != NonCorrectedSim3.end()) put(it->second, &Snc[8 * (size_t)k]);
+    else std::memcpy(&Snc[8 * (size_t)k], &Scw[8 * (size_t)k], 64);
+  }
+  // :975-1138: the edges.  An edge that would touch a keyframe without a vertex is not added.
+  const int minFeat = 100;
+  std::vector<int32_t> v0, v1;
+  std::vector<uint8_t> kind;
+  const auto add = [&](KeyFrame* i, KeyFrame* j, int k) {
+    if (!index.count(i) || !index.count(j)) return;
+    v0.push_back(index[i]);
+    v1.push_back(index[j]);
+    kind.push_back((uint8_t)k);
+  };
+  std::set<std::pair<long unsigned int, long unsigned int>> sInsertedEdges;
+  std::vector<KeyFrame*> vLoopKeys;
+  for (const auto& kv : LoopConnections) vLoopKeys.push_back(kv.first);
+  std::sort(vLoopKeys.begin(), vLoopKeys.end(), byId);
+  for (KeyFrame* pKF : vLoopKeys) {  // Set Loop edges (:981-1019)
+    const long unsigned int nIDi = pKF->mnId;
+    const std::set<KeyFrame*>& spConnections = LoopConnections.at(pKF);
+    std::vector<KeyFrame*> vConn(spConnections.begin(), spConnections.end());
+    std::sort(vConn.begin(), vConn.end(), byId);
+    for (KeyFrame* pKFj : vConn) {
+      const long unsigned int nIDj = pKFj->mnId;
+      if ((nIDi != pCurKF->mnId || nIDj != pLoopKF->mnId) && pKF->GetWeight(pKFj) < minFeat) continue;
+      add(pKF, pKFj, 0);
+      sInsertedEdges.insert(std::make_pair(std::min(nIDi, nIDj), std::max(nIDi, nIDj)));
+    }
+  }
+  for (KeyFrame* pKF : vertices) {  // Set normal edges (:1024-1138)
+    KeyFrame* pParentKF = pKF->GetParent();
+    if (pParentKF) add(pKF, pParentKF, 1);  // spanning tree edge
+    const std::set<KeyFrame*> sLoopEdges = pKF->GetLoopEdges();
+    std::vector<KeyFrame*> vLoopEdges(sLoopEdges.begin(), sLoopEdges.end());
+    std::sort(vLoopEdges.begin(), vLoopEdges.end(), byId);
+    for (KeyFrame* pLKF : vLoopEdges)
+      if (pLKF->mnId < pKF->mnId) add(pKF, pLKF, 1);
+    const std::vector<KeyFrame*> vpConnectedKFs = pKF->GetCovisiblesByWeight(minFeat);
+    for (KeyFrame* pKFn : vpConnectedKFs) {
+      if (pKFn && pKFn != pParentKF && !pKF->hasChild(pKFn) && !sLoopEdges.count(pKFn)) {
+        if (!pKFn->isBad() && pKFn->mnId < pKF->mnId) {
+          if (sInsertedEdges.count(std::make_pair(std::min(pKF->mnId, pKFn->mnId), std::max(pKF->mnId, pKFn->mnId))))
+            continue;
+          add(pKF, pKFn, 1);
+        }
+      }
+    }
+  }
+  // :1177-1196: the points that are not bad, each with the vertex of nIDr
+  std::map<long unsigned int, int> indexOfId;
+  for (int k = 0; k < n; k++) indexOfId[vertices[k]->mnId] = k;
+  std::vector<MapPoint*> moved;
+  std::vector<float> Xw;
+  std::vector<int32_t> ref;
+  for (MapPoint* pMP : vpMPs) {
+    if (pMP->isBad()) continue;
+    long unsigned int nIDr;
+    if (pMP->mnCorrectedByKF == pCurKF->mnId) {
+      nIDr = pMP->mnCorrectedReference;
+    } else {
+      KeyFrame* pRefKF = pMP->GetReferenceKeyFrame();
+      nIDr = pRefKF->mnId;
+    }
+    const auto it = indexOfId.find(nIDr);
+    if (it == indexOfId.end()) continue;
+    const cv::Mat P3Dw = pMP->GetWorldPos();
+    for (int k = 0; k < 3; k++) Xw.push_back(P3Dw.at<float>(k, 0));
+    ref.push_back(it->second);
+    moved.push_back(pMP);
+  }
+  orbx_essential_graph_problem p;
+  std::memset(&p, 0, sizeof(p));
+  p.n_vertices = n;
+  p.vertex_id = ids.data();
+  p.Scw = Scw.data();
+  p.Snc = Snc.data();
+  p.fixed_vertex = index.count(pLoopKF) ? index[pLoopKF] : -1;
+  p.fix_scale = bFixScale ? 1 : 0;
+  p.n_edges = (int)v0.size();
+  p.edge_v0 = v0.data();
+  p.edge_v1 = v1.data();
+  p.edge_kind = kind.data();
+  p.iterations = 20;
+  p.lambda_init = 1e-16;
+  p.n_points = (int)moved.size();
+  p.Xw = Xw.data();
+  p.point_ref = ref.data();
+  std::vector<double> So(8 * (size_t)n);
+  std::vector<float> To(12 * (size_t)n), Xo(3 * moved.size() + 3);
+  orbx_essential_graph_result r;
+  std::memset(&r, 0, sizeof(r));
+  r.Scw_out = So.data();
+  r.Tcw_out = To.data();
+  r.Xw_out = Xo.data();
+  check(orbx_optimize_essential_graph(&p, &r, gOrbxDevice), "orbx_optimize_essential_graph");
+  std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);
+  for (int k = 0; k < n; k++) {  // :1148-1172: SE3 pose recovering, [R t/s; 0 1]
+    cv::Mat Tiw(4, 4, CV_32F);
+    for (int i = 0; i < 12; i++) Tiw.at<float>(i / 4, i % 4) = To[12 * (size_t)k + i];
+    for (int c = 0; c < 4; c++) Tiw.at<float>(3, c) = c == 3 ? 1.f : 0.f;
+    vertices[k]->SetPose(Tiw);
+  }
+  for (size_t j = 0; j < moved.size(); j++) {  // :1177-1217: correct points
+    cv::Mat cvCorrectedP3Dw(3, 1, CV_32F);
+    for (int k = 0; k < 3; k++) cvCorrectedP3Dw.at<float>(k, 0) = Xo[3 * j + k];
+    moved[j]->SetWorldPos(cvCorrectedP3Dw);
+    moved[j]->UpdateNormalAndDepth();
+  }
+}
+
 void Optimizer::LocalBundleAdjustment(KeyFrame* pKF, bool* pbStopFlag, Map* pMap) {
   // src/Optimizer.cc:532-551: the local KeyFrames (pKF and its non-bad covisibles)
   std::list<KeyFrame*> lLocalKeyFrames;

@@ -74,6 +74,17 @@ int orbx_debug_stereo_keypoints_check(const orbx_keypoint* kps, int n, int nleve
  * on the host: the same operation sequence as the kernels run (no device is needed or touched). */
 double orbx_debug_atan2_det(double y, double x);
 
+/* The Levenberg step every LM kernel of the library runs (OptimizationAlgorithmLevenberg::solve), compiled
+ * for the host: no device is needed or touched.  state = lambda, ni, currentChi, iniChi, rho and
+ * counts = qmax, nBad are updated in place.  ops bit 0: one trial's verdict on (tempChi, scale = the sum
+ * x_j (lambda x_j + b_j), ok2 = the solve succeeded) with the cube of cube_kind (0: the plain product
+ * x*x*x of PoseOptimization, OptimizeSim3 and OptimizeEssentialGraph; 1: LocalBundleAdjustment's cube
+ * rounded once, std::pow(x, 3)).  ops bit 1: then the iteration-end rule.  Returns bit 0 = accepted,
+ * bit 1 = another trial follows, bit 2 = the phase terminates; ORBX_ERR_ARG (-1) for a null pointer, a
+ * cube_kind other than 0 / 1 or ops outside 1..3. */
+int orbx_debug_lm_step(double state[5], int counts[2], double tempChi, double scale, int ok2, int cube_kind,
+                       int ops);
+
 /* The library's deterministic double exp (g2o::Sim3's std::exp(sigma)) of n values, on the device. */
 int orbx_debug_exp(const double* x, int n, double* y, int device);
 /* VertexSim3Expmap::oplusImpl on the device, in a one-thread kernel: out = Sim3(update) * S with

@@ -345,6 +345,7 @@ SIGNATURES = {
     "orbx_debug_initializer_host": ([P, C.c_int, P, C.c_float, C.c_int, P, C.c_int, P, P, C.c_int,
                                      C.POINTER(C.c_int), P, P, P, P, C.POINTER(InitializerResult)], C.c_int),
     "orbx_debug_acosf_det": ([C.c_float], C.c_float),
+    "orbx_debug_lm_step": ([P, P, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int], C.c_int),
     "orbx_debug_sim3_exp": ([P, P, C.c_int, P, C.c_int], C.c_int),
     "orbx_debug_log": ([P, C.c_int, P, C.c_int], C.c_int),
     "orbx_debug_acos": ([P, C.c_int, P, C.c_int], C.c_int),

@@ -2,8 +2,11 @@
 // control on the device.  k_ba_update / k_ba_restore (push, oplus, pop), the phase entry
 // (k_ba_lm_start; batched: k_ba_dmax_many + k_ba_lm_init_many), the per-trial verdict
 // (k_ba_lm_control, or fused with the errors in k_ba_errors_ctl), k_ba_lm_resume, k_ba_lm_final_many.
+// The verdict's Levenberg arithmetic (gain ratio, lambda update, trial budget, the _nBad rule) is
+// orbx_lm.h's lm::trial / lm::iteration_end, here with the once-rounded cube of oracle/localba.cpp.
 #pragma once
 #include "ba_linearize.h"
+#include "orbx_lm.h"
 
 namespace orbx {
 
@@ -170,10 +173,13 @@ __device__ __forceinline__ void k_ba_lm_init_body(const BaDev& D, int iterations
   LmState* L = const_cast<LmState*>(D.lm);
   const double a = fixed_sum_wave(D.scal + 8, D.nbe);
   if (threadIdx.x != 0) return;
-  L->lambda = 1e-5 * D.scal[3];
-  L->ni = 2;
+  lm::Step s;
+  lm::start(s, 1e-5 * D.scal[3]);
+  L->lambda = s.lambda;
+  L->ni = s.ni;
   L->currentChi = L->iniChi = a;
-  L->it = L->qmax = L->nBad = L->trials = 0;
+  L->nBad = s.nBad;
+  L->it = L->qmax = L->trials = 0;
   L->relin = 0;  // linearised by the entry launches
   L->rejected = 0;
   L->iterations = iterations;
@@ -264,37 +270,24 @@ __device__ __forceinline__ void k_ba_lm_control_body(const BaDev& D, DevStop sto
   const bool ok2 = D.scal[2] != 0.0;
   if (L->qmax == 0) L->iniChi = L->currentChi;
   L->trials++;
-  const double tempChi = ok2 ? b : 1.7976931348623157e308;
-  double rho = L->currentChi - tempChi;
-  double scale = ok2 ? u : 0.0;
-  scale += 1e-3;
-  rho /= scale;
-  if (rho > 0 && isfinite(tempChi)) {
-    double alpha = 1. - lm_cube(2 * rho - 1);
-    alpha = alpha < 2. / 3. ? alpha : 2. / 3.;
-    const double scaleFactor = 1. / 3. > alpha ? 1. / 3. : alpha;
-    L->lambda *= scaleFactor;
-    L->ni = 2;
-    L->currentChi = tempChi;
-  } else {
-    L->lambda *= L->ni;
-    L->ni *= 2;
-    if (ok2) L->rejected = 1;
-  }
-  L->qmax++;
-  if (rho < 0 && L->qmax < 10 && !st) {  // another trial of this iteration
+  // the shared step on a copy of the state's Levenberg fields (LmState's layout is the host's and the
+  // capture path's; rho lives for this call only).  Its min / max take the operands in std::min's and
+  // std::max's order, as the oracle does: should the cube overflow (rho beyond 1e102, i.e. an LM scale
+  // of exactly -1e-3) the factor is the oracle's 1/3, where this kernel's former operand order gave 2/3.
+  lm::Step s = {L->lambda, L->ni, L->currentChi, L->iniChi, 0.0, L->qmax, L->nBad};
+  const lm::Verdict v = lm::trial<lm::Cube::kRounded>(s, b, u, ok2);
+  L->lambda = s.lambda;
+  L->ni = s.ni;
+  L->currentChi = s.currentChi;
+  L->qmax = s.qmax;
+  if (!v.accept && ok2) L->rejected = 1;
+  if (v.go && !st) {  // another trial of this iteration
     L->relin = 0;
     return;
   }
   L->it++;
-  bool brk = L->qmax == 10 || rho == 0;
-  if (!brk) {
-    if ((L->iniChi - L->currentChi) * 1e3 < L->iniChi)
-      L->nBad++;
-    else
-      L->nBad = 0;
-    brk = L->nBad >= 3;
-  }
+  const bool brk = lm::iteration_end(s);
+  L->nBad = s.nBad;
   L->qmax = 0;
   const bool st2 = !brk && L->it < L->iterations && st;
   L->stopped = st || st2;

@@ -59,14 +59,6 @@ struct LmState {
   unsigned ticket;   // k_ba_errors_ctl: blocks of the current launch that have stored their partial
 };
 
-// rho's cube rounded once (std::pow(x, 3) in the reference; glibc's pow is
-// within 0.52 ulp): x^2 and x^2*x split exactly with fma, host and device alike
-__host__ __device__ inline double lm_cube(double x) {
-  const double p = x * x, pe = fma(x, x, -p);
-  const double c = p * x, ce = fma(p, x, -c);
-  return c + (ce + pe * x);
-}
-
 struct BaDev {
   int nc, np, ne;
   // cameras

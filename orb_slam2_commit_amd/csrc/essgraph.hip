@@ -21,8 +21,9 @@
 //                back substitution run on wave 0 (seven rows of a block row across lanes).  Entries
 //                outside the envelope are structural zeros and are skipped.  No MFMA: its fused
 //                accumulation would change the rounding.
-//   control      optimization_algorithm_levenberg.cpp as oracle/poseopt.cpp restates it, at
-//                7 (n - 1) unknowns, with the user's lambda_init.
+//   control      optimization_algorithm_levenberg.cpp as oracle/poseopt.cpp restates it (orbx_lm.h's
+//                Step, shared with the other Levenberg kernels), at 7 (n - 1) unknowns, with the user's
+//                lambda_init.
 // k_eg_finish    one thread per vertex (Scw_out, Tiw) and per map point (the correction).
 //
 // Everything is FP64 from basic IEEE operations (log_det / acos_det / exp_det / sincos_d), so the
@@ -137,8 +138,9 @@ struct Shared {
   double E[NW][29 * 7];  // per wave: the error and its 28 perturbations
   double J[NW][98];      // per wave: J0 | J1, [k][d] (k the error entry)
   double Ld[49], d[7];   // the factored diagonal block of the current block column
-  double lambda, ni, currentChi, iniChi, rho, chi0;
-  int qmax, accept, nbad_lm, go, term, trials, fails, fail, its;
+  Step lm;  // lambda, ni, currentChi, iniChi, rho, qmax, nBad (orbx_lm.h)
+  double chi0;
+  int accept, go, term, trials, fails, fail, its;
   long long t_lin, t_solve, t_update;  // phase times in wall_clock64 ticks (thread 0)
 };
 
@@ -417,7 +419,7 @@ __global__ __launch_bounds__(BS) void k_eg_lm(const Dev D) {
     S.trials = 0;
     S.fails = 0;
     S.its = 0;
-    S.currentChi = 0.0;
+    S.lm.currentChi = 0.0;
     S.chi0 = 0.0;
     S.t_lin = S.t_solve = S.t_update = 0;
   }
@@ -429,24 +431,20 @@ __global__ __launch_bounds__(BS) void k_eg_lm(const Dev D) {
     eg_assemble(D);
     if (tid == 0) {
       const double chi = lds_chain(D.chain, D.E, 1, 0.0, false);
-      S.currentChi = chi;
-      S.iniChi = chi;
+      S.lm.currentChi = chi;
+      S.lm.iniChi = chi;
       if (iter == 0) S.chi0 = chi;
       S.its++;
     }
     __syncthreads();
     if (tid == 0) S.t_lin += wall_clock64() - t0;
     if (tid == 0) {
-      if (iter == 0) {
-        S.lambda = D.lambda_init;  // setUserLambdaInit: computeLambdaInit returns the user's value
-        S.ni = 2;
-        S.nbad_lm = 0;
-      }
-      S.qmax = 0;
+      if (iter == 0) start(S.lm, D.lambda_init);  // setUserLambdaInit: computeLambdaInit returns the user's value
+      S.lm.qmax = 0;
     }
     __syncthreads();
     for (;;) {
-      const double lambda = S.lambda;
+      const double lambda = S.lm.lambda;
       t0 = tid == 0 ? wall_clock64() : 0;
       for (int q = tid; q < 8 * D.n; q += BS) D.bak[q] = D.est[q];  // push
       eg_factor(D, S, lambda);
@@ -482,30 +480,11 @@ __global__ __launch_bounds__(BS) void k_eg_lm(const Dev D) {
       __syncthreads();
       if (tid == 0) {
         S.trials++;
-        if (!ok2) {
-          S.fails++;
-          tempChi = 1.7976931348623157e308;
-        }
-        double rho = S.currentChi - tempChi;
-        double scale = ok2 ? lds_chain(D.chain, D.N, 1, 0.0, false) : 0.0;
-        scale += 1e-3;
-        rho /= scale;
-        if (rho > 0 && __builtin_isfinite(tempChi)) {
-          const double t3 = 2 * rho - 1;
-          double alpha = 1. - t3 * t3 * t3;
-          alpha = (2. / 3. < alpha) ? 2. / 3. : alpha;
-          S.lambda *= (1. / 3. < alpha) ? alpha : 1. / 3.;
-          S.ni = 2;
-          S.currentChi = tempChi;
-          S.accept = 1;
-        } else {
-          S.lambda *= S.ni;
-          S.ni *= 2;
-          S.accept = 0;  // pop
-        }
-        S.qmax++;
-        S.rho = rho;
-        S.go = (rho < 0 && S.qmax < 10);
+        if (!ok2) S.fails++;
+        const double scale = ok2 ? lds_chain(D.chain, D.N, 1, 0.0, false) : 0.0;
+        const Verdict v = trial<Cube::kProduct>(S.lm, tempChi, scale, ok2);
+        S.accept = v.accept;  // else: pop
+        S.go = v.go;
       }
       __syncthreads();
       if (!S.accept)
@@ -514,16 +493,7 @@ __global__ __launch_bounds__(BS) void k_eg_lm(const Dev D) {
       if (tid == 0) S.t_update += wall_clock64() - t0;
       if (!S.go) break;
     }
-    if (tid == 0) {
-      int term = 0;
-      if (S.qmax == 10 || S.rho == 0) term = 1;
-      else {
-        if ((S.iniChi - S.currentChi) * 1e3 < S.iniChi) S.nbad_lm++;
-        else S.nbad_lm = 0;
-        if (S.nbad_lm >= 3) term = 1;
-      }
-      S.term = term;
-    }
+    if (tid == 0) S.term = iteration_end(S.lm);
     __syncthreads();
     if (S.term) break;
   }
@@ -531,7 +501,7 @@ __global__ __launch_bounds__(BS) void k_eg_lm(const Dev D) {
     D.stats[0] = S.its;
     D.stats[1] = S.trials;
     D.stats[2] = S.chi0;
-    D.stats[3] = S.currentChi;
+    D.stats[3] = S.lm.currentChi;
     D.stats[4] = S.fails;
     D.stats[5] = (double)S.t_lin;
     D.stats[6] = (double)S.t_solve;

@@ -22,7 +22,8 @@
 // sets), four launches, one readback.
 //
 // Arithmetic: the OpenCV 3.2 calls restated operation by operation (parity), float and
-// double exactly where the library uses them, -ffp-contract=off; acos through acosf_det.  Every
+// double exactly where the library uses them, -ffp-contract=off; acos through acosf_det.  The Jacobi
+// SVD is orbx_cvsvd.h's, the template PnP instantiates at double.  Every
 // routine is __host__ __device__: orbx_debug_initializer_host runs the same code on the host.
 // tests/initializer_literal.py is the same sequence in numpy, and both equal it bit for bit.
 //
@@ -40,6 +41,7 @@
 
 #include "../../include/orbx.h"
 #include "../../include/orbx_debug.h"
+#include "orbx_cvsvd.h"
 #include "orbx_device.h"
 #include "orbx_ransac.h"
 
@@ -82,145 +84,9 @@ struct InitRt {  // one motion hypothesis of CheckRT
 };
 
 // ------------------------------------------------------------------ OpenCV 3.2 pieces
-// cv::RNG::next
-struct InitCvRng {
-  uint64_t state;
-  INIT_HD unsigned next() {
-    state = (uint64_t)(unsigned)state * 4164903690U + (unsigned)(state >> 32);
-    return (unsigned)state;
-  }
-};
-
-// JacobiSVDImpl_<float> (lapack.cpp, generic path; oracle/pnp.cpp restates the double instantiation):
-// At holds n rows of length m; on exit its first n1 rows are the left singular vectors (descending
-// W), Vt the right ones.  Vt == nullptr skips V's arithmetic only (nobody reads it): the control
-// flow is the one with a Vt.  minval = FLT_MIN, eps = 2 FLT_EPSILON.  w (may be null): (float)W.
-// The sizes and row strides are template arguments so that the element loops unroll (a row's LDS
-// loads issue together); the pair loops stay rolled.  The operation order is the library's.
-template <int m, int n, int n1, int astep, int vstep>
-INIT_HD void init_jsvd(float* At, double* W, float* w, float* Vt) {
-  const double minval = FLT_MIN;
-  const float eps = FLT_EPSILON * 2;
-  const int max_iter = m > 30 ? m : 30;
-  for (int i = 0; i < n; i++) {
-    double sd = 0;
-    _Pragma("unroll") for (int k = 0; k < m; k++) {
-      const float t = At[i * astep + k];
-      sd += (double)t * (double)t;
-    }
-    W[i] = sd;
-    if (Vt) {
-      _Pragma("unroll") for (int k = 0; k < n; k++) Vt[i * vstep + k] = 0;
-      Vt[i * vstep + i] = 1;
-    }
-  }
-  for (int iter = 0; iter < max_iter; iter++) {
-    bool changed = false;
-    for (int i = 0; i < n - 1; i++)
-      for (int j = i + 1; j < n; j++) {
-        float* Ai = At + i * astep;
-        float* Aj = At + j * astep;
-        double a = W[i], p = 0, b = W[j];
-        _Pragma("unroll") for (int k = 0; k < m; k++) p += (double)Ai[k] * (double)Aj[k];
-        if (__builtin_fabs(p) <= (double)eps * __builtin_sqrt(a * b)) continue;
-        p *= 2;
-        const double beta = a - b, gamma = __builtin_sqrt(p * p + beta * beta);
-        float c, s;
-        if (beta < 0) {
-          const double delta = (gamma - beta) * 0.5;
-          s = (float)__builtin_sqrt(delta / gamma);
-          c = (float)(p / (gamma * (double)s * 2));
-        } else {
-          c = (float)__builtin_sqrt((gamma + beta) / (gamma * 2));
-          s = (float)(p / (gamma * (double)c * 2));
-        }
-        a = b = 0;
-        _Pragma("unroll") for (int k = 0; k < m; k++) {
-          const float t0 = c * Ai[k] + s * Aj[k];
-          const float t1 = -s * Ai[k] + c * Aj[k];
-          Ai[k] = t0;
-          Aj[k] = t1;
-          a += (double)t0 * (double)t0;
-          b += (double)t1 * (double)t1;
-        }
-        W[i] = a;
-        W[j] = b;
-        changed = true;
-        if (Vt) {
-          float* Vi = Vt + i * vstep;
-          float* Vj = Vt + j * vstep;
-          _Pragma("unroll") for (int k = 0; k < n; k++) {
-            const float t0 = c * Vi[k] + s * Vj[k];
-            const float t1 = -s * Vi[k] + c * Vj[k];
-            Vi[k] = t0;
-            Vj[k] = t1;
-          }
-        }
-      }
-    if (!changed) break;
-  }
-  for (int i = 0; i < n; i++) {
-    double sd = 0;
-    _Pragma("unroll") for (int k = 0; k < m; k++) {
-      const float t = At[i * astep + k];
-      sd += (double)t * (double)t;
-    }
-    W[i] = __builtin_sqrt(sd);
-  }
-  for (int i = 0; i < n - 1; i++) {
-    int j = i;
-    for (int k = i + 1; k < n; k++)
-      if (W[j] < W[k]) j = k;
-    if (i != j) {
-      const double tw = W[i];
-      W[i] = W[j];
-      W[j] = tw;
-      _Pragma("unroll") for (int k = 0; k < m; k++) {
-        const float t = At[i * astep + k];
-        At[i * astep + k] = At[j * astep + k];
-        At[j * astep + k] = t;
-      }
-      if (Vt)
-        _Pragma("unroll") for (int k = 0; k < n; k++) {
-          const float t = Vt[i * vstep + k];
-          Vt[i * vstep + k] = Vt[j * vstep + k];
-          Vt[j * vstep + k] = t;
-        }
-    }
-  }
-  if (w)
-    for (int i = 0; i < n; i++) w[i] = (float)W[i];
-  InitCvRng rng{0x12345678};
-  for (int i = 0; i < n1; i++) {
-    double sd = i < n ? W[i] : 0;
-    for (int ii = 0; ii < 100 && sd <= minval; ii++) {
-      // a zero singular value: a +-1/m vector, projected off the earlier rows twice, normalised
-      const float val0 = (float)(1. / m);
-      _Pragma("unroll") for (int k = 0; k < m; k++) At[i * astep + k] = (rng.next() & 256) != 0 ? val0 : -val0;
-      for (int it = 0; it < 2; it++)
-        for (int j = 0; j < i; j++) {
-          sd = 0;
-          _Pragma("unroll") for (int k = 0; k < m; k++) sd += (double)(At[i * astep + k] * At[j * astep + k]);
-          float asum = 0;
-          _Pragma("unroll") for (int k = 0; k < m; k++) {
-            const float t = (float)((double)At[i * astep + k] - sd * (double)At[j * astep + k]);
-            At[i * astep + k] = t;
-            asum += __builtin_fabsf(t);
-          }
-          asum = asum > eps * 100.f ? 1 / asum : 0;
-          _Pragma("unroll") for (int k = 0; k < m; k++) At[i * astep + k] *= asum;
-        }
-      sd = 0;
-      _Pragma("unroll") for (int k = 0; k < m; k++) {
-        const float t = At[i * astep + k];
-        sd += (double)t * (double)t;
-      }
-      sd = __builtin_sqrt(sd);
-    }
-    const float s = (float)(sd > minval ? 1 / sd : 0.);
-    _Pragma("unroll") for (int k = 0; k < m; k++) At[i * astep + k] *= s;
-  }
-}
+// cv::SVD is orbx_cvsvd.h's JacobiSVDImpl_ at T = float (minval = FLT_MIN, eps = 2 FLT_EPSILON), always
+// in its rolled form (kSmall = false): the matrices are run-time indexed memory, LDS on the device.
+using cvsvd::jacobi_svd;
 
 // det3 (lapack.cpp) of a 3x3 CV_32F, in double
 INIT_HD double init_det3(const float* m) {
@@ -289,16 +155,15 @@ INIT_HD void init_svd3(const float* A, float* ws, double* W, float* u, float* w,
   float* V = ws + 9;
   for (int r = 0; r < 3; r++)
     for (int c = 0; c < 3; c++) B[3 * c + r] = A[3 * r + c];
-  float* wl = ws + 18;
-  init_jsvd<3, 3, 3, 3, 3>(B, W, wl, V);
+  jacobi_svd<float, 3, 3, 3, true, false>(B, W, V);
   for (int r = 0; r < 3; r++)
     for (int c = 0; c < 3; c++) {
       u[3 * r + c] = B[3 * c + r];
       vt[3 * r + c] = V[3 * r + c];
     }
-  for (int k = 0; k < 3; k++) w[k] = wl[k];
+  for (int k = 0; k < 3; k++) w[k] = (float)W[k];
 }
-constexpr int kInitSvd3Ws = 21;
+constexpr int kInitSvd3Ws = 21;  // 18 + 3 spare (the slices carved after it keep their offsets)
 
 // ------------------------------------------------------------------ hypotheses
 constexpr int kInitSolveWs = 9 * 16 + 81 + kInitSvd3Ws + 64;
@@ -324,7 +189,7 @@ INIT_HD void init_solve(const InitJob& J, int it, int model, float* ws, double* 
         At[16 * c + 2 * j + 1] = r1[c];
       }
     }
-    init_jsvd<16, 9, 0, 16, 9>(At, W, nullptr, Vt);
+    jacobi_svd<float, 16, 9, 0, true, false>(At, W, Vt);
     float Hn[9], P[9], H21[9], H12[9];
 #pragma unroll
     for (int k = 0; k < 9; k++) Hn[k] = Vt[72 + k];
@@ -343,7 +208,7 @@ INIT_HD void init_solve(const InitJob& J, int it, int model, float* ws, double* 
       for (int c = 0; c < 9; c++) At[9 * j + c] = r[c];
     }
     for (int c = 0; c < 9; c++) At[72 + c] = 0.f;  // temp_u = Scalar::all(0)
-    init_jsvd<9, 8, 9, 9, 9>(At, W, nullptr, nullptr);
+    jacobi_svd<float, 9, 8, 9, false, false>(At, W, nullptr);
     float* Fpre = tmp;
     for (int k = 0; k < 9; k++) Fpre[k] = At[72 + k];
     float u[9], w[3], vt[9];
@@ -667,7 +532,7 @@ INIT_HD int init_rt_point(const InitRt& C, float x1, float y1, float x2, float y
     At[4 * c + 2] = x2 == 1.f ? p22 - C.P2[c] : (p22 * x2 + C.P2[c] * -1.0f) + 0.0f;
     At[4 * c + 3] = y2 == 1.f ? p22 - C.P2[4 + c] : (p22 * y2 + C.P2[4 + c] * -1.0f) + 0.0f;
   }
-  init_jsvd<4, 4, 0, 4, 4>(At, W, nullptr, Vt);
+  jacobi_svd<float, 4, 4, 0, true, false>(At, W, Vt);
   const double iw = 1.0 / (double)Vt[15];
   X[0] = init_scale(Vt[12], iw);
   X[1] = init_scale(Vt[13], iw);

@@ -10,7 +10,7 @@
 //                   k_ba_point_schur, k_ba_lin_schur (the three point-side kernels fused)
 //   ba_schur.h      k_ba_pair_table, k_ba_pairs, k_ba_schur_fin, the trial's fold flags
 //   ba_ldlt.h       k_ba_ldlt / k_ba_ldlt_col / k_ba_ldlt_pan and LdltPlan
-//   ba_lm.h         k_ba_update, k_ba_restore, k_ba_lm_*, k_ba_errors_ctl
+//   ba_lm.h         k_ba_update, k_ba_restore, k_ba_lm_*, k_ba_errors_ctl (the Levenberg step: orbx_lm.h)
 //   ba_structure.h  k_ba_struct_*, k_ba_prep, k_ba_outliers, k_ba_export
 //   ba_capture.h    k_ba_capture_pre / _post: the test-only capture of one trial (orbx_debug.h)
 //   ba_host.h       struct LocalBA: buffers, phase structure, optimize_dev (one optimize() call)

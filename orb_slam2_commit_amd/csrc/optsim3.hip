@@ -12,7 +12,8 @@
 // the 28 upper H entries, the 7 b entries) are taken in that order, one FP64 chain per entry on its
 // own lane over LDS-staged per-edge terms, chunk by chunk (the result does not depend on the chunk
 // size: a chain carries across chunks).  With exp_det / sincos_d for g2o::Sim3's exp and the shared
-// Eigen-LDLT restatement at N = 7 (orbx_lm.h) the kernel reproduces tests/optsim3_literal.py bit for bit.
+// Eigen-LDLT restatement at N = 7 and Levenberg step (orbx_lm.h; the literal's lm_trial /
+// lm_iteration_end are its twin) the kernel reproduces tests/optsim3_literal.py bit for bit.
 //
 // Bound: latency (dependent FP64 chains of length 2n per LM iteration and trial; the serial 7x7
 // solve and Sim3 exp on one lane); throughput comes from problems in flight.  Algorithmic bytes per
@@ -99,8 +100,8 @@ struct Shared {
   Pair pert[15];  // [0] the estimate; [1 + 2d], [2 + 2d]: oplus(+delta e_d), oplus(-delta e_d)
   Pair trial;
   double H[49], b[7], x[7];
-  double lambda, ni, currentChi, iniChi, rho;
-  int qmax, ok2, nbad_lm, go, term, trials;
+  Step lm;  // lambda, ni, currentChi, iniChi, rho, qmax, nBad (orbx_lm.h)
+  int ok2, go, term, trials;
   int scan[BS / 64];
 };
 
@@ -196,34 +197,21 @@ __global__ __launch_bounds__(BS) void k_optimize_sim3(const Dev* __restrict__ pr
         }
         if (wid == 0 && lane < kTerm) {
           if (lane < 28) {
-            int r = 0, c = lane;
-            while (c >= 7 - r) {
-              c -= 7 - r;
-              r++;
-            }
-            c += r;
+            int r, c;
+            tri_rc<7>(lane, r, c);
             S.H[7 * r + c] = acc;
             S.H[7 * c + r] = acc;
           } else if (lane < 35) {
             S.b[lane - 28] = acc;
           } else {
-            S.currentChi = acc;
-            S.iniChi = acc;
+            S.lm.currentChi = acc;
+            S.lm.iniChi = acc;
           }
         }
         __syncthreads();
         if (tid == 0) {
-          if (iter == 0) {
-            double m = 0;
-            for (int j = 0; j < 7; j++) {
-              const double a = __builtin_fabs(S.H[8 * j]);
-              m = (a < m) ? m : a;  // std::max(|H_jj|, m)
-            }
-            S.lambda = 1e-5 * m;
-            S.ni = 2;
-            S.nbad_lm = 0;
-          }
-          S.qmax = 0;
+          if (iter == 0) start(S.lm, lambda_init<7>(S.H));
+          S.lm.qmax = 0;
         }
         __syncthreads();
         // ---- trials ----
@@ -234,7 +222,7 @@ __global__ __launch_bounds__(BS) void k_optimize_sim3(const Dev* __restrict__ pr
 #pragma unroll
             for (int j = 0; j < 49; j++) Hd[j] = S.H[j];
 #pragma unroll
-            for (int j = 0; j < 7; j++) Hd[8 * j] += S.lambda;
+            for (int j = 0; j < 7; j++) Hd[8 * j] += S.lm.lambda;
             double x[7];
             const bool ok2 = ldlt<7>(Hd, S.b, x);
             S.ok2 = ok2;
@@ -268,42 +256,17 @@ __global__ __launch_bounds__(BS) void k_optimize_sim3(const Dev* __restrict__ pr
           }
           if (tid == 0) {
             const bool ok2 = S.ok2;
-            if (!ok2) tempChi = 1.7976931348623157e308;
-            double rho = S.currentChi - tempChi;
             double scale = 0.0;
             if (ok2)
-              for (int j = 0; j < 7; j++) scale += S.x[j] * (S.lambda * S.x[j] + S.b[j]);
-            scale += 1e-3;
-            rho /= scale;
-            if (rho > 0 && __builtin_isfinite(tempChi)) {
-              const double t3 = 2 * rho - 1;
-              double alpha = 1. - t3 * t3 * t3;
-              alpha = (2. / 3. < alpha) ? 2. / 3. : alpha;     // std::min(alpha, 2/3)
-              S.lambda *= (1. / 3. < alpha) ? alpha : 1. / 3.;  // std::max(1/3, alpha)
-              S.ni = 2;
-              S.currentChi = tempChi;
-            } else {
-              S.lambda *= S.ni;
-              S.ni *= 2;
-              S.S = S.bak;  // pop; the rejected trial's errors stay in the edges
-            }
-            S.qmax++;
-            S.rho = rho;
-            S.go = (rho < 0 && S.qmax < 10);
+              for (int j = 0; j < 7; j++) scale += S.x[j] * (S.lm.lambda * S.x[j] + S.b[j]);
+            const Verdict v = trial<Cube::kProduct>(S.lm, tempChi, scale, ok2);
+            if (!v.accept) S.S = S.bak;  // pop; the rejected trial's errors stay in the edges
+            S.go = v.go;
           }
           __syncthreads();
           if (!S.go) break;
         }
-        if (tid == 0) {
-          int term = 0;
-          if (S.qmax == 10 || S.rho == 0) term = 1;
-          else {
-            if ((S.iniChi - S.currentChi) * 1e3 < S.iniChi) S.nbad_lm++;
-            else S.nbad_lm = 0;
-            if (S.nbad_lm >= 3) term = 1;
-          }
-          S.term = term;
-        }
+        if (tid == 0) S.term = iteration_end(S.lm);
         __syncthreads();
         if (S.term) break;
       }
@@ -324,17 +287,9 @@ __global__ __launch_bounds__(BS) void k_optimize_sim3(const Dev* __restrict__ pr
         keep = !(c12 > th2 || c21 > th2);
         if (!keep) P.inlier[i] = 0;
       }
-      const uint64_t m = __ballot(keep);
-      const int pre = __popcll(m & ((1ull << lane) - 1));
-      if (lane == 0) S.scan[wid] = __popcll(m);
-      __syncthreads();  // every act[k] of this chunk has been read
-      int off = base;
-      for (int w = 0; w < wid; w++) off += S.scan[w];
-      if (keep && phase == 0) act[off + pre] = i;
-      int tot = 0;
-      for (int w = 0; w < BS / 64; w++) tot += S.scan[w];
-      base += tot;
-      __syncthreads();
+      compact_chunk<BS>(keep, S.scan, base, [&](int slot) {
+        if (phase == 0) act[slot] = i;  // (the second pass only counts)
+      });
     }
     __threadfence_block();
     __syncthreads();
@@ -509,6 +464,24 @@ extern "C" orbx_status orbx_optimize_sim3_device(const orbx_optimize_sim3_proble
 }
 
 // ------------------------------------------------------------------ debug probes (orbx_debug.h)
+extern "C" int orbx_debug_lm_step(double state[5], int counts[2], double tempChi, double scale, int ok2,
+                                  int cube_kind, int ops) {  // the host build of orbx_lm.h's step
+  if (!state || !counts || cube_kind < 0 || cube_kind > 1 || ops < 1 || ops > 3) return ORBX_ERR_ARG;
+  namespace lm = orbx::lm;
+  lm::Step s = {state[0], state[1], state[2], state[3], state[4], counts[0], counts[1]};
+  int r = 0;
+  if (ops & 1) {
+    const lm::Verdict v = cube_kind ? lm::trial<lm::Cube::kRounded>(s, tempChi, scale, ok2 != 0)
+                                    : lm::trial<lm::Cube::kProduct>(s, tempChi, scale, ok2 != 0);
+    r |= (v.accept ? 1 : 0) | (v.go ? 2 : 0);
+  }
+  if ((ops & 2) && lm::iteration_end(s)) r |= 4;
+  state[0] = s.lambda; state[1] = s.ni; state[2] = s.currentChi; state[3] = s.iniChi; state[4] = s.rho;
+  counts[0] = s.qmax;
+  counts[1] = s.nBad;
+  return r;
+}
+
 extern "C" int orbx_debug_exp(const double* x, int n, double* y, int device) {
   if (n < 0 || (n > 0 && (!x || !y))) return ORBX_ERR_ARG;
   const orbx_status dv = pick_device(device);

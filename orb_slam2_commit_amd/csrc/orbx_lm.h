@@ -1,6 +1,9 @@
 // orbx_lm.h -- the device pieces the single-vertex g2o Levenberg kernels share (poseopt.hip's SE3
 // vertex, optsim3.hip's Sim3 vertex): Eigen's quaternion product / rotation / matrix conversions and
-// the Eigen::LDLT<MatrixXd> restatement of oracle/poseopt.cpp, as a template on the system size.
+// the Eigen::LDLT<MatrixXd> restatement of oracle/poseopt.cpp, as a template on the system size;
+// and the Levenberg step itself (lm::Step, start / trial / iteration_end), which essgraph.hip's pose
+// graph and LocalBA's device control (ba_lm.h) run too, with the upper-triangle scatter and the ordered
+// block compaction of the single-vertex kernels.
 // The operation sequences are the oracle's; nothing here may be re-associated.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -244,6 +247,123 @@ __device__ __forceinline__ double lds_chain(const double* base, int m, int st, d
   }
   for (int k = m8; k < m; k++) s = sub ? s - base[k * st] : s + base[k * st];
   return s;
+}
+
+// ------------------------------------------------------------------------------------------------
+// g2o's OptimizationAlgorithmLevenberg::solve, once: the scalar state, the start, a trial's verdict
+// and the iteration-end rule.  k_pose_optimization, k_optimize_sim3 and k_eg_lm keep a Step in LDS and
+// thread 0 calls these; LocalBA's k_ba_lm_control_body (ba_lm.h) runs them on a copy of its LmState's
+// fields.  Host and device alike (orbx_debug_lm_step runs the host build; tests/test_lm_step.py holds
+// it to the literals' lm_trial / lm_iteration_end bit for bit).
+struct Step {
+  double lambda, ni, currentChi, iniChi, rho;
+  int qmax, nBad;
+};
+
+// optimize()'s first iteration: lambda0 is computeLambdaInit's value
+__host__ __device__ __forceinline__ void start(Step& s, double lambda0) {
+  s.lambda = lambda0;
+  s.ni = 2;
+  s.nBad = 0;
+}
+// computeLambdaInit without a user value: tau * max|H_jj| over an N x N row-major H
+template <int N>
+__host__ __device__ __forceinline__ double lambda_init(const double* H) {
+  double m = 0;
+  for (int j = 0; j < N; j++) {
+    const double a = __builtin_fabs(H[(N + 1) * j]);
+    m = (a < m) ? m : a;  // std::max(|H_jj|, m)
+  }
+  return 1e-5 * m;
+}
+
+// The (2 rho - 1)^3 of the accepted trial's scale factor, as each yardstick computes it.  The two are
+// NOT the same function and may not be merged: they differ in the last bit for more than a quarter of
+// the arguments, and each kernel equals its own yardstick bit for bit.
+//   cube_product: the plain product.  oracle/poseopt.cpp (PoseOptimization), tests/optsim3_literal.py
+//                 (OptimizeSim3) and tests/essgraph_literal.py (OptimizeEssentialGraph) write
+//                 t3 * t3 * t3, two roundings.
+//   cube_rounded: the cube rounded once.  oracle/localba.cpp (LocalBundleAdjustment) calls
+//                 std::pow(x, 3) as g2o does (glibc's pow is within an ulp of it): x^2 and x^2 * x split
+//                 exactly with fma, host and device alike.
+enum class Cube { kProduct, kRounded };
+__host__ __device__ __forceinline__ double cube_product(double x) { return x * x * x; }
+__host__ __device__ __forceinline__ double cube_rounded(double x) {
+  const double p = x * x, pe = __builtin_fma(x, x, -p);
+  const double c = p * x, ce = __builtin_fma(p, x, -c);
+  return c + (ce + pe * x);
+}
+
+struct Verdict {
+  bool accept;  // the trial's state stays (else: pop)
+  bool go;      // another trial of this iteration follows
+};
+// One trial's verdict.  tempChi: activeRobustChi2 at the trial state; scale: sum x_j (lambda x_j + b_j);
+// ok2: the solve succeeded (else both are replaced, as in the reference).
+template <Cube kCube>
+__host__ __device__ __forceinline__ Verdict trial(Step& s, double tempChi, double scale, bool ok2) {
+  if (!ok2) {
+    tempChi = 1.7976931348623157e308;  // std::numeric_limits<double>::max()
+    scale = 0.0;
+  }
+  double rho = s.currentChi - tempChi;
+  scale += 1e-3;
+  rho /= scale;
+  const bool accept = rho > 0 && __builtin_isfinite(tempChi);
+  if (accept) {
+    const double t3 = 2 * rho - 1;
+    double alpha = 1. - (kCube == Cube::kRounded ? cube_rounded(t3) : cube_product(t3));
+    alpha = (2. / 3. < alpha) ? 2. / 3. : alpha;     // std::min(alpha, 2/3)
+    s.lambda *= (1. / 3. < alpha) ? alpha : 1. / 3.;  // std::max(1/3, alpha)
+    s.ni = 2;
+    s.currentChi = tempChi;
+  } else {
+    s.lambda *= s.ni;
+    s.ni *= 2;
+  }
+  s.qmax++;
+  s.rho = rho;
+  return {accept, rho < 0 && s.qmax < 10};
+}
+// After an iteration's last trial: true when optimize() stops (the trial budget, rho == 0, or the
+// third iteration in a row that gained less than a thousandth of its starting chi)
+__host__ __device__ __forceinline__ bool iteration_end(Step& s) {
+  if (s.qmax == 10 || s.rho == 0) return true;
+  if ((s.iniChi - s.currentChi) * 1e3 < s.iniChi) s.nBad++;
+  else s.nBad = 0;
+  return s.nBad >= 3;
+}
+
+// entry q of an N x N upper triangle stored row by row (c >= r): its row and column
+template <int N>
+__host__ __device__ __forceinline__ void tri_rc(int q, int& r, int& c) {
+  r = 0;
+  c = q;
+  while (c >= N - r) {
+    c -= N - r;
+    r++;
+  }
+  c += r;
+}
+
+// Ordered compaction of one chunk of kBS items (one per thread, every thread of the block calls):
+// thread tid's kept item goes to slot base + (the kept items of lower threads); put(slot) stores it.
+// base advances by the chunk's kept count.  A slot never lies above the item's own position in the
+// list, so a caller may compact in place.  scan: kBS / 64 ints of LDS.
+template <int kBS, class Put>
+__device__ __forceinline__ void compact_chunk(bool keep, int* scan, int& base, Put put) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const uint64_t m = __ballot(keep);
+  const int pre = __popcll(m & ((1ull << lane) - 1));
+  if (lane == 0) scan[wid] = __popcll(m);
+  __syncthreads();  // (every item of this chunk has been read by now)
+  int off = base;
+  for (int w = 0; w < wid; w++) off += scan[w];
+  if (keep) put(off + pre);
+  int tot = 0;
+  for (int w = 0; w < kBS / 64; w++) tot += scan[w];
+  base += tot;
+  __syncthreads();
 }
 
 }  // namespace lm

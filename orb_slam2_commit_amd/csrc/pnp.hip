@@ -16,8 +16,8 @@
 // (:182-301) including its `mnIterations<maxIts || nCurrent<nIterations` loop condition.
 // orbx_pnp_iterate is that path with one run, its whole H as the first chunk.
 //
-// EPnP and the OpenCV 3.2 helpers it calls (cvMulTransposed, Jacobi cvSVD,
-// cvInvert/cvSolve through SVBkSb) use only IEEE + - * / sqrt in the same
+// EPnP and the OpenCV 3.2 helpers it calls (cvMulTransposed; Jacobi cvSVD and
+// cvInvert/cvSolve through SVBkSb, both in orbx_cvsvd.h) use only IEEE + - * / sqrt in the same
 // order as the oracle, with every reduction sequential in the reference's
 // order, so poses and masks are bit-identical to the CPU restatement.  The
 // parallelism is only where it cannot change a bit: per-point terms, the
@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "../../include/orbx.h"
+#include "orbx_cvsvd.h"
 #include "orbx_ransac.h"
 
 namespace orbx {
@@ -51,308 +52,9 @@ struct PnpIn {
 };
 
 // ------------------------------------------------------------ OpenCV 3.2 math
-struct CvRng {
-  unsigned long long state;
-  __device__ unsigned next() {
-    state = (unsigned long long)(unsigned)state * 4164903690U + (unsigned)(state >> 32);
-    return (unsigned)state;
-  }
-};
-
-__device__ inline void swap_d(double& a, double& b) {
-  const double t = a;
-  a = b;
-  b = t;
-}
-
-// JacobiSVDImpl_<double> (see oracle/pnp.cpp) on N rows of length M in At
-// (row stride M), n1 = N.  Sizes are compile-time so the small systems live
-// in registers; kV = false skips the V rotations -- they never feed back into
-// At or W, so U and W are unchanged (EPnP's 12x12 SVD only reads Ut).
-// One Jacobi rotation of rows i < j (At row stride M, W the squared row
-// norms); returns false when the pair is already orthogonal (skipped).
-template <int M, int N, bool kV>
-__device__ __forceinline__ bool jacobi_rotate(double* At, double* W, double* Vt, int i, int j) {
-  const double eps = DBL_EPSILON * 10;
-  double* Ai = At + i * M;
-  double* Aj = At + j * M;
-  double a = W[i], p = 0, b = W[j];
-  double xi[M], xj[M];
-#pragma unroll
-  for (int k = 0; k < M; k++) {
-    xi[k] = Ai[k];
-    xj[k] = Aj[k];
-  }
-#pragma unroll
-  for (int k = 0; k < M; k++) p += xi[k] * xj[k];
-  if (fabs(p) <= eps * sqrt(a * b)) return false;
-  p *= 2;
-  const double beta = a - b, gamma = sqrt(p * p + beta * beta);
-  double c, s;
-  if (beta < 0) {
-    const double delta = (gamma - beta) * 0.5;
-    s = sqrt(delta / gamma);
-    c = p / (gamma * s * 2);
-  } else {
-    c = sqrt((gamma + beta) / (gamma * 2));
-    s = p / (gamma * c * 2);
-  }
-  a = b = 0;
-#pragma unroll
-  for (int k = 0; k < M; k++) {
-    const double t0 = c * xi[k] + s * xj[k];
-    const double t1 = -s * xi[k] + c * xj[k];
-    Ai[k] = t0;
-    Aj[k] = t1;
-    a += t0 * t0;
-    b += t1 * t1;
-  }
-  W[i] = a;
-  W[j] = b;
-  if (kV) {
-    double* Vi = Vt + i * N;
-    double* Vj = Vt + j * N;
-#pragma unroll
-    for (int k = 0; k < N; k++) {
-      const double t0 = c * Vi[k] + s * Vj[k];
-      const double t1 = -s * Vi[k] + c * Vj[k];
-      Vi[k] = t0;
-      Vj[k] = t1;
-    }
-  }
-  return true;
-}
-
-// After the sweeps: singular values, descending sort (rows of At and Vt
-// swapped along), and the cv::RNG(0x12345678) completion of null rows.
-template <int M, int N, bool kV, bool kSmall>
-__device__ __forceinline__ void jacobi_tail(double* At, double* W, double* Wout, double* Vt) {
-  const double minval = DBL_MIN, eps = DBL_EPSILON * 10;
-#pragma unroll
-  for (int i = 0; i < N; i++) {
-    double sd = 0;
-#pragma unroll
-    for (int k = 0; k < M; k++) {
-      const double t = At[i * M + k];
-      sd += t * t;
-    }
-    W[i] = sqrt(sd);
-  }
-#pragma unroll
-  for (int i = 0; i < N - 1; i++) {
-    int j = i;
-#pragma unroll
-    for (int k = i + 1; k < N; k++)
-      if (W[j] < W[k]) j = k;
-    if (i != j) {
-      if constexpr (kSmall) {  // W[j] with j runtime: select chains keep W in registers
-        double wj = W[i];
-#pragma unroll
-        for (int k = i + 1; k < N; k++)
-          if (k == j) wj = W[k];
-#pragma unroll
-        for (int k = i + 1; k < N; k++)
-          if (k == j) W[k] = W[i];
-        W[i] = wj;
-      } else {
-        swap_d(W[i], W[j]);
-      }
-      if constexpr (kSmall) {  // rows of register arrays: swap with every candidate row under a
-                               // select (static indices), never a runtime-indexed (scratch) access
-#pragma unroll
-        for (int r = i + 1; r < N; r++) {
-          const bool sw = r == j;
-#pragma unroll
-          for (int k = 0; k < M; k++) {
-            const double a = At[i * M + k], b = At[r * M + k];
-            At[i * M + k] = sw ? b : a;
-            At[r * M + k] = sw ? a : b;
-          }
-          if (kV) {
-#pragma unroll
-            for (int k = 0; k < N; k++) {
-              const double a = Vt[i * N + k], b = Vt[r * N + k];
-              Vt[i * N + k] = sw ? b : a;
-              Vt[r * N + k] = sw ? a : b;
-            }
-          }
-        }
-      } else {
-#pragma unroll
-        for (int k = 0; k < M; k++) swap_d(At[i * M + k], At[j * M + k]);
-        if (kV) {
-#pragma unroll
-          for (int k = 0; k < N; k++) swap_d(Vt[i * N + k], Vt[j * N + k]);
-        }
-      }
-    }
-  }
-  if (kSmall) {
-#pragma unroll
-    for (int i = 0; i < N; i++) Wout[i] = W[i];
-  }
-  CvRng rng{0x12345678};
-#pragma unroll
-  for (int i = 0; i < N; i++) {
-    double sd = W[i];
-    for (int ii = 0; ii < 100 && sd <= minval; ii++) {
-      const double val0 = 1. / M;
-#pragma unroll
-      for (int k = 0; k < M; k++) At[i * M + k] = (rng.next() & 256) != 0 ? val0 : -val0;
-      for (int iter = 0; iter < 2; iter++)
-        for (int j = 0; j < i; j++) {
-          sd = 0;
-#pragma unroll
-          for (int k = 0; k < M; k++) sd += At[i * M + k] * At[j * M + k];
-          double asum = 0;
-#pragma unroll
-          for (int k = 0; k < M; k++) {
-            const double t = At[i * M + k] - sd * At[j * M + k];
-            At[i * M + k] = t;
-            asum += fabs(t);
-          }
-          asum = asum > eps * 100 ? 1 / asum : 0;
-#pragma unroll
-          for (int k = 0; k < M; k++) At[i * M + k] *= asum;
-        }
-      sd = 0;
-#pragma unroll
-      for (int k = 0; k < M; k++) {
-        const double t = At[i * M + k];
-        sd += t * t;
-      }
-      sd = sqrt(sd);
-    }
-    const double s = sd > minval ? 1 / sd : 0.;
-#pragma unroll
-    for (int k = 0; k < M; k++) At[i * M + k] *= s;
-  }
-}
-
-// JacobiSVDImpl_<double> (see oracle/pnp.cpp) on N rows of length M in At
-// (row stride M), n1 = N, one thread.  Sizes are compile-time so the small
-// systems live in registers; kV = false skips the V rotations -- they never
-// feed back into At or W, so U and W are unchanged.
-template <int M, int N, bool kV>
-__device__ __forceinline__ void jacobi_svd(double* At, double* Wout, double* Vt) {
-  constexpr bool kSmall = N <= 6;  // else W works in Wout and the pair loops stay rolled
-  double Wreg[kSmall ? N : 1];
-  double* W = kSmall ? Wreg : Wout;
-  constexpr int max_iter = M > 30 ? M : 30;
-#pragma unroll
-  for (int i = 0; i < N; i++) {
-    double sd = 0;
-#pragma unroll
-    for (int k = 0; k < M; k++) {
-      const double t = At[i * M + k];
-      sd += t * t;
-    }
-    W[i] = sd;
-    if (kV) {
-#pragma unroll
-      for (int k = 0; k < N; k++) Vt[i * N + k] = 0;
-      Vt[i * N + i] = 1;
-    }
-  }
-  for (int iter = 0; iter < max_iter; iter++) {
-    bool changed = false;
-    if constexpr (kSmall) {
-#pragma unroll
-      for (int i = 0; i < N - 1; i++)
-#pragma unroll
-        for (int j = i + 1; j < N; j++) changed |= jacobi_rotate<M, N, kV>(At, W, Vt, i, j);
-    } else {
-#pragma unroll 1
-      for (int i = 0; i < N - 1; i++)
-#pragma unroll 1
-        for (int j = i + 1; j < N; j++) changed |= jacobi_rotate<M, N, kV>(At, W, Vt, i, j);
-    }
-    if (!changed) break;
-  }
-  jacobi_tail<M, N, kV, kSmall>(At, W, Wout, Vt);
-}
-
-// The same SVD (no V) run by one wave on LDS data: rotation (i, j) only
-// touches rows i, j, and in the cyclic order each row's rotations come in
-// increasing i + j, so step t = i + j runs every pair (lane i, t - i) at once
-// -- disjoint rows, each row's rotations in the reference order, so the
-// result is bit-identical -- 2N-3 steps per sweep instead of N(N-1)/2.  The
-// sort and null-row completion stay on lane 0.
-template <int M, int N>
-__device__ __forceinline__ void jacobi_svd_wave(double* At, double* W) {
-  constexpr int max_iter = M > 30 ? M : 30;
-  const int lane = threadIdx.x & 63;
-  if (lane < N) {
-    double sd = 0;
-#pragma unroll
-    for (int k = 0; k < M; k++) {
-      const double t = At[lane * M + k];
-      sd += t * t;
-    }
-    W[lane] = sd;
-  }
-  __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): LDS writes visible wave-wide
-  __builtin_amdgcn_wave_barrier();
-  for (int iter = 0; iter < max_iter; iter++) {
-    bool changed = false;
-    for (int t = 1; t <= 2 * N - 3; t++) {
-      const int j = t - lane;
-      if (lane < j && j < N) changed |= jacobi_rotate<M, N, false>(At, W, nullptr, lane, j);
-      __builtin_amdgcn_s_waitcnt(0xC07F);
-      __builtin_amdgcn_wave_barrier();
-    }
-    if (__ballot(changed) == 0) break;
-  }
-  if (lane == 0) jacobi_tail<M, N, false, false>(At, W, W, nullptr);
-  __builtin_amdgcn_s_waitcnt(0xC07F);
-  __builtin_amdgcn_wave_barrier();
-}
-
-// _SVDcompute, m >= n: left singular vectors as rows Ut (n x m), w, Vt.
-template <int M, int N, bool kV = true>
-__device__ __forceinline__ void svd_rows(const double* A, double* Ut, double* w, double* Vt) {
-#pragma unroll
-  for (int i = 0; i < N; i++)
-#pragma unroll
-    for (int k = 0; k < M; k++) Ut[i * M + k] = A[k * N + i];
-  jacobi_svd<M, N, kV>(Ut, w, Vt);
-}
-
-// SVBkSbImpl_ (kInv: b = identity, i.e. the inverse)
-template <int M, int N, bool kInv>
-__device__ __forceinline__ void svd_backsubst(const double* Ut, const double* w, const double* Vt, const double* b, double* x) {
-  constexpr int nb = kInv ? M : 1;
-#pragma unroll
-  for (int i = 0; i < N * nb; i++) x[i] = 0;
-  double threshold = 0;
-#pragma unroll
-  for (int i = 0; i < N; i++) threshold += w[i];
-  threshold *= DBL_EPSILON * 2;
-#pragma unroll
-  for (int i = 0; i < N; i++) {
-    double wi = w[i];
-    if (fabs(wi) <= threshold) continue;
-    wi = 1 / wi;
-    const double* u = Ut + i * M;
-    const double* v = Vt + i * N;
-    if (!kInv) {
-      double s = 0;
-#pragma unroll
-      for (int j = 0; j < M; j++) s += u[j] * b[j];
-      s *= wi;
-#pragma unroll
-      for (int j = 0; j < N; j++) x[j] = x[j] + s * v[j];
-    } else {
-      double buffer[nb];
-#pragma unroll
-      for (int j = 0; j < nb; j++) buffer[j] = u[j] * wi;
-#pragma unroll
-      for (int j = 0; j < N; j++)
-#pragma unroll
-        for (int k = 0; k < nb; k++) x[j * nb + k] += buffer[k] * v[j];
-    }
-  }
-}
+// cvSVD / cvInvert / cvSolve: orbx_cvsvd.h's Jacobi SVD and back substitution at T = double.  The small
+// systems (N <= 6) live in registers (kSmall); the 12x12 runs on a wave in LDS (jacobi_svd_wave).
+using namespace cvsvd;
 
 __device__ inline double dot3(const double* a, const double* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
 __device__ inline double dist2(const double* p1, const double* p2) {
@@ -363,7 +65,7 @@ __device__ inline double dist2(const double* p1, const double* p2) {
 template <int K>
 __device__ __forceinline__ void solve6(const double* L, const double* rho, double* x) {
   double ut[6 * K], w[K], vt[K * K];
-  svd_rows<6, K>(L, ut, w, vt);
+  svd_rows<double, 6, K, true, true>(L, ut, w, vt);
   svd_backsubst<6, K, false>(ut, w, vt, rho, x);
 }
 
@@ -604,7 +306,7 @@ __device__ __forceinline__ void epnp_compute_pose(const PnpIn& in, const EpnpPts
     P9[6] = P9[2];
     P9[7] = P9[5];
     double uct[9], dc[3], vt[9];
-    svd_rows<3, 3>(P9, uct, dc, vt);
+    svd_rows<double, 3, 3, true, true>(P9, uct, dc, vt);
 #pragma unroll
     for (int i = 1; i < 4; i++) {
       const double k = sqrt(dc[i - 1] / n);
@@ -616,7 +318,7 @@ __device__ __forceinline__ void epnp_compute_pose(const PnpIn& in, const EpnpPts
     for (int i = 0; i < 3; i++)
 #pragma unroll
       for (int j = 1; j < 4; j++) cc[3 * i + j - 1] = S->cws[j][i] - S->cws[0][i];
-    svd_rows<3, 3>(cc, ut, w, vt);
+    svd_rows<double, 3, 3, true, true>(cc, ut, w, vt);
     svd_backsubst<3, 3, true>(ut, w, vt, nullptr, ci);
 #pragma unroll
     for (int e = 0; e < 9; e++) S->ci[e] = ci[e];
@@ -684,7 +386,7 @@ __device__ __forceinline__ void epnp_compute_pose(const PnpIn& in, const EpnpPts
     }
     __builtin_amdgcn_s_waitcnt(0xC07F);
     __builtin_amdgcn_wave_barrier();
-    jacobi_svd_wave<12, 12>(S->ut, S->d);
+    jacobi_svd_wave<double, 12, 12>(S->ut, S->d);
   }
   __syncthreads();
   if (tid == 0) {
@@ -765,7 +467,7 @@ __device__ __forceinline__ void epnp_compute_pose(const PnpIn& in, const EpnpPts
         double abt[9], ut[9], w[3], vt[9], U[9], V[9];
 #pragma unroll
         for (int e = 0; e < 9; e++) abt[e] = S->abt_ap[ap][e];
-        svd_rows<3, 3>(abt, ut, w, vt);
+        svd_rows<double, 3, 3, true, true>(abt, ut, w, vt);
 #pragma unroll
         for (int i = 0; i < 3; i++)
 #pragma unroll

@@ -10,9 +10,10 @@
 // in edge insertion order (activeRobustChi2, buildSystem's H and b) are then
 // taken in exactly that order, one FP64 chain per H/b entry on its own lane,
 // from contiguous scratch rows.  With the deterministic sin/cos of
-// SE3Quat::exp and the same Eigen-LDLT restatement as the oracle
-// (oracle/poseopt.cpp), the GPU reproduces the oracle bit for bit: pose, outlier
-// flags, return value and per-round iteration counts.
+// SE3Quat::exp and the same Eigen-LDLT restatement and Levenberg step as the
+// oracle (oracle/poseopt.cpp; both in orbx_lm.h, shared with optsim3.hip), the
+// GPU reproduces the oracle bit for bit: pose, outlier flags, return value and
+// per-round iteration counts.
 //
 // Bound: latency (dependent FP64 chains of length n per LM iteration, ~10
 // cycles per link); throughput comes from thousands of frames in flight.
@@ -32,7 +33,7 @@
 namespace orbx {
 namespace pose {
 
-using namespace lm;  // Quat, qmul, qrot, qmat, mat2q, qnormalize, ldlt<N>, lds_chain
+using namespace lm;  // Quat, qmul, qrot, qmat, mat2q, qnormalize, ldlt<N>, lds_chain, the Levenberg Step
 
 constexpr int PBS = 256;
 constexpr int kRow = 32;  // scratch doubles per edge: 27 terms | err[3] | chi term | pad
@@ -193,8 +194,8 @@ constexpr int kChiCh = kCh * kTs;  // chi terms per trial pass (one double each)
 struct Shared {
   SE3 T, T0, bak;
   double H[36], b[6], x[6];
-  double lambda, ni, currentChi, iniChi, tempChi, rho;
-  int nact, qmax, ok2, nbad_lm, go, term, robust, nbad_cls;
+  Step lm;  // lambda, ni, currentChi, iniChi, rho, qmax, nBad (orbx_lm.h)
+  int ok2, go, term, robust, nbad_cls;
   int scan[PBS / 64];
 };
 
@@ -253,18 +254,7 @@ __global__ __launch_bounds__(PBS) void k_pose_optimization(const PoseDev* __rest
     int base = 0;
     for (int c0 = 0; c0 < n; c0 += PBS) {
       const int i = c0 + tid;
-      const int a = (i < n && !P.outlier[i]) ? 1 : 0;
-      const uint64_t m = __ballot(a);
-      const int pre = __popcll(m & ((1ull << lane) - 1));
-      if (lane == 0) S.scan[wid] = __popcll(m);
-      __syncthreads();
-      int off = base;
-      for (int w = 0; w < wid; w++) off += S.scan[w];
-      if (a) act[off + pre] = i;
-      int tot = 0;
-      for (int w = 0; w < PBS / 64; w++) tot += S.scan[w];
-      base += tot;
-      __syncthreads();
+      compact_chunk<PBS>(i < n && !P.outlier[i], S.scan, base, [&](int slot) { act[slot] = i; });
     }
     const int nact = base;
     __threadfence_block();
@@ -331,35 +321,22 @@ __global__ __launch_bounds__(PBS) void k_pose_optimization(const PoseDev* __rest
         }
         if (wid == 0 && lane < kTerm) {
           if (lane < 21) {
-            int r = 0, c = lane;
-            while (c >= 6 - r) {
-              c -= 6 - r;
-              r++;
-            }
-            c += r;
+            int r, c;
+            tri_rc<6>(lane, r, c);
             S.H[6 * r + c] = acc;
             S.H[6 * c + r] = acc;
           } else if (lane < 27) {
             S.b[lane - 21] = acc;
           } else {
-            S.currentChi = acc;
-            S.iniChi = acc;
+            S.lm.currentChi = acc;
+            S.lm.iniChi = acc;
           }
         }
         __syncthreads();
         POSE_TS(2);
         if (tid == 0) {
-          if (iter == 0) {
-            double m = 0;
-            for (int j = 0; j < 6; j++) {
-              const double a = __builtin_fabs(S.H[7 * j]);
-              m = (a < m) ? m : a;  // std::max(|H_jj|, m)
-            }
-            S.lambda = 1e-5 * m;
-            S.ni = 2;
-            S.nbad_lm = 0;
-          }
-          S.qmax = 0;
+          if (iter == 0) start(S.lm, lambda_init<6>(S.H));
+          S.lm.qmax = 0;
         }
         __syncthreads();
         POSE_TS(3);
@@ -371,7 +348,7 @@ __global__ __launch_bounds__(PBS) void k_pose_optimization(const PoseDev* __rest
 #pragma unroll
             for (int j = 0; j < 36; j++) Hd[j] = S.H[j];
 #pragma unroll
-            for (int j = 0; j < 6; j++) Hd[7 * j] += S.lambda;
+            for (int j = 0; j < 6; j++) Hd[7 * j] += S.lm.lambda;
             const bool ok2 = ldlt<6>(Hd, S.b, S.x);
             S.ok2 = ok2;
             POSE_TS(9);
@@ -407,43 +384,18 @@ __global__ __launch_bounds__(PBS) void k_pose_optimization(const PoseDev* __rest
           }
           if (tid == 0) {
             const bool ok2 = S.ok2;
-            if (!ok2) tempChi = 1.7976931348623157e308;
-            double rho = S.currentChi - tempChi;
             double scale = 0.0;
             if (ok2)
-              for (int j = 0; j < 6; j++) scale += S.x[j] * (S.lambda * S.x[j] + S.b[j]);
-            scale += 1e-3;
-            rho /= scale;
-            if (rho > 0 && __builtin_isfinite(tempChi)) {
-              const double t3 = 2 * rho - 1;
-              double alpha = 1. - t3 * t3 * t3;
-              alpha = (2. / 3. < alpha) ? 2. / 3. : alpha;       // std::min(alpha, 2/3)
-              S.lambda *= (1. / 3. < alpha) ? alpha : 1. / 3.;    // std::max(1/3, alpha)
-              S.ni = 2;
-              S.currentChi = tempChi;
-            } else {
-              S.lambda *= S.ni;
-              S.ni *= 2;
-              S.T = S.bak;
-            }
-            S.qmax++;
-            S.rho = rho;
-            S.go = (rho < 0 && S.qmax < 10);
+              for (int j = 0; j < 6; j++) scale += S.x[j] * (S.lm.lambda * S.x[j] + S.b[j]);
+            const Verdict v = trial<Cube::kProduct>(S.lm, tempChi, scale, ok2);
+            if (!v.accept) S.T = S.bak;  // pop
+            S.go = v.go;
           }
           __syncthreads();
           POSE_TS(7);
           if (!S.go) break;
         }
-        if (tid == 0) {
-          int term = 0;
-          if (S.qmax == 10 || S.rho == 0) term = 1;
-          else {
-            if ((S.iniChi - S.currentChi) * 1e3 < S.iniChi) S.nbad_lm++;
-            else S.nbad_lm = 0;
-            if (S.nbad_lm >= 3) term = 1;
-          }
-          S.term = term;
-        }
+        if (tid == 0) S.term = iteration_end(S.lm);
         __syncthreads();
         POSE_TS(7);
         if (S.term) break;

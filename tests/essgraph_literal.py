@@ -49,12 +49,11 @@ addEdge refuses a null vertex) and its pose stays; a bad point stays.
 `counters` records how often each branch fired so a test can assert its input reaches them.
 """
 import collections
-import math
 
 import numpy as np
 
-from optsim3_literal import (DBL_MAX, EPS, exp_det, mat2q, qmul, qrot, sim3_exp, sim3_inverse,  # noqa: F401
-                             sim3_map, sim3_mul)
+from optsim3_literal import (DBL_MAX, EPS, exp_det, lm_iteration_end, lm_trial, mat2q, qmul, qrot,  # noqa: F401
+                             sim3_exp, sim3_inverse, sim3_map, sim3_mul)
 
 F32 = np.float32
 F64 = np.float64
@@ -503,38 +502,21 @@ class Graph:
                 self.fails += 1
                 self.c["solver_failures"] += 1
             tempChi = self.chi2(self.errors())
-            if not ok2:
-                tempChi = DBL_MAX
-            rho = currentChi - tempChi
             scale = 0.0
             if ok2:
                 for v in (x * (self.lam * x + self.b)).tolist():
                     scale = scale + v
-            scale += 1e-3
-            rho /= scale
-            if rho > 0 and math.isfinite(tempChi):
-                t3 = 2 * rho - 1
-                alpha = 1. - t3 * t3 * t3
-                alpha = min(alpha, 2. / 3.)
-                self.lam *= max(1. / 3., alpha)
-                self.ni = 2.0
-                currentChi = tempChi
-            else:
-                self.lam *= self.ni
-                self.ni *= 2
+            (self.lam, self.ni, currentChi, rho, qmax, self.nBad), accept, go = lm_trial(
+                (self.lam, self.ni, currentChi, rho, qmax, self.nBad), tempChi, scale, ok2)
+            if not accept:
                 self.est = bak
                 self.c["rejected_trials"] += 1
-            qmax += 1
-            if not (rho < 0 and qmax < 10):
+            if not go:
                 break
         self.chi = currentChi
-        if qmax == 10 or rho == 0:
-            return False
-        if (iniChi - currentChi) * 1e3 < iniChi:
-            self.nBad += 1
-        else:
-            self.nBad = 0
-        return self.nBad < 3
+        (self.lam, self.ni, currentChi, rho, qmax, self.nBad), stop = lm_iteration_end(
+            (self.lam, self.ni, currentChi, rho, qmax, self.nBad), iniChi)
+        return not stop
 
     def optimize(self, its, lambda_init):
         n = 0

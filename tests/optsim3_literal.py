@@ -40,6 +40,7 @@ Evaluation orders, choice by choice:
 `counters` records how often each branch fired so a test can assert its input reaches them.
 """
 import collections
+import fractions
 import math
 import struct
 
@@ -348,6 +349,76 @@ def ldlt_solve(Hin, b, n):
 
 
 # ------------------------------------------------------------------ the optimizer
+def cube_product(x):
+    """t3 * t3 * t3, as oracle/poseopt.cpp writes OptimizationAlgorithmLevenberg's pow(2 rho - 1, 3): the
+    cube of PoseOptimization, OptimizeSim3 and OptimizeEssentialGraph."""
+    return x * x * x
+
+
+def cube_rounded(x):
+    """x^3 rounded once: LocalBundleAdjustment's cube.  oracle/localba.cpp calls std::pow(x, 3); glibc's pow
+    is within an ulp of this value but not always equal to it (x = 6.118015287389873 is one last bit off),
+    so the exact rational cube, rounded by float(), is the reference."""
+    if not math.isfinite(x):
+        return x * x * x
+    try:
+        return float(fractions.Fraction(x) ** 3)
+    except OverflowError:
+        return math.copysign(math.inf, x)
+
+
+def lm_trial(state, tempChi, scale, ok2, cube=cube_product, counters=None):
+    """One trial's verdict of OptimizationAlgorithmLevenberg::solve (oracle/poseopt.cpp:441-466), pure.
+    state = (lam, ni, currentChi, rho, qmax, nBad); scale = sum x_j (lam x_j + b_j) of a successful solve.
+    Returns (state, accepted, another trial follows).  counters (optional): the branch taken."""
+    lam, ni, currentChi, rho, qmax, nBad = state
+    c = collections.Counter() if counters is None else counters
+    if not ok2:
+        tempChi = DBL_MAX
+        scale = 0.0
+        c["not_ok2"] += 1
+    rho = currentChi - tempChi
+    scale += 1e-3
+    rho /= scale
+    accept = rho > 0 and math.isfinite(tempChi)
+    if accept:
+        t3 = 2 * rho - 1
+        alpha = 1. - cube(t3)
+        c["alpha_above_2/3" if alpha > 2. / 3. else "alpha_below_1/3" if alpha < 1. / 3. else "alpha_between"] += 1
+        alpha = min(alpha, 2. / 3.)
+        lam *= max(1. / 3., alpha)
+        ni = 2.0
+        currentChi = tempChi
+    else:
+        c["reject_rho_nan" if rho != rho else "reject_rho_le_0" if rho <= 0 else "reject_nonfinite_chi"] += 1
+        lam *= ni
+        ni *= 2
+    qmax += 1
+    go = rho < 0 and qmax < 10
+    if rho < 0 and not go:
+        c["tenth_trial"] += 1
+    return (lam, ni, currentChi, rho, qmax, nBad), accept, go
+
+
+def lm_iteration_end(state, iniChi, counters=None):
+    """The rule after an iteration's last trial (oracle/poseopt.cpp:467-471 and optimize()'s _nBad
+    count), pure.  Returns (state, optimize() stops)."""
+    lam, ni, currentChi, rho, qmax, nBad = state
+    c = collections.Counter() if counters is None else counters
+    if qmax == 10 or rho == 0:
+        c["stop_qmax_10" if qmax == 10 else "stop_rho_0"] += 1
+        return state, True
+    if (iniChi - currentChi) * 1e3 < iniChi:
+        nBad += 1
+        c["nbad_up"] += 1
+    else:
+        nBad = 0
+        c["nbad_reset"] += 1
+    if nBad >= 3:
+        c["stop_nbad_3"] += 1
+    return (lam, ni, currentChi, rho, qmax, nBad), nBad >= 3
+
+
 class _Graph:
     """The one-vertex graph after the intake loop, with g2o's Levenberg over it."""
 
@@ -465,39 +536,21 @@ class _Graph:
                 self.counters["not_positive"] += 1
             self.errors()
             tempChi = self.chi2()
-            if not ok2:
-                tempChi = DBL_MAX
-            rho = currentChi - tempChi
             scale = 0.0
             if ok2:
                 for j in range(7):
                     scale += x[j] * (self.lam * x[j] + self.b[j])
-            scale += 1e-3
-            rho /= scale
-            if rho > 0 and math.isfinite(tempChi):
-                t3 = 2 * rho - 1
-                alpha = 1. - t3 * t3 * t3
-                alpha = min(alpha, 2. / 3.)
-                self.lam *= max(1. / 3., alpha)
-                self.ni = 2.0
-                currentChi = tempChi
-                self.last_rejected = False
-            else:
-                self.lam *= self.ni
-                self.ni *= 2
+            (self.lam, self.ni, currentChi, rho, qmax, self.nBad), accept, go = lm_trial(
+                (self.lam, self.ni, currentChi, rho, qmax, self.nBad), tempChi, scale, ok2)
+            self.last_rejected = not accept
+            if not accept:
                 self.S = bak  # pop; the rejected trial's errors stay in the edges
                 self.counters["rejected_trials"] += 1
-                self.last_rejected = True
-            qmax += 1
-            if not (rho < 0 and qmax < 10):
+            if not go:
                 break
-        if qmax == 10 or rho == 0:
-            return False
-        if (iniChi - currentChi) * 1e3 < iniChi:
-            self.nBad += 1
-        else:
-            self.nBad = 0
-        return self.nBad < 3
+        (self.lam, self.ni, currentChi, rho, qmax, self.nBad), stop = lm_iteration_end(
+            (self.lam, self.ni, currentChi, rho, qmax, self.nBad), iniChi)
+        return not stop
 
     def optimize(self, its):
         if len(self.act) == 0:

@@ -14,6 +14,7 @@
 #include "ba_lm.h"
 #include "ba_schur.h"
 #include "ba_structure.h"
+#include "orbx_scratch.h"
 
 namespace orbx {
 
@@ -93,7 +94,7 @@ struct Arena {
   }
   template <class T>
   T* take(size_t n) {
-    off = (off + 255) & ~(size_t)255;
+    off = scratch_align(off);
     T* d = reinterpret_cast<T*>(dbuf + off);
     off += std::max<size_t>(n, 1) * sizeof(T);
     return d;
@@ -115,7 +116,7 @@ struct Arena {
 
 inline size_t arena_bytes(std::initializer_list<size_t> sizes) {
   size_t t = 0;
-  for (size_t x : sizes) t += ((std::max<size_t>(x, 1) + 255) & ~(size_t)255);
+  for (size_t x : sizes) t += scratch_align(std::max<size_t>(x, 1));
   return t + 256;
 }
 

@@ -825,7 +825,7 @@ orbx_status orbx_extract(orbx_extractor* h, const uint8_t* img, int width, int h
   auto chk = [&](hipError_t x) { if (x != hipSuccess) e = x; };
   const size_t npx = (size_t)width * height;
   h->out_kps = 256;
-  h->out_desc = h->out_kps + (((size_t)kcap * sizeof(orbx_keypoint) + 255) & ~(size_t)255);
+  h->out_desc = h->out_kps + scratch_align((size_t)kcap * sizeof(orbx_keypoint));
   h->out_bytes = h->out_desc + (size_t)kcap * 32;
   chk(h->in.ensure(npx + kInSlack));
   chk(h->out.ensure(h->out_bytes));
@@ -845,7 +845,7 @@ orbx_status orbx_extract(orbx_extractor* h, const uint8_t* img, int width, int h
     // mvImagePyramid (src/ORBextractor.cc:1215-1250 rebuilds it on every call): levels 1.. leave in
     // one more D2H behind the output block; level 0 is the staged input, copied on the host while
     // the kernels run
-    h->hpyr_l0 = (npx + 255) & ~(size_t)255;
+    h->hpyr_l0 = scratch_align(npx);
     if (h->ensure_hpyr(h->hpyr_l0 + (size_t)P->G.pyr_bytes) != hipSuccess) return ORBX_ERR_HIP;
   }
   // count, keypoints and descriptors in ONE copy, then the stream's only synchronisation
@@ -1030,7 +1030,7 @@ orbx_status orbx_frame_stereo(orbx_extractor* h, const uint8_t* imL, size_t stri
   // device output block: counts (L, R) and the match count | keypoints (L | R, kc each) |
   // descriptors (L | R) | uRight | depth -- one copy back; the images go in as a batch of two
   const size_t npx = (size_t)width * height;
-  const size_t o_kps = 256, o_desc = o_kps + (((size_t)2 * kc * sizeof(orbx_keypoint) + 255) & ~(size_t)255),
+  const size_t o_kps = 256, o_desc = o_kps + scratch_align((size_t)2 * kc * sizeof(orbx_keypoint)),
                o_ur = o_desc + (size_t)2 * kc * 32, o_dep = o_ur + (size_t)kc * 4, o_end = o_dep + (size_t)kc * 4;
   hipError_t e = hipSuccess;
   auto chk = [&](hipError_t x) { if (x != hipSuccess) e = x; };
@@ -1104,60 +1104,57 @@ static orbx_status bow_host(const orbx_bow_side* A, const orbx_bow_side* B, floa
   const int nout = mode ? A->n : B->n;
   *nmatches = 0;
   if (A->n > kMaxBowFeatures || B->n > kMaxBowFeatures || A->n < 0 || B->n < 0) return ORBX_ERR_CAPACITY;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return ORBX_ERR_NODEV;
-  if (device < 0 || device >= ndev || hipSetDevice(device) != hipSuccess) return ORBX_ERR_ARG;
-  // one arena: both sides' arrays + outputs + the problem descriptor
-  auto side_bytes = [](const orbx_bow_side* s) {
-    return (size_t)s->n * 32 + (size_t)s->n * 4 + (size_t)s->n + (size_t)s->n_nodes * 4 +
-           (size_t)(s->n_nodes + 1) * 4 + (size_t)(s->n_nodes ? s->node_off[s->n_nodes] : 0) * 4 + 64;
-  };
-  const size_t bytes = side_bytes(A) + side_bytes(B) + (size_t)nout * 4 + 64 + sizeof(BowProblem) + 64;
+  const orbx_status dv = orbx::select_device(device);
+  if (dv != ORBX_OK) return dv;
   // a pooled lease (orbx_scratch.h): no allocation, no device-wide synchronisation per call
-  ScratchGuard g(device);
-  if (!g.l || g.l->reserve(bytes, bytes) != hipSuccess) return ORBX_ERR_HIP;
-  uint8_t* host = g.l->h;
-  uint8_t* dbase = g.l->d;
-  size_t off = 0;
-  auto put = [&](const void* src, size_t nbytes) -> void* {
-    off = (off + 15) & ~(size_t)15;
-    if (src && nbytes) std::memcpy(host + off, src, nbytes);
-    void* d = dbase + off;
-    off += nbytes;
-    return d;
-  };
-  auto side = [&](const orbx_bow_side* s) {
-    orbx_bow_side d = *s;
-    const int nf = s->n_nodes ? s->node_off[s->n_nodes] : 0;
-    d.desc = (const uint8_t*)put(s->desc, (size_t)s->n * 32);
-    d.angle = (const float*)put(s->angle, (size_t)s->n * 4);
-    d.valid = s->valid ? (const uint8_t*)put(s->valid, (size_t)s->n) : nullptr;
-    d.node_id = (const uint32_t*)put(s->node_id, (size_t)s->n_nodes * 4);
-    d.node_off = (const int32_t*)put(s->node_off, (size_t)(s->n_nodes + 1) * 4);
-    d.feat = (const int32_t*)put(s->feat, (size_t)nf * 4);
-    return d;
-  };
+  using orbx::Staging;
+  Staging S(device);
+  struct Side {
+    Staging::Slot<uint8_t> desc, valid;
+    Staging::Slot<float> angle;
+    Staging::Slot<uint32_t> node_id;
+    Staging::Slot<int32_t> node_off, feat;
+  } L[2];
+  const orbx_bow_side* sides[2] = {A, B};
+  for (int z = 0; z < 2; z++) {
+    const orbx_bow_side* s = sides[z];
+    const size_t n = (size_t)s->n, nn = (size_t)s->n_nodes;
+    L[z].desc = S.in(s->desc, n * 32);
+    L[z].angle = S.in(s->angle, n);
+    L[z].valid = S.in_opt(s->valid, n);
+    L[z].node_id = S.in(s->node_id, nn);
+    L[z].node_off = S.in(s->node_off, nn + 1);
+    L[z].feat = S.in(s->feat, nn ? (size_t)s->node_off[nn] : 0);
+  }
+  const auto s_P = S.record<BowProblem>();
+  const auto s_match = S.out<int32_t>((size_t)nout), s_n = S.out<int32_t>(1);
+  const orbx_status cs = S.commit();
+  if (cs != ORBX_OK) return cs;
   BowProblem P;
   std::memset(&P, 0, sizeof(P));  // no device-count overrides on the host path
-  P.a = side(A);
-  P.b = side(B);
+  for (int z = 0; z < 2; z++) {
+    orbx_bow_side& d = z ? P.b : P.a;
+    d = *sides[z];
+    d.desc = S.dev(L[z].desc);
+    d.angle = S.dev(L[z].angle);
+    d.valid = S.dev(L[z].valid);
+    d.node_id = S.dev(L[z].node_id);
+    d.node_off = S.dev(L[z].node_off);
+    d.feat = S.dev(L[z].feat);
+  }
   P.nnratio = nnratio;
   P.check_ori = check_ori;
   P.mode = mode;
-  const size_t o_out = (off + 15) & ~(size_t)15;
-  P.match = (int32_t*)put(nullptr, (size_t)nout * 4);
-  P.nmatches = (int32_t*)put(nullptr, 4);
-  const size_t o_end = off;
-  BowProblem* dP = (BowProblem*)put(&P, sizeof(P));
-  hipStream_t st = g.l->st;
-  // outputs [o_out, o_end) come back in one copy: matches then the count
-  hipError_t e = hipMemcpyAsync(dbase, host, off, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = launch_search_by_bow(dP, 1, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(host + o_out, dbase + o_out, o_end - o_out, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = g.l->sync();
+  P.match = S.dev(s_match);
+  P.nmatches = S.dev(s_n);
+  S.fill(s_P, P);
+  hipError_t e = S.upload(Staging::Outputs::zeroed);
+  if (e == hipSuccess) e = launch_search_by_bow(S.dev(s_P), 1, S.stream());
+  if (e == hipSuccess) e = S.download();
+  if (e == hipSuccess) e = S.sync();
   if (e != hipSuccess) return ORBX_ERR_HIP;
-  if (nout) std::memcpy(match, host + o_out, (size_t)nout * 4);
-  std::memcpy(nmatches, host + ((uint8_t*)P.nmatches - dbase), 4);
+  S.fetch(s_match, match, (size_t)nout);
+  S.fetch(s_n, (int32_t*)nmatches, 1);
   return ORBX_OK;
 }
 
@@ -1177,12 +1174,11 @@ orbx_status orbx_search_by_bow_device(const orbx_bow_problem* problems, int n, v
   for (int i = 0; i < n; i++)
     if (problems[i].a.n > kMaxBowFeatures || problems[i].b.n > kMaxBowFeatures) return ORBX_ERR_CAPACITY;
   hipStream_t st = (hipStream_t)stream;
-  BowProblem* dP = nullptr;
-  if (hipMallocAsync((void**)&dP, sizeof(BowProblem) * n, st) != hipSuccess) return ORBX_ERR_HIP;
-  hipError_t e = hipMemcpyAsync(dP, problems, sizeof(BowProblem) * n, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = launch_search_by_bow(dP, n, st);
-  hipError_t e2 = hipFreeAsync(dP, st);
-  return hip_status(e != hipSuccess ? e : e2);
+  const size_t bytes = sizeof(BowProblem) * n;
+  return orbx::with_stream_block(bytes, st, [&](uint8_t* d) {
+    const hipError_t e = hipMemcpyAsync(d, problems, bytes, hipMemcpyHostToDevice, st);
+    return e != hipSuccess ? e : launch_search_by_bow((const BowProblem*)d, n, st);
+  });
 }
 
 orbx_status orbx_profile_enable(orbx_extractor* h, int enable) {
@@ -1355,10 +1351,9 @@ extern "C" orbx_status orbx_debug_stereo_keypoints(orbx_extractor* left, orbx_ex
   if (hipSetDevice(h->device) != hipSuccess) return ORBX_ERR_HIP;
   // scratch block of this call alone (the handles' output blocks keep their extractions):
   // counts (L, R) and the match count | keypoints L | R | descriptors L | R | uRight | depth
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t o_kL = 256, o_kR = o_kL + up((size_t)nL * sizeof(orbx_keypoint)),
-               o_dL = o_kR + up((size_t)nR * sizeof(orbx_keypoint)), o_dR = o_dL + up((size_t)nL * 32),
-               o_res = o_dR + up((size_t)nR * 32), o_end = o_res + (size_t)8 * nL;
+  const size_t o_kL = 256, o_kR = o_kL + scratch_align((size_t)nL * sizeof(orbx_keypoint)),
+               o_dL = o_kR + scratch_align((size_t)nR * sizeof(orbx_keypoint)), o_dR = o_dL + scratch_align((size_t)nL * 32),
+               o_res = o_dR + scratch_align((size_t)nR * 32), o_end = o_res + (size_t)8 * nL;
   DevBuf<uint8_t> blk;
   if (blk.ensure(o_end) != hipSuccess) return ORBX_ERR_HIP;
   hipError_t e = hipSuccess;

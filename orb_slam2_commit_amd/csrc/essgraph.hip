@@ -760,13 +760,6 @@ hipError_t enqueue_run(const Dev& D, hipStream_t st) {
   return e;
 }
 
-orbx_status pick_device(int device) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return ORBX_ERR_NODEV;
-  if (device < 0 || device >= ndev || hipSetDevice(device) != hipSuccess) return ORBX_ERR_ARG;
-  return ORBX_OK;
-}
-
 // a host-form session: the plan, a scratch lease, the problem's pose tables staged and uploaded
 struct HostRun {
   Plan P;
@@ -832,7 +825,7 @@ static orbx_status run_host(const orbx_essential_graph_problem* p, const orbx_es
   if (!p || !res || !res->Scw_out || !res->Tcw_out || (p->n_points > 0 && !res->Xw_out)) return ORBX_ERR_ARG;
   const orbx_status chk = check(*p, true);
   if (chk != ORBX_OK) return chk;
-  const orbx_status dv = pick_device(device);
+  const orbx_status dv = orbx::select_device(device);
   if (dv != ORBX_OK) return dv;
   const size_t n = (size_t)p->n_vertices, m = (size_t)p->n_points;
   const size_t r_scw = 0, r_tcw = r_scw + orbx::scratch_align(n * 64), r_xw = r_tcw + orbx::scratch_align(n * 48),
@@ -895,41 +888,39 @@ extern "C" orbx_status orbx_optimize_essential_graph_device(const orbx_essential
   if (!make_plan(*p, P)) return ORBX_ERR_CAPACITY;
   const Layout L = make_layout(P, 0, false);
   hipStream_t st = (hipStream_t)stream;
-  uint8_t* d = nullptr;
-  if (hipMallocAsync((void**)&d, L.end, st) != hipSuccess) return ORBX_ERR_HIP;
-  Dev D = make_dev(*p, P, L, d, false);
-  D.Scw = p->Scw; D.Snc = p->Snc; D.Xw = p->Xw; D.pref = p->point_ref;
-  D.Scw_out = res->Scw_out; D.Tcw_out = res->Tcw_out; D.Xw_out = res->Xw_out;
-  D.o_iterations = res->iterations; D.o_trials = res->trials; D.o_chi0 = res->chi2_initial;
-  D.o_chi1 = res->chi2_final; D.o_fail = res->solver_failures;
-  // pageable source: hipMemcpyAsync returns once P.ints is staged, so the plan may go
-  hipError_t e = enqueue_setup(P, L, D, d, P.ints.data(), st);
-  if (e == hipSuccess) e = enqueue_run(D, st);
-  const hipError_t e2 = hipFreeAsync(d, st);
-  return e != hipSuccess ? ORBX_ERR_HIP : (e2 != hipSuccess ? ORBX_ERR_HIP : ORBX_OK);
+  return orbx::with_stream_block(L.end, st, [&](uint8_t* d) {
+    Dev D = make_dev(*p, P, L, d, false);
+    D.Scw = p->Scw; D.Snc = p->Snc; D.Xw = p->Xw; D.pref = p->point_ref;
+    D.Scw_out = res->Scw_out; D.Tcw_out = res->Tcw_out; D.Xw_out = res->Xw_out;
+    D.o_iterations = res->iterations; D.o_trials = res->trials; D.o_chi0 = res->chi2_initial;
+    D.o_chi1 = res->chi2_final; D.o_fail = res->solver_failures;
+    // pageable source: hipMemcpyAsync returns once P.ints is staged, so the plan may go
+    const hipError_t e = enqueue_setup(P, L, D, d, P.ints.data(), st);
+    return e != hipSuccess ? e : enqueue_run(D, st);
+  });
 }
 
 // ------------------------------------------------------------------ debug probes (orbx_debug.h)
 static int debug_unary(const double* x, int n, double* y, int device, int what) {
   if (n < 0 || (n > 0 && (!x || !y))) return ORBX_ERR_ARG;
-  const orbx_status dv = pick_device(device);
+  const orbx_status dv = orbx::select_device(device);
   if (dv != ORBX_OK) return dv;
   if (n == 0) return ORBX_OK;
-  const size_t bytes = orbx::scratch_align((size_t)n * 8);
-  orbx::ScratchGuard g(device);
-  if (!g.l || g.l->reserve(2 * bytes, 2 * bytes) != hipSuccess) return ORBX_ERR_HIP;
-  std::memcpy(g.l->h, x, (size_t)n * 8);
-  hipStream_t st = g.l->st;
-  hipError_t e = hipMemcpyAsync(g.l->d, g.l->h, bytes, hipMemcpyHostToDevice, st);
+  orbx::Staging S(device);
+  const auto s_x = S.in(x, (size_t)n);
+  const auto s_y = S.out<double>((size_t)n);
+  const orbx_status cs = S.commit();
+  if (cs != ORBX_OK) return cs;
+  hipError_t e = S.upload(orbx::Staging::Outputs::skipped);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_debug_unary, dim3((n + 255) / 256), dim3(256), 0, st, (const double*)g.l->d, n,
-                       (double*)(g.l->d + bytes), what);
+    hipLaunchKernelGGL(k_debug_unary, dim3((n + 255) / 256), dim3(256), 0, S.stream(), (const double*)S.dev(s_x), n,
+                       S.dev(s_y), what);
     e = hipGetLastError();
   }
-  if (e == hipSuccess) e = hipMemcpyAsync(g.l->h + bytes, g.l->d + bytes, bytes, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = g.l->sync();
+  if (e == hipSuccess) e = S.download();
+  if (e == hipSuccess) e = S.sync();
   if (e != hipSuccess) return ORBX_ERR_HIP;
-  std::memcpy(y, g.l->h + bytes, (size_t)n * 8);
+  S.fetch(s_y, y, (size_t)n);
   return ORBX_OK;
 }
 extern "C" int orbx_debug_log(const double* x, int n, double* y, int device) { return debug_unary(x, n, y, device, 0); }
@@ -937,26 +928,26 @@ extern "C" int orbx_debug_acos(const double* x, int n, double* y, int device) { 
 
 extern "C" int orbx_debug_sim3_log(const double* S, int n, double* out, int32_t* branch, int device) {
   if (n < 0 || (n > 0 && (!S || !out))) return ORBX_ERR_ARG;
-  const orbx_status dv = pick_device(device);
+  const orbx_status dv = orbx::select_device(device);
   if (dv != ORBX_OK) return dv;
   if (n == 0) return ORBX_OK;
-  const size_t b_in = orbx::scratch_align((size_t)n * 64), b_out = orbx::scratch_align((size_t)n * 56),
-               b_br = orbx::scratch_align((size_t)n * 4);
-  orbx::ScratchGuard g(device);
-  if (!g.l || g.l->reserve(b_in + b_out + b_br, b_in + b_out + b_br) != hipSuccess) return ORBX_ERR_HIP;
-  std::memcpy(g.l->h, S, (size_t)n * 64);
-  hipStream_t st = g.l->st;
-  hipError_t e = hipMemcpyAsync(g.l->d, g.l->h, b_in, hipMemcpyHostToDevice, st);
+  orbx::Staging G(device);
+  const auto s_S = G.in(S, (size_t)n * 8);
+  const auto s_out = G.out<double>((size_t)n * 7);
+  const auto s_br = G.out<int32_t>((size_t)n);
+  const orbx_status cs = G.commit();
+  if (cs != ORBX_OK) return cs;
+  hipError_t e = G.upload(orbx::Staging::Outputs::skipped);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_debug_sim3_log, dim3((n + 255) / 256), dim3(256), 0, st, (const double*)g.l->d, n,
-                       (double*)(g.l->d + b_in), (int32_t*)(g.l->d + b_in + b_out));
+    hipLaunchKernelGGL(k_debug_sim3_log, dim3((n + 255) / 256), dim3(256), 0, G.stream(), (const double*)G.dev(s_S), n,
+                       G.dev(s_out), G.dev(s_br));
     e = hipGetLastError();
   }
-  if (e == hipSuccess) e = hipMemcpyAsync(g.l->h + b_in, g.l->d + b_in, b_out + b_br, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = g.l->sync();
+  if (e == hipSuccess) e = G.download();
+  if (e == hipSuccess) e = G.sync();
   if (e != hipSuccess) return ORBX_ERR_HIP;
-  std::memcpy(out, g.l->h + b_in, (size_t)n * 56);
-  if (branch) std::memcpy(branch, g.l->h + b_in + b_out, (size_t)n * 4);
+  G.fetch(s_out, out, (size_t)n * 7);
+  G.fetch(s_br, branch, (size_t)n);
   return ORBX_OK;
 }
 
@@ -967,7 +958,7 @@ extern "C" int orbx_debug_essgraph_linearize(const orbx_essential_graph_problem*
   q.n_points = 0;
   const orbx_status chk = check(q, true);
   if (chk != ORBX_OK) return chk;
-  const orbx_status dv = pick_device(device);
+  const orbx_status dv = orbx::select_device(device);
   if (dv != ORBX_OK) return dv;
   HostRun R(device);
   size_t od = 0, oh = 0;
@@ -1008,7 +999,7 @@ extern "C" int orbx_debug_essgraph_solve(const orbx_essential_graph_problem* p, 
   q.n_points = 0;
   const orbx_status chk = check(q, true);
   if (chk != ORBX_OK) return chk;
-  const orbx_status dv = pick_device(device);
+  const orbx_status dv = orbx::select_device(device);
   if (dv != ORBX_OK) return dv;
   Plan P;
   if (!make_plan(q, P)) return ORBX_ERR_CAPACITY;

@@ -872,7 +872,7 @@ orbx_status init_run_device(orbx_initializer* h, const float* keys2_xy, InitCall
   size_t o = 0;
   auto take = [&](size_t bytes) {
     const size_t at = o;
-    o += orbx::align256(bytes);
+    o += orbx::scratch_align(bytes);
     return at;
   };
   const size_t o_job = take(sizeof(InitJob)), o_k2 = take(8 * n2), o_pn2 = take(8 * n2), o_m1 = take(4 * N),

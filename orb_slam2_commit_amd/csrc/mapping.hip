@@ -125,13 +125,6 @@ __global__ __launch_bounds__(UBS) void k_undistort(const orbx_keypoint* __restri
 // ------------------------------------------------------------------ C ABI
 namespace {
 
-orbx_status set_device(int device) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return ORBX_ERR_NODEV;
-  if (device < 0 || device >= ndev || hipSetDevice(device) != hipSuccess) return ORBX_ERR_ARG;
-  return ORBX_OK;
-}
-
 bool camera_ok(const orbx_camera& c) { return c.n_dist >= 4 && c.n_dist <= 5 && c.K[0] != 0.0f && c.K[4] != 0.0f; }
 
 }  // namespace
@@ -153,39 +146,28 @@ extern "C" orbx_status orbx_distinctive_descriptors(const uint8_t* desc, const i
   if (obs_off[0] != 0) return ORBX_ERR_ARG;
   for (int p = 0; p < n_points; p++)  // host check of the CSR the kernel trusts (row index fits 16 bits)
     if (obs_off[p + 1] < obs_off[p] || obs_off[p + 1] - obs_off[p] > 65535) return ORBX_ERR_ARG;
-  const orbx_status ds = set_device(device);
+  const orbx_status ds = orbx::select_device(device);
   if (ds != ORBX_OK) return ds;
-  const size_t nd = (size_t)obs_off[n_points];
-  const size_t b_desc = (nd * 32 + 255) & ~(size_t)255, b_off = ((size_t)(n_points + 1) * 4 + 255) & ~(size_t)255;
-  const size_t b_best = ((size_t)n_points * 4 + 255) & ~(size_t)255;
-  // pooled lease (orbx_scratch.h): inputs staged in pinned memory, one stream, no allocation
-  const size_t total = b_desc + b_off + b_best + (size_t)n_points * 32;
-  orbx::ScratchGuard g(device);
-  if (!g.l || g.l->reserve(total, total) != hipSuccess) return ORBX_ERR_HIP;
-  uint8_t* d = g.l->d;
-  uint8_t* h = g.l->h;
-  uint8_t *d_desc = d, *d_off = d + b_desc, *d_best = d_off + b_off, *d_out = d_best + b_best;
-  if (nd) std::memcpy(h, desc, nd * 32);
-  std::memcpy(h + b_desc, obs_off, (size_t)(n_points + 1) * 4);
-  hipStream_t sm = g.l->st;
-  hipError_t e = hipMemcpyAsync(d, h, b_desc + (size_t)(n_points + 1) * 4, hipMemcpyHostToDevice, sm);
-  orbx_status st = ORBX_ERR_HIP;
-  if (e == hipSuccess)
-    st = orbx_distinctive_descriptors_device(d_desc, (const int32_t*)d_off, n_points, (int32_t*)d_best,
-                                             out_desc ? d_out : nullptr, sm);
-  if (st == ORBX_OK) {
-    // best and the descriptors are adjacent: one copy back
-    e = hipMemcpyAsync(h + (d_best - d), d_best, out_desc ? b_best + (size_t)n_points * 32 : (size_t)n_points * 4,
-                       hipMemcpyDeviceToHost, sm);
-    if (e == hipSuccess) e = g.l->sync();
-    if (e != hipSuccess) {
-      st = ORBX_ERR_HIP;
-    } else {
-      std::memcpy(best, h + (d_best - d), (size_t)n_points * 4);
-      if (out_desc) std::memcpy(out_desc, h + (d_out - d), (size_t)n_points * 32);
-    }
-  }
-  return st;
+  using orbx::Staging;
+  const size_t nd = (size_t)obs_off[n_points], np = (size_t)n_points;
+  Staging S(device);
+  const auto s_desc = S.in(desc, nd * 32);
+  const auto s_off = S.in(obs_off, np + 1);
+  const auto s_best = S.out<int32_t>(np);
+  const auto s_out = S.out<uint8_t>(out_desc ? np * 32 : 0);
+  orbx_status st = S.commit();
+  if (st != ORBX_OK) return st;
+  hipError_t e = S.upload(Staging::Outputs::skipped);
+  if (e != hipSuccess) return ORBX_ERR_HIP;
+  st = orbx_distinctive_descriptors_device(S.dev(s_desc), S.dev(s_off), n_points, S.dev(s_best),
+                                           out_desc ? S.dev(s_out) : nullptr, S.stream());
+  if (st != ORBX_OK) return st;
+  e = S.download();
+  if (e == hipSuccess) e = S.sync();
+  if (e != hipSuccess) return ORBX_ERR_HIP;
+  S.fetch(s_best, best, np);
+  S.fetch(s_out, out_desc, np * 32);
+  return ORBX_OK;
 }
 
 extern "C" orbx_status orbx_undistort_keypoints_device(const orbx_keypoint* keys, const int32_t* frame_off,
@@ -206,34 +188,24 @@ extern "C" orbx_status orbx_undistort_keypoints(const orbx_keypoint* keys, int n
   if (n < 0 || !cam || (n > 0 && (!keys || !keys_un))) return ORBX_ERR_ARG;
   if (!camera_ok(*cam)) return ORBX_ERR_ARG;
   if (n == 0) return ORBX_OK;
-  const orbx_status ds = set_device(device);
+  const orbx_status ds = orbx::select_device(device);
   if (ds != ORBX_OK) return ds;
-  const size_t bk = ((size_t)n * sizeof(orbx_keypoint) + 255) & ~(size_t)255;
-  const size_t total = 2 * bk + 256 + sizeof(orbx_camera);
-  orbx::ScratchGuard g(device);  // pooled lease (orbx_scratch.h)
-  if (!g.l || g.l->reserve(total, total) != hipSuccess) return ORBX_ERR_HIP;
-  uint8_t* d = g.l->d;
-  uint8_t* h = g.l->h;
-  orbx_keypoint *d_in = (orbx_keypoint*)d, *d_out = (orbx_keypoint*)(d + bk);
-  int32_t* d_off = (int32_t*)(d + 2 * bk);
-  orbx_camera* d_cam = (orbx_camera*)(d + 2 * bk + 256);
+  using orbx::Staging;
   const int32_t off[2] = {0, n};
-  std::memcpy(h, keys, (size_t)n * sizeof(orbx_keypoint));
-  std::memcpy(h + 2 * bk, off, sizeof(off));
-  std::memcpy(h + 2 * bk + 256, cam, sizeof(orbx_camera));
-  hipStream_t sm = g.l->st;
-  // inputs in two copies (keypoints; offsets + camera), the output in one
-  hipError_t e = hipMemcpyAsync(d, h, (size_t)n * sizeof(orbx_keypoint), hipMemcpyHostToDevice, sm);
-  if (e == hipSuccess) e = hipMemcpyAsync(d + 2 * bk, h + 2 * bk, 256 + sizeof(orbx_camera), hipMemcpyHostToDevice, sm);
-  orbx_status st = ORBX_ERR_HIP;
-  if (e == hipSuccess) st = orbx_undistort_keypoints_device(d_in, d_off, 1, n, d_cam, d_out, sm);
-  if (st == ORBX_OK) {
-    e = hipMemcpyAsync(h + bk, d_out, (size_t)n * sizeof(orbx_keypoint), hipMemcpyDeviceToHost, sm);
-    if (e == hipSuccess) e = g.l->sync();
-    if (e != hipSuccess)
-      st = ORBX_ERR_HIP;
-    else
-      std::memcpy(keys_un, h + bk, (size_t)n * sizeof(orbx_keypoint));
-  }
-  return st;
+  Staging S(device);
+  const auto s_in = S.in(keys, (size_t)n);
+  const auto s_off = S.in(off, 2);
+  const auto s_cam = S.in(cam, 1);
+  const auto s_out = S.out<orbx_keypoint>((size_t)n);
+  orbx_status st = S.commit();
+  if (st != ORBX_OK) return st;
+  hipError_t e = S.upload(Staging::Outputs::skipped);
+  if (e != hipSuccess) return ORBX_ERR_HIP;
+  st = orbx_undistort_keypoints_device(S.dev(s_in), S.dev(s_off), 1, n, S.dev(s_cam), S.dev(s_out), S.stream());
+  if (st != ORBX_OK) return st;
+  e = S.download();
+  if (e == hipSuccess) e = S.sync();
+  if (e != hipSuccess) return ORBX_ERR_HIP;
+  S.fetch(s_out, keys_un, (size_t)n);
+  return ORBX_OK;
 }

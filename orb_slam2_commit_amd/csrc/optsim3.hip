@@ -355,13 +355,6 @@ orbx_status osim3_check(const orbx_optimize_sim3_problem& p) {
   return ORBX_OK;
 }
 
-orbx_status pick_device(int device) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return ORBX_ERR_NODEV;
-  if (device < 0 || device >= ndev || hipSetDevice(device) != hipSuccess) return ORBX_ERR_ARG;
-  return ORBX_OK;
-}
-
 }  // namespace
 
 extern "C" orbx_status orbx_optimize_sim3(const orbx_optimize_sim3_problem* p, int device) {
@@ -369,59 +362,53 @@ extern "C" orbx_status orbx_optimize_sim3(const orbx_optimize_sim3_problem* p, i
   const orbx_status chk = osim3_check(*p);
   if (chk != ORBX_OK) return chk;
   if (p->n_dev) return ORBX_ERR_ARG;  // device batches only
-  const orbx_status dv = pick_device(device);
+  const orbx_status dv = orbx::select_device(device);
   if (dv != ORBX_OK) return dv;
+  using orbx::Staging;
   using orbx::osim3::Dev;
   const size_t n = (size_t)p->n;
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t o_x1 = 0, o_x2 = o_x1 + al(n * 12), o_o1 = o_x2 + al(n * 12), o_o2 = o_o1 + al(n * 8),
-               o_w1 = o_o2 + al(n * 8), o_w2 = o_w1 + al(n * 4), o_S = o_w2 + al(n * 4), o_in = o_S + al(64),
-               o_cnt = o_in + al(n), o_scr = o_cnt + al(32), o_act = o_scr + al(n * 32), o_dev = o_act + al(n * 4),
-               total = o_dev + al(sizeof(Dev));
-  orbx::ScratchGuard g(device);  // pooled lease: no per-call allocation (orbx_scratch.h)
-  if (!g.l || g.l->reserve(total, o_scr + sizeof(Dev)) != hipSuccess) return ORBX_ERR_HIP;
-  uint8_t* host = g.l->h;
-  std::memset(host + o_S, 0, o_scr - o_S);
-  if (n) {
-    std::memcpy(host + o_x1, p->x3dc1, n * 12);
-    std::memcpy(host + o_x2, p->x3dc2, n * 12);
-    std::memcpy(host + o_o1, p->obs1, n * 8);
-    std::memcpy(host + o_o2, p->obs2, n * 8);
-    std::memcpy(host + o_w1, p->inv_sigma2_1, n * 4);
-    std::memcpy(host + o_w2, p->inv_sigma2_2, n * 4);
-  }
-  uint8_t* d = g.l->d;
+  Staging S(device);  // pooled lease: no per-call allocation (orbx_scratch.h)
+  const auto s_x1 = S.in(p->x3dc1, n * 3), s_x2 = S.in(p->x3dc2, n * 3);
+  const auto s_o1 = S.in(p->obs1, n * 2), s_o2 = S.in(p->obs2, n * 2);
+  const auto s_w1 = S.in(p->inv_sigma2_1, n), s_w2 = S.in(p->inv_sigma2_2, n);
+  const auto s_dev = S.record<Dev>();
+  const auto s_S = S.out<double>(8);
+  const auto s_in = S.out<uint8_t>(n);
+  const auto s_cnt = S.out<int32_t>(8);  // n_in | n_bad | iterations[2] | trials
+  const auto s_err = S.device_only<double>(n * 4);
+  const auto s_act = S.device_only<int>(n);
+  const orbx_status cs = S.commit();
+  if (cs != ORBX_OK) return cs;
   Dev pd;
   pd.p = *p;
-  pd.p.x3dc1 = (const float*)(d + o_x1);
-  pd.p.x3dc2 = (const float*)(d + o_x2);
-  pd.p.obs1 = (const float*)(d + o_o1);
-  pd.p.obs2 = (const float*)(d + o_o2);
-  pd.p.inv_sigma2_1 = (const float*)(d + o_w1);
-  pd.p.inv_sigma2_2 = (const float*)(d + o_w2);
-  pd.p.S12_out = (double*)(d + o_S);
-  pd.p.inlier = (uint8_t*)(d + o_in);
-  int32_t* cnt = (int32_t*)(d + o_cnt);  // n_in | n_bad | iterations[2] | trials
+  pd.p.x3dc1 = S.dev(s_x1);
+  pd.p.x3dc2 = S.dev(s_x2);
+  pd.p.obs1 = S.dev(s_o1);
+  pd.p.obs2 = S.dev(s_o2);
+  pd.p.inv_sigma2_1 = S.dev(s_w1);
+  pd.p.inv_sigma2_2 = S.dev(s_w2);
+  pd.p.S12_out = S.dev(s_S);
+  pd.p.inlier = S.dev(s_in);
+  int32_t* cnt = S.dev(s_cnt);
   pd.p.n_in = cnt;
   pd.p.n_bad = cnt + 1;
   pd.p.iterations = cnt + 2;
   pd.p.trials = cnt + 4;
-  pd.err = (double*)(d + o_scr);
-  pd.act = (int*)(d + o_act);
-  std::memcpy(host + o_scr, &pd, sizeof(pd));  // the record rides in the staging block's tail
-  hipStream_t st = g.l->st;
-  hipError_t e = hipMemcpyAsync(d, host, o_scr, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d + o_dev, host + o_scr, sizeof(pd), hipMemcpyHostToDevice, st);
+  pd.err = S.dev(s_err);
+  pd.act = S.dev(s_act);
+  S.fill(s_dev, pd);
+  hipError_t e = S.upload(Staging::Outputs::zeroed);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(orbx::osim3::k_optimize_sim3, dim3(1), dim3(orbx::osim3::BS), 0, st, (const Dev*)(d + o_dev));
+    hipLaunchKernelGGL(orbx::osim3::k_optimize_sim3, dim3(1), dim3(orbx::osim3::BS), 0, S.stream(),
+                       (const Dev*)S.dev(s_dev));
     e = hipGetLastError();
   }
-  if (e == hipSuccess) e = hipMemcpyAsync(host + o_S, d + o_S, o_scr - o_S, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = g.l->sync();
+  if (e == hipSuccess) e = S.download();
+  if (e == hipSuccess) e = S.sync();
   if (e != hipSuccess) return ORBX_ERR_HIP;
-  std::memcpy(p->S12_out, host + o_S, 64);
-  if (n) std::memcpy(p->inlier, host + o_in, n);
-  const int32_t* hc = (const int32_t*)(host + o_cnt);
+  S.fetch(s_S, p->S12_out, 8);
+  S.fetch(s_in, p->inlier, n);
+  const int32_t* hc = S.host(s_cnt);
   *p->n_in = hc[0];
   if (p->n_bad) *p->n_bad = hc[1];
   if (p->iterations) std::memcpy(p->iterations, hc + 2, 8);
@@ -440,27 +427,27 @@ extern "C" orbx_status orbx_optimize_sim3_device(const orbx_optimize_sim3_proble
     rows += (size_t)problems[i].n;
   }
   hipStream_t st = (hipStream_t)stream;
+  // the records, then every problem's rows of errors, then their active lists
   const size_t dev_bytes = sizeof(Dev) * n;
-  const size_t err_off = (dev_bytes + 255) & ~(size_t)255;
+  const size_t err_off = orbx::scratch_align(dev_bytes);
   const size_t act_off = err_off + rows * 32;
-  uint8_t* d = nullptr;
-  if (hipMallocAsync((void**)&d, act_off + rows * 4 + 16, st) != hipSuccess) return ORBX_ERR_HIP;
-  std::vector<Dev> pd(n);
-  size_t r = 0;
-  for (int i = 0; i < n; i++) {
-    pd[i].p = problems[i];
-    pd[i].err = (double*)(d + err_off) + r * 4;
-    pd[i].act = (int*)(d + act_off) + r;
-    r += (size_t)problems[i].n;
-  }
-  hipError_t e = hipMemcpyAsync(d, pd.data(), dev_bytes, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(orbx::osim3::k_optimize_sim3, dim3(n), dim3(orbx::osim3::BS), 0, st, (const Dev*)d);
-    e = hipGetLastError();
-  }
-  // pageable source: hipMemcpyAsync returns once pd is staged, so pd may go
-  const hipError_t e2 = hipFreeAsync(d, st);
-  return e != hipSuccess ? ORBX_ERR_HIP : (e2 != hipSuccess ? ORBX_ERR_HIP : ORBX_OK);
+  return orbx::with_stream_block(act_off + rows * 4 + 16, st, [&](uint8_t* d) {
+    std::vector<Dev> pd(n);
+    size_t r = 0;
+    for (int i = 0; i < n; i++) {
+      pd[i].p = problems[i];
+      pd[i].err = (double*)(d + err_off) + r * 4;
+      pd[i].act = (int*)(d + act_off) + r;
+      r += (size_t)problems[i].n;
+    }
+    // pageable source: hipMemcpyAsync returns once pd is staged, so pd may go
+    hipError_t e = hipMemcpyAsync(d, pd.data(), dev_bytes, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(orbx::osim3::k_optimize_sim3, dim3(n), dim3(orbx::osim3::BS), 0, st, (const Dev*)d);
+      e = hipGetLastError();
+    }
+    return e;
+  });
 }
 
 // ------------------------------------------------------------------ debug probes (orbx_debug.h)
@@ -484,47 +471,49 @@ extern "C" int orbx_debug_lm_step(double state[5], int counts[2], double tempChi
 
 extern "C" int orbx_debug_exp(const double* x, int n, double* y, int device) {
   if (n < 0 || (n > 0 && (!x || !y))) return ORBX_ERR_ARG;
-  const orbx_status dv = pick_device(device);
+  const orbx_status dv = orbx::select_device(device);
   if (dv != ORBX_OK) return dv;
   if (n == 0) return ORBX_OK;
-  const size_t bytes = ((size_t)n * 8 + 255) & ~(size_t)255;
-  orbx::ScratchGuard g(device);
-  if (!g.l || g.l->reserve(2 * bytes, 2 * bytes) != hipSuccess) return ORBX_ERR_HIP;
-  std::memcpy(g.l->h, x, (size_t)n * 8);
-  hipStream_t st = g.l->st;
-  hipError_t e = hipMemcpyAsync(g.l->d, g.l->h, bytes, hipMemcpyHostToDevice, st);
+  orbx::Staging S(device);
+  const auto s_x = S.in(x, (size_t)n);
+  const auto s_y = S.out<double>((size_t)n);
+  const orbx_status cs = S.commit();
+  if (cs != ORBX_OK) return cs;
+  hipError_t e = S.upload(orbx::Staging::Outputs::skipped);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(orbx::osim3::k_debug_exp, dim3((n + 255) / 256), dim3(256), 0, st, (const double*)g.l->d, n,
-                       (double*)(g.l->d + bytes));
+    hipLaunchKernelGGL(orbx::osim3::k_debug_exp, dim3((n + 255) / 256), dim3(256), 0, S.stream(),
+                       (const double*)S.dev(s_x), n, S.dev(s_y));
     e = hipGetLastError();
   }
-  if (e == hipSuccess) e = hipMemcpyAsync(g.l->h + bytes, g.l->d + bytes, bytes, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = g.l->sync();
+  if (e == hipSuccess) e = S.download();
+  if (e == hipSuccess) e = S.sync();
   if (e != hipSuccess) return ORBX_ERR_HIP;
-  std::memcpy(y, g.l->h + bytes, (size_t)n * 8);
+  S.fetch(s_y, y, (size_t)n);
   return ORBX_OK;
 }
 
 extern "C" int orbx_debug_sim3_exp(const double update[7], const double S[8], int fix_scale, double out[8],
                                    int device) {
   if (!update || !S || !out) return ORBX_ERR_ARG;
-  const orbx_status dv = pick_device(device);
+  const orbx_status dv = orbx::select_device(device);
   if (dv != ORBX_OK) return dv;
-  orbx::ScratchGuard g(device);
-  if (!g.l || g.l->reserve(512, 512) != hipSuccess) return ORBX_ERR_HIP;
-  double* h = (double*)g.l->h;
-  std::memcpy(h, update, 56);
-  std::memcpy(h + 7, S, 64);
-  hipStream_t st = g.l->st;
-  hipError_t e = hipMemcpyAsync(g.l->d, g.l->h, 256, hipMemcpyHostToDevice, st);
+  double in[15];  // update | S, as the kernel reads them
+  std::memcpy(in, update, 56);
+  std::memcpy(in + 7, S, 64);
+  orbx::Staging G(device);
+  const auto s_in = G.in(in, 15);
+  const auto s_out = G.out<double>(8);
+  const orbx_status cs = G.commit();
+  if (cs != ORBX_OK) return cs;
+  hipError_t e = G.upload(orbx::Staging::Outputs::skipped);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(orbx::osim3::k_debug_sim3_exp, dim3(1), dim3(64), 0, st, (const double*)g.l->d, fix_scale,
-                       (double*)(g.l->d + 256));
+    hipLaunchKernelGGL(orbx::osim3::k_debug_sim3_exp, dim3(1), dim3(64), 0, G.stream(), (const double*)G.dev(s_in),
+                       fix_scale, G.dev(s_out));
     e = hipGetLastError();
   }
-  if (e == hipSuccess) e = hipMemcpyAsync(g.l->h + 256, g.l->d + 256, 64, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = g.l->sync();
+  if (e == hipSuccess) e = G.download();
+  if (e == hipSuccess) e = G.sync();
   if (e != hipSuccess) return ORBX_ERR_HIP;
-  std::memcpy(out, g.l->h + 256, 64);
+  G.fetch(s_out, out, 8);
   return ORBX_OK;
 }

@@ -10,10 +10,10 @@
 #include <vector>
 
 #include "../../include/orbx.h"
+#include "orbx_scratch.h"
 
 namespace orbx {
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 #define RANSAC_CHECK(x)                          \
   do {                                           \

@@ -755,7 +755,7 @@ __global__ __launch_bounds__(256) void k_pnp_setup(const PnpSetupJob* __restrict
 // stream-ordered allocation (hipMallocAsync) holding all of its arrays.
 namespace {
 
-using orbx::align256;
+using orbx::scratch_align;
 using orbx::RansacDevice;
 
 RansacDevice g_pnp_dev[64];
@@ -800,7 +800,7 @@ struct orbx_pnp {
     size_t o = 0;
     auto take = [&](size_t bytes) {
       uint8_t* p = base ? base + o : nullptr;
-      o += align256(bytes);
+      o += scratch_align(bytes);
       return p;
     };
     d_p3d = (float*)take(12 * nn);
@@ -939,10 +939,10 @@ orbx_status orbx_pnp_create_many(const orbx_pnp_problem* problems, int n, const 
     hs[i] = pnp_new(&problems[i], prm, device);
     if (!hs[i]) return fail(ORBX_ERR_HIP);
     if (hs[i]->alloc(std::max(hs[i]->max_its, 8)) != hipSuccess) return fail(ORBX_ERR_HIP);
-    stage += align256((uint8_t*)hs[i]->d_best - (uint8_t*)hs[i]->d_p3d);
+    stage += scratch_align((uint8_t*)hs[i]->d_best - (uint8_t*)hs[i]->d_p3d);
   }
   // all correspondences in one pinned block, one upload, one gather launch into the solvers' blocks
-  const size_t off_data = align256(n * sizeof(orbx::PnpGatherJob));
+  const size_t off_data = scratch_align(n * sizeof(orbx::PnpGatherJob));
   const size_t bytes = off_data + stage;
   if (dev.pinned_reserve(bytes) != hipSuccess || dev.dstage_reserve(bytes) != hipSuccess) return fail(ORBX_ERR_HIP);
   uint8_t* hp = (uint8_t*)dev.pinned;
@@ -954,7 +954,7 @@ orbx_status orbx_pnp_create_many(const orbx_pnp_problem* problems, int n, const 
     const size_t len = (uint8_t*)h->d_best - (uint8_t*)h->d_p3d;
     if (problems[i].n > 0) pnp_stage_problem(h, &problems[i], prm, hp + o);
     jobs[i] = orbx::PnpGatherJob{dp + o, (uint8_t*)h->d_p3d, problems[i].n > 0 ? (int)len : 0};
-    o += align256(len);
+    o += scratch_align(len);
   }
   hipStream_t st = dev.st;
   if (n == 1) {  // one destination range: uploaded in place, nothing to gather
@@ -1102,9 +1102,9 @@ orbx_status pnp_launch_chunks(RansacDevice& dev, hipStream_t st, std::vector<std
     ncounts += q.second;
     maxc = std::max(maxc, q.second);
   }
-  const size_t off_sets = align256(nj * sizeof(orbx::PnpHypJob));
-  const size_t off_counts = off_sets + align256(nsets * sizeof(int));
-  const size_t bytes = off_counts + align256(ncounts * sizeof(int));
+  const size_t off_sets = scratch_align(nj * sizeof(orbx::PnpHypJob));
+  const size_t off_counts = off_sets + scratch_align(nsets * sizeof(int));
+  const size_t bytes = off_counts + scratch_align(ncounts * sizeof(int));
   RANSAC_CHECK(dev.pinned_reserve(bytes));
   RANSAC_CHECK(dev.dstage_reserve(bytes));
   uint8_t* hp = (uint8_t*)dev.pinned;
@@ -1190,8 +1190,8 @@ orbx_status pnp_read_best(RansacDevice& dev, hipStream_t st, std::vector<PnpRun*
   if (rs.empty()) return ORBX_OK;
   const size_t nj = 2 * rs.size();
   size_t data = 0;
-  for (PnpRun* r : rs) data += 96 + align256((size_t)r->h->N);
-  const size_t off_data = align256(nj * sizeof(orbx::PnpGatherJob));
+  for (PnpRun* r : rs) data += 96 + scratch_align((size_t)r->h->N);
+  const size_t off_data = scratch_align(nj * sizeof(orbx::PnpGatherJob));
   const size_t bytes = off_data + data;
   RANSAC_CHECK(dev.pinned_reserve(bytes));
   RANSAC_CHECK(dev.dstage_reserve(bytes));
@@ -1203,7 +1203,7 @@ orbx_status pnp_read_best(RansacDevice& dev, hipStream_t st, std::vector<PnpRun*
     orbx_pnp* h = rs[j]->h;
     jobs[2 * j] = orbx::PnpGatherJob{(const uint8_t*)rs[j]->best_pose(), dp + o, 96};
     jobs[2 * j + 1] = orbx::PnpGatherJob{rs[j]->best_mask(), dp + o + 96, h->N};
-    o += 96 + align256((size_t)h->N);
+    o += 96 + scratch_align((size_t)h->N);
   }
   RANSAC_CHECK(hipMemcpyAsync(dp, hp, nj * sizeof(orbx::PnpGatherJob), hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(orbx::k_pnp_gather, dim3(nj), dim3(256), 0, st, (const orbx::PnpGatherJob*)dp);
@@ -1217,7 +1217,7 @@ orbx_status pnp_read_best(RansacDevice& dev, hipStream_t st, std::vector<PnpRun*
     std::memcpy(r->out->Tcw, h->best_Tcw, sizeof(float) * 16);
     if (r->inliers) std::memcpy(r->inliers, hp + o + 96, h->N);
     r->read_best = false;
-    o += 96 + align256((size_t)h->N);
+    o += 96 + scratch_align((size_t)h->N);
   }
   rs.clear();
   return ORBX_OK;
@@ -1228,9 +1228,9 @@ orbx_status pnp_refine_round(RansacDevice& dev, hipStream_t st, std::vector<PnpR
   const size_t nj = pend.size();
   // staging: job records | per job 16 doubles (R t, count) | per job its refined mask
   size_t masks = 0;
-  for (PnpRun* r : pend) masks += align256((size_t)r->h->N);
-  const size_t off_res = align256(nj * sizeof(orbx::PnpRefJob));
-  const size_t off_mask = off_res + align256(nj * 16 * sizeof(double));
+  for (PnpRun* r : pend) masks += scratch_align((size_t)r->h->N);
+  const size_t off_res = scratch_align(nj * sizeof(orbx::PnpRefJob));
+  const size_t off_mask = off_res + scratch_align(nj * 16 * sizeof(double));
   const size_t bytes = off_mask + masks;
   RANSAC_CHECK(dev.pinned_reserve(bytes));
   RANSAC_CHECK(dev.dstage_reserve(bytes));
@@ -1251,7 +1251,7 @@ orbx_status pnp_refine_round(RansacDevice& dev, hipStream_t st, std::vector<PnpR
     double* out = (double*)(dp + off_res) + 16 * j;
     moff[j] = mo;
     jobs[j] = orbx::PnpRefJob{h->in(), order[j]->best_mask(), h->d_idx, h->d_rwork, out, dp + mo, (int*)(out + 12)};
-    mo += align256((size_t)h->N);
+    mo += scratch_align((size_t)h->N);
   }
   RANSAC_CHECK(hipMemcpyAsync(dp, hp, nj * sizeof(orbx::PnpRefJob), hipMemcpyHostToDevice, st));
   const orbx::PnpRefJob* dj = (const orbx::PnpRefJob*)dp;

@@ -489,52 +489,46 @@ extern "C" orbx_status orbx_pose_optimization(const orbx_pose_problem* p, int de
   const orbx_status chk = pose_check(*p);
   if (chk != ORBX_OK) return chk;
   if (p->n_dev || p->Tcw_dev) return ORBX_ERR_ARG;  // device batches only
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return ORBX_ERR_NODEV;
-  if (device < 0 || device >= ndev || hipSetDevice(device) != hipSuccess) return ORBX_ERR_ARG;
+  const orbx_status dv = orbx::select_device(device);
+  if (dv != ORBX_OK) return dv;
+  using orbx::Staging;
+  using orbx::pose::PoseDev;
   const size_t n = (size_t)p->n;
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t o_obs = 0, o_X = o_obs + al(n * 12), o_s2 = o_X + al(n * 12), o_Tout = o_s2 + al(n * 4),
-               o_out = o_Tout + al(64), o_ng = o_out + al(n), o_it = o_ng + al(4),
-               o_scr = o_it + al(16), o_act = o_scr + al(n * orbx::pose::kRow * 8), o_dev = o_act + al(n * 4),
-               total = o_dev + al(sizeof(orbx::pose::PoseDev));
-  orbx::ScratchGuard g(device);  // pooled lease: no per-call allocation (orbx_scratch.h)
-  if (!g.l || g.l->reserve(total, o_scr + sizeof(orbx::pose::PoseDev)) != hipSuccess) return ORBX_ERR_HIP;
-  uint8_t* host = g.l->h;
-  std::memset(host, 0, o_scr);  // outputs start zeroed, as before
-  if (n) {
-    std::memcpy(host + o_obs, p->obs, n * 12);
-    std::memcpy(host + o_X, p->Xw, n * 12);
-    std::memcpy(host + o_s2, p->inv_sigma2, n * 4);
-  }
-  uint8_t* d = g.l->d;
-  orbx::pose::PoseDev pd;
+  Staging S(device);  // pooled lease: no per-call allocation (orbx_scratch.h)
+  const auto s_obs = S.in(p->obs, n * 3), s_X = S.in(p->Xw, n * 3), s_s2 = S.in(p->inv_sigma2, n);
+  const auto s_dev = S.record<PoseDev>();
+  const auto s_Tout = S.out<float>(16);
+  const auto s_out = S.out<uint8_t>(n);
+  const auto s_ng = S.out<int32_t>(1), s_it = S.out<int32_t>(4);
+  const auto s_scr = S.device_only<double>(n * orbx::pose::kRow);
+  const auto s_act = S.device_only<int>(n);
+  const orbx_status cs = S.commit();
+  if (cs != ORBX_OK) return cs;
+  PoseDev pd;
   pd.p = *p;
-  pd.p.obs = (const float*)(d + o_obs);
-  pd.p.Xw = (const float*)(d + o_X);
-  pd.p.inv_sigma2 = (const float*)(d + o_s2);
-  pd.p.Tcw_out = (float*)(d + o_Tout);
-  pd.p.outlier = (uint8_t*)(d + o_out);
-  pd.p.ngood = (int32_t*)(d + o_ng);
-  pd.p.iterations = (int32_t*)(d + o_it);
-  pd.scratch = (double*)(d + o_scr);
-  pd.act = (int*)(d + o_act);
-  std::memcpy(host + o_scr, &pd, sizeof(pd));  // the record rides in the staging block's tail
-  hipStream_t st = g.l->st;
-  hipError_t e = hipMemcpyAsync(d, host, o_scr, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d + o_dev, host + o_scr, sizeof(pd), hipMemcpyHostToDevice, st);
+  pd.p.obs = S.dev(s_obs);
+  pd.p.Xw = S.dev(s_X);
+  pd.p.inv_sigma2 = S.dev(s_s2);
+  pd.p.Tcw_out = S.dev(s_Tout);
+  pd.p.outlier = S.dev(s_out);
+  pd.p.ngood = S.dev(s_ng);
+  pd.p.iterations = S.dev(s_it);
+  pd.scratch = S.dev(s_scr);
+  pd.act = S.dev(s_act);
+  S.fill(s_dev, pd);
+  hipError_t e = S.upload(Staging::Outputs::zeroed);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(orbx::pose::k_pose_optimization, dim3(1), dim3(orbx::pose::PBS), 0, st,
-                       (const orbx::pose::PoseDev*)(d + o_dev));
+    hipLaunchKernelGGL(orbx::pose::k_pose_optimization, dim3(1), dim3(orbx::pose::PBS), 0, S.stream(),
+                       (const PoseDev*)S.dev(s_dev));
     e = hipGetLastError();
   }
-  if (e == hipSuccess) e = hipMemcpyAsync(host + o_Tout, d + o_Tout, o_scr - o_Tout, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = g.l->sync();
+  if (e == hipSuccess) e = S.download();
+  if (e == hipSuccess) e = S.sync();
   if (e != hipSuccess) return ORBX_ERR_HIP;
-  std::memcpy(p->Tcw_out, host + o_Tout, 64);
-  if (n) std::memcpy(p->outlier, host + o_out, n);
-  std::memcpy(p->ngood, host + o_ng, 4);
-  if (p->iterations) std::memcpy(p->iterations, host + o_it, 16);
+  S.fetch(s_Tout, p->Tcw_out, 16);
+  S.fetch(s_out, p->outlier, n);
+  S.fetch(s_ng, p->ngood, 1);
+  S.fetch(s_it, p->iterations, 4);
   return ORBX_OK;
 }
 
@@ -547,27 +541,27 @@ extern "C" orbx_status orbx_pose_optimization_device(const orbx_pose_problem* pr
     if (s != ORBX_OK) return s;
     rows += (size_t)problems[i].n;
   }
+  using orbx::pose::PoseDev;
   hipStream_t st = (hipStream_t)stream;
-  const size_t dev_bytes = sizeof(orbx::pose::PoseDev) * n;
-  const size_t scr_off = (dev_bytes + 255) & ~(size_t)255;
+  // the records, then every problem's rows of scratch, then their active lists
+  const size_t dev_bytes = sizeof(PoseDev) * n;
+  const size_t scr_off = orbx::scratch_align(dev_bytes);
   const size_t act_off = scr_off + rows * orbx::pose::kRow * 8;
-  uint8_t* d = nullptr;
-  if (hipMallocAsync((void**)&d, act_off + rows * 4 + 16, st) != hipSuccess) return ORBX_ERR_HIP;
-  std::vector<orbx::pose::PoseDev> pd(n);
-  size_t r = 0;
-  for (int i = 0; i < n; i++) {
-    pd[i].p = problems[i];
-    pd[i].scratch = (double*)(d + scr_off) + r * orbx::pose::kRow;
-    pd[i].act = (int*)(d + act_off) + r;
-    r += (size_t)problems[i].n;
-  }
-  hipError_t e = hipMemcpyAsync(d, pd.data(), dev_bytes, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(orbx::pose::k_pose_optimization, dim3(n), dim3(orbx::pose::PBS), 0, st,
-                       (const orbx::pose::PoseDev*)d);
-    e = hipGetLastError();
-  }
-  // pageable source: hipMemcpyAsync returns once pd is staged, so pd may go
-  const hipError_t e2 = hipFreeAsync(d, st);
-  return e != hipSuccess ? ORBX_ERR_HIP : (e2 != hipSuccess ? ORBX_ERR_HIP : ORBX_OK);
+  return orbx::with_stream_block(act_off + rows * 4 + 16, st, [&](uint8_t* d) {
+    std::vector<PoseDev> pd(n);
+    size_t r = 0;
+    for (int i = 0; i < n; i++) {
+      pd[i].p = problems[i];
+      pd[i].scratch = (double*)(d + scr_off) + r * orbx::pose::kRow;
+      pd[i].act = (int*)(d + act_off) + r;
+      r += (size_t)problems[i].n;
+    }
+    // pageable source: hipMemcpyAsync returns once pd is staged, so pd may go
+    hipError_t e = hipMemcpyAsync(d, pd.data(), dev_bytes, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(orbx::pose::k_pose_optimization, dim3(n), dim3(orbx::pose::PBS), 0, st, (const PoseDev*)d);
+      e = hipGetLastError();
+    }
+    return e;
+  });
 }

@@ -1077,7 +1077,7 @@ inline InitSplit init_split_at(uint8_t* d) {
   size_t o = 0;
   auto take = [&](size_t b) {
     uint8_t* p = d + o;
-    o += (b + 255) & ~(size_t)255;
+    o += scratch_align(b);
     return p;
   };
   InitSplit S;
@@ -1253,104 +1253,91 @@ orbx_status proj_run_host(const orbx_proj_problem* const* ps, int n, int device)
     const orbx_status chk = proj_check(*ps[z], true);
     if (chk != ORBX_OK) return chk;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return ORBX_ERR_NODEV;
-  if (device < 0 || device >= ndev || hipSetDevice(device) != hipSuccess) return ORBX_ERR_ARG;
-  size_t off = 0;
-  struct Item { const void* src; size_t bytes; size_t at; };
-  std::vector<Item> items;
-  auto reserve = [&](const void* src, size_t bytes) -> size_t {
-    off = (off + 255) & ~(size_t)255;
-    items.push_back({src, bytes, off});
-    const size_t at = off;
-    off += bytes;
-    return at;
-  };
+  const orbx_status dv = orbx::select_device(device);
+  if (dv != ORBX_OK) return dv;
+  using orbx::Staging;
+  Staging S(device);  // pooled lease: no per-call allocation (orbx_scratch.h)
   struct Lay {
-    size_t keys, fdesc, ur, occ, desc, flags, pos, nrm, dmm, ang, oct, trk, lvl, fout, pm, nm;
-  };
-  Lay L[2];
+    Staging::Slot<orbx_keypoint> keys;
+    Staging::Slot<uint8_t> fdesc, desc, flags;
+    Staging::Slot<int8_t> occ;
+    Staging::Slot<float> ur, pos, nrm, dmm, ang, trk;
+    Staging::Slot<int32_t> oct, lvl, fout, pm, nm;
+  } L[2];
   for (int z = 0; z < n; z++) {  // inputs
     const orbx_proj_problem* p = ps[z];
     const size_t nF = (size_t)p->f.n, nP = (size_t)p->n_points;
     Lay& a = L[z];
-    a.keys = reserve(p->f.keys_un, nF * sizeof(orbx_keypoint));
-    a.fdesc = reserve(p->f.desc, nF * 32);
-    a.ur = p->f.u_right ? reserve(p->f.u_right, nF * 4) : 0;
-    a.occ = p->f.occ ? reserve(p->f.occ, nF) : 0;
-    a.desc = reserve(p->desc, nP * 32);
-    a.flags = reserve(p->flags, nP);
-    a.pos = p->pos ? reserve(p->pos, nP * 12) : 0;
-    a.nrm = p->normal ? reserve(p->normal, nP * 12) : 0;
-    a.dmm = p->dist_minmax ? reserve(p->dist_minmax, nP * 8) : 0;
-    a.ang = p->angle ? reserve(p->angle, nP * 4) : 0;
-    a.oct = p->octave ? reserve(p->octave, nP * 4) : 0;
+    a.keys = S.in(p->f.keys_un, nF);
+    a.fdesc = S.in(p->f.desc, nF * 32);
+    a.ur = S.in_opt(p->f.u_right, nF);
+    a.occ = S.in_opt(p->f.occ, nF);
+    a.desc = S.in(p->desc, nP * 32);
+    a.flags = S.in(p->flags, nP);
+    a.pos = S.in_opt(p->pos, nP * 3);
+    a.nrm = S.in_opt(p->normal, nP * 3);
+    a.dmm = S.in_opt(p->dist_minmax, nP * 2);
+    a.ang = S.in_opt(p->angle, nP);
+    a.oct = S.in_opt(p->octave, nP);
   }
-  off = (off + 255) & ~(size_t)255;
-  const size_t o_out = off;  // outputs are contiguous from here up to the descriptors
-  for (int z = 0; z < n; z++) {
+  const auto s_prob = S.record<orbx_proj_problem>(n);
+  for (int z = 0; z < n; z++) {  // outputs
     const orbx_proj_problem* p = ps[z];
     const size_t nF = (size_t)p->f.n, nP = (size_t)p->n_points;
-    const bool local = p->kind == ORBX_PROJ_LOCAL;
     Lay& a = L[z];
-    a.trk = local ? reserve(p->frustum ? nullptr : p->track, nP * 16) : 0;  // (in / out)
-    a.lvl = local ? reserve(p->frustum ? nullptr : p->track_level, nP * 4) : 0;
-    a.fout = reserve(nullptr, nF * 4);
-    a.pm = reserve(nullptr, nP * 4);
-    a.nm = reserve(nullptr, 4);
+    if (p->kind == ORBX_PROJ_LOCAL) {  // the isInFrustum results: computed with frustum, else given
+      a.trk = S.inout(p->frustum ? nullptr : p->track, nP * 4);
+      a.lvl = S.inout(p->frustum ? nullptr : p->track_level, nP);
+    }
+    a.fout = S.out<int32_t>(nF);
+    a.pm = S.out<int32_t>(nP);
+    a.nm = S.out<int32_t>(1);
   }
-  const size_t a_prob = reserve(nullptr, sizeof(orbx_proj_problem) * n);
-  const size_t a_split = reserve(nullptr, orbx::kProjSplitBytes * n);  // device-only scratch (not copied)
-  orbx::ScratchGuard g(device);  // pooled lease: no per-call allocation (orbx_scratch.h)
-  if (!g.l || g.l->reserve(off, off) != hipSuccess) return ORBX_ERR_HIP;
-  uint8_t* hst = g.l->h;
-  std::memset(hst, 0, a_split);
-  for (const Item& it : items)
-    if (it.src && it.bytes) std::memcpy(hst + it.at, it.src, it.bytes);
-  uint8_t* d = g.l->d;
+  const auto s_split = S.device_only<uint8_t>(orbx::kProjSplitBytes * n);  // problem z's at z * kProjSplitBytes
+  const orbx_status cs = S.commit();
+  if (cs != ORBX_OK) return cs;
   int kinds[2], nPs[2];
   for (int z = 0; z < n; z++) {
     const orbx_proj_problem* p = ps[z];
     const Lay& a = L[z];
-    const bool local = p->kind == ORBX_PROJ_LOCAL;
     orbx_proj_problem q = *p;
-    q.f.keys_un = (const orbx_keypoint*)(d + a.keys);
-    q.f.desc = d + a.fdesc;
-    q.f.u_right = p->f.u_right ? (const float*)(d + a.ur) : nullptr;
-    q.f.occ = p->f.occ ? (const int8_t*)(d + a.occ) : nullptr;
-    q.desc = d + a.desc;
-    q.flags = d + a.flags;
-    q.pos = p->pos ? (const float*)(d + a.pos) : nullptr;
-    q.normal = p->normal ? (const float*)(d + a.nrm) : nullptr;
-    q.dist_minmax = p->dist_minmax ? (const float*)(d + a.dmm) : nullptr;
-    q.angle = p->angle ? (const float*)(d + a.ang) : nullptr;
-    q.octave = p->octave ? (const int32_t*)(d + a.oct) : nullptr;
-    q.track = local ? (float*)(d + a.trk) : nullptr;
-    q.track_level = local ? (int32_t*)(d + a.lvl) : nullptr;
-    q.frame_out = (int32_t*)(d + a.fout);
-    q.point_match = (int32_t*)(d + a.pm);
-    q.nmatches = (int32_t*)(d + a.nm);
-    std::memcpy(hst + a_prob + z * sizeof(orbx_proj_problem), &q, sizeof(q));
+    q.f.keys_un = S.dev(a.keys);
+    q.f.desc = S.dev(a.fdesc);
+    q.f.u_right = S.dev(a.ur);
+    q.f.occ = S.dev(a.occ);
+    q.desc = S.dev(a.desc);
+    q.flags = S.dev(a.flags);
+    q.pos = S.dev(a.pos);
+    q.normal = S.dev(a.nrm);
+    q.dist_minmax = S.dev(a.dmm);
+    q.angle = S.dev(a.ang);
+    q.octave = S.dev(a.oct);
+    q.track = S.dev(a.trk);
+    q.track_level = S.dev(a.lvl);
+    q.frame_out = S.dev(a.fout);
+    q.point_match = S.dev(a.pm);
+    q.nmatches = S.dev(a.nm);
+    S.fill(s_prob, q, z);
     kinds[z] = p->kind;
     nPs[z] = p->n_points;
   }
-  hipStream_t st = g.l->st;
-  hipError_t e = hipMemcpyAsync(d, hst, a_split, hipMemcpyHostToDevice, st);
+  hipError_t e = S.upload(Staging::Outputs::zeroed);
   if (e == hipSuccess)
-    e = orbx::launch_search_by_projection_split((const orbx::ProjProblem*)(d + a_prob), kinds, nPs, n, d + a_split, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(hst + o_out, d + o_out, a_prob - o_out, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = g.l->sync();
+    e = orbx::launch_search_by_projection_split((const orbx::ProjProblem*)S.dev(s_prob), kinds, nPs, n,
+                                                S.dev(s_split), S.stream());
+  if (e == hipSuccess) e = S.download();
+  if (e == hipSuccess) e = S.sync();
   if (e != hipSuccess) return proj_status(e);
   for (int z = 0; z < n; z++) {
     const orbx_proj_problem* p = ps[z];
     const Lay& a = L[z];
-    const size_t nF = (size_t)p->f.n, nP = (size_t)p->n_points;
-    if (nF) std::memcpy(p->frame_out, hst + a.fout, nF * 4);
-    if (nP) std::memcpy(p->point_match, hst + a.pm, nP * 4);
-    std::memcpy(p->nmatches, hst + a.nm, 4);
-    if (p->kind == ORBX_PROJ_LOCAL && p->frustum && nP) {
-      std::memcpy(p->track, hst + a.trk, nP * 16);
-      std::memcpy(p->track_level, hst + a.lvl, nP * 4);
+    const size_t nP = (size_t)p->n_points;
+    S.fetch(a.fout, p->frame_out, (size_t)p->f.n);
+    S.fetch(a.pm, p->point_match, nP);
+    S.fetch(a.nm, p->nmatches, 1);
+    if (p->kind == ORBX_PROJ_LOCAL && p->frustum) {
+      S.fetch(a.trk, p->track, nP * 4);
+      S.fetch(a.lvl, p->track_level, nP);
     }
   }
   return ORBX_OK;
@@ -1370,12 +1357,11 @@ extern "C" orbx_status orbx_search_by_projection_device(const orbx_proj_problem*
     if (s != ORBX_OK) return s;
   }
   hipStream_t st = (hipStream_t)stream;
-  orbx::ProjProblem* dP = nullptr;
-  if (hipMallocAsync((void**)&dP, sizeof(orbx::ProjProblem) * n, st) != hipSuccess) return ORBX_ERR_HIP;
-  hipError_t e = hipMemcpyAsync(dP, problems, sizeof(orbx::ProjProblem) * n, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = orbx::launch_search_by_projection(dP, n, st);
-  const hipError_t e2 = hipFreeAsync(dP, st);
-  return proj_status(e != hipSuccess ? e : e2);
+  const size_t bytes = sizeof(orbx::ProjProblem) * n;
+  return orbx::with_stream_block(bytes, st, [&](uint8_t* d) {
+    const hipError_t e = hipMemcpyAsync(d, problems, bytes, hipMemcpyHostToDevice, st);
+    return e != hipSuccess ? e : orbx::launch_search_by_projection((const orbx::ProjProblem*)d, n, st);
+  });
 }
 
 namespace {
@@ -1456,58 +1442,41 @@ extern "C" orbx_status orbx_search_for_initialization(const orbx_init_problem* p
   if (p->window < 0) return ORBX_ERR_ARG;
   for (int i = 0; i < n1; i++)
     if (p->f1.keys_un[i].octave < 0) return ORBX_ERR_ARG;  // GetFeaturesInArea(.., level1, level1) needs level1 >= 0
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return ORBX_ERR_NODEV;
-  if (device < 0 || device >= ndev || hipSetDevice(device) != hipSuccess) return ORBX_ERR_ARG;
-  size_t off = 0;
-  auto at = [&](size_t bytes) {
-    off = (off + 255) & ~(size_t)255;
-    const size_t a = off;
-    off += bytes;
-    return a;
-  };
-  const size_t a_k1 = at((size_t)n1 * sizeof(orbx_keypoint)), a_d1 = at((size_t)n1 * 32);
-  const size_t a_k2 = at((size_t)n2 * sizeof(orbx_keypoint)), a_d2 = at((size_t)n2 * 32);
-  const size_t a_prev = at((size_t)n1 * 8), a_m = at((size_t)n1 * 4 + 4), a_nm = at(4);
-  const size_t a_prob = at(sizeof(orbx_init_problem));
-  const size_t a_split = at(orbx::kInitSplitBytes);  // device-only scratch
-  orbx::ScratchGuard g(device);
-  if (!g.l || g.l->reserve(off, off) != hipSuccess) return ORBX_ERR_HIP;
-  uint8_t* h = g.l->h;
-  uint8_t* d = g.l->d;
-  std::memset(h, 0, a_split);
-  if (n1) {
-    std::memcpy(h + a_k1, p->f1.keys_un, (size_t)n1 * sizeof(orbx_keypoint));
-    std::memcpy(h + a_d1, p->f1.desc, (size_t)n1 * 32);
-    std::memcpy(h + a_prev, p->prev_matched, (size_t)n1 * 8);
-  }
-  if (n2) {
-    std::memcpy(h + a_k2, p->f2.keys_un, (size_t)n2 * sizeof(orbx_keypoint));
-    std::memcpy(h + a_d2, p->f2.desc, (size_t)n2 * 32);
-  }
+  const orbx_status dv = orbx::select_device(device);
+  if (dv != ORBX_OK) return dv;
+  using orbx::Staging;
+  Staging A(device);
+  const auto s_k1 = A.in(p->f1.keys_un, (size_t)n1), s_k2 = A.in(p->f2.keys_un, (size_t)n2);
+  const auto s_d1 = A.in(p->f1.desc, (size_t)n1 * 32), s_d2 = A.in(p->f2.desc, (size_t)n2 * 32);
+  const auto s_prob = A.record<orbx_init_problem>();
+  const auto s_prev = A.inout(p->prev_matched, (size_t)n1 * 2);
+  const auto s_m = A.out<int32_t>((size_t)n1 + 1), s_nm = A.out<int32_t>(1);
+  const auto s_split = A.device_only<uint8_t>(orbx::kInitSplitBytes);
+  const orbx_status cs = A.commit();
+  if (cs != ORBX_OK) return cs;
   orbx_init_problem q = *p;
-  q.f1.keys_un = (const orbx_keypoint*)(d + a_k1);
-  q.f1.desc = d + a_d1;
-  q.f2.keys_un = (const orbx_keypoint*)(d + a_k2);
-  q.f2.desc = d + a_d2;
+  q.f1.keys_un = A.dev(s_k1);
+  q.f1.desc = A.dev(s_d1);
+  q.f2.keys_un = A.dev(s_k2);
+  q.f2.desc = A.dev(s_d2);
   q.f1.u_right = q.f2.u_right = nullptr;
   q.f1.occ = q.f2.occ = nullptr;
-  q.prev_matched = (float*)(d + a_prev);
-  q.match12 = (int32_t*)(d + a_m);
-  q.nmatches = (int32_t*)(d + a_nm);
-  std::memcpy(h + a_prob, &q, sizeof(q));
-  hipStream_t st = g.l->st;
+  q.prev_matched = A.dev(s_prev);
+  q.match12 = A.dev(s_m);
+  q.nmatches = A.dev(s_nm);
+  A.fill(s_prob, q);
+  hipStream_t st = A.stream();
   const size_t smem = orbx::init_smem_bytes(n1, n2);
   // the dynamic LDS reaches ~79 KB at 8192 features (above the 64 KB default)
   hipError_t e = hipSuccess;
   for (const void* k : {(const void*)orbx::k_init_split_prep, (const void*)orbx::k_init_split_sweep,
                         (const void*)orbx::k_init_split_list, (const void*)orbx::k_init_split_final})
     if (e == hipSuccess) e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  if (e == hipSuccess) e = hipMemcpyAsync(d, h, a_split, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = A.upload(Staging::Outputs::zeroed);
   if (e == hipSuccess) {
     // one problem over many blocks: ~64 F1 keypoints per block per sweep
-    const orbx_init_problem* dp = (const orbx_init_problem*)(d + a_prob);
-    const orbx::InitSplit S = orbx::init_split_at(d + a_split);
+    const orbx_init_problem* dp = A.dev(s_prob);
+    const orbx::InitSplit S = orbx::init_split_at(A.dev(s_split));
     const int nb = std::min(64, std::max(1, (n1 + orbx::IBS / orbx::kGroup - 1) / (orbx::IBS / orbx::kGroup)));
     hipLaunchKernelGGL(orbx::k_init_split_prep, dim3(1), dim3(orbx::IBS), smem, st, dp, S);
     for (int s = 0; s < orbx::kInitSplitSweeps; s++) {
@@ -1517,13 +1486,11 @@ extern "C" orbx_status orbx_search_for_initialization(const orbx_init_problem* p
     hipLaunchKernelGGL(orbx::k_init_split_final, dim3(1), dim3(orbx::IBS), smem, st, dp, S);
     e = hipGetLastError();
   }
-  if (e == hipSuccess) e = hipMemcpyAsync(h + a_prev, d + a_prev, a_prob - a_prev, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = g.l->sync();
+  if (e == hipSuccess) e = A.download();
+  if (e == hipSuccess) e = A.sync();
   if (e != hipSuccess) return ORBX_ERR_HIP;
-  if (n1) {
-    std::memcpy(p->prev_matched, h + a_prev, (size_t)n1 * 8);
-    std::memcpy(p->match12, h + a_m, (size_t)n1 * 4);
-  }
-  std::memcpy(p->nmatches, h + a_nm, 4);
+  A.fetch(s_prev, p->prev_matched, (size_t)n1 * 2);
+  A.fetch(s_m, p->match12, (size_t)n1);
+  A.fetch(s_nm, p->nmatches, 1);
   return ORBX_OK;
 }

@@ -73,4 +73,25 @@ void scratch_release(ScratchLease* l) {
   p.free.push_back(l);
 }
 
+orbx_status select_device(int device) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return ORBX_ERR_NODEV;
+  if (device < 0 || device >= ndev || hipSetDevice(device) != hipSuccess) return ORBX_ERR_ARG;
+  return ORBX_OK;
+}
+
+orbx_status Staging::commit() {
+  if (bad_) return ORBX_ERR_ARG;
+  if (!l_) l_ = scratch_acquire(device_);
+  if (!l_ || l_->reserve(device_bytes(), pinned_bytes()) != hipSuccess) return ORBX_ERR_HIP;
+  std::memset(l_->h + outputs_begin(), 0, outputs_end() - outputs_begin());
+  for (const Copy& c : copies_) {
+    if (c.src)
+      std::memcpy(l_->h + c.off, c.src, c.bytes);
+    else
+      std::memset(l_->h + c.off, 0, c.bytes);
+  }
+  return ORBX_OK;
+}
+
 }  // namespace orbx

@@ -576,7 +576,7 @@ struct orbx_sim3 {
     size_t o = 0;
     auto take = [&](size_t bytes) {
       uint8_t* p = base ? base + o : nullptr;
-      o += orbx::align256(bytes);
+      o += orbx::scratch_align(bytes);
       return p;
     };
     d_x1 = (float*)take(12 * nn);
@@ -701,29 +701,29 @@ orbx_status sim3_run(std::vector<Sim3Run>& runs, bool shared, uint8_t* const* in
   orbx::RansacDevice& dev = g_sim3_dev[device];
   hipStream_t st = dev.st;
   // staging layout: [jobs | sets] uploaded, [hyps | masks | counts] device only, [recs + masks] read back
-  const size_t off_sets = orbx::align256(sizeof(Sim3Job) * (size_t)n);
+  const size_t off_sets = orbx::scratch_align(sizeof(Sim3Job) * (size_t)n);
   size_t o = off_sets;
   std::vector<size_t> o_sets(n), o_hyps(n), o_masks(n), o_counts(n), o_rec(n);
   int Hmax = 0;
   for (int i = 0; i < n; i++) {
     o_sets[i] = o;
-    o += orbx::align256(sizeof(int) * 3 * (size_t)runs[i].H);
+    o += orbx::scratch_align(sizeof(int) * 3 * (size_t)runs[i].H);
     Hmax = std::max(Hmax, runs[i].H);
   }
   const size_t up_bytes = o;
   for (int i = 0; i < n; i++) {
     const size_t H = runs[i].H, N = std::max(runs[i].h->N, 1);
     o_hyps[i] = o;
-    o += orbx::align256(sizeof(Sim3Hyp) * H);
+    o += orbx::scratch_align(sizeof(Sim3Hyp) * H);
     o_masks[i] = o;
-    o += orbx::align256(H * N);
+    o += orbx::scratch_align(H * N);
     o_counts[i] = o;
-    o += orbx::align256(sizeof(int) * H);
+    o += orbx::scratch_align(sizeof(int) * H);
   }
   const size_t off_back = o;
   for (int i = 0; i < n; i++) {
     o_rec[i] = o;
-    o += orbx::align256(sizeof(Sim3Rec) + (size_t)std::max(runs[i].h->N, 1));
+    o += orbx::scratch_align(sizeof(Sim3Rec) + (size_t)std::max(runs[i].h->N, 1));
   }
   const size_t total = o, back_bytes = total - off_back;
   RANSAC_CHECK(dev.dstage_reserve(total));
@@ -837,7 +837,7 @@ orbx_status orbx_sim3_create_many(const orbx_sim3_solver_problem* problems, int 
     stage += hs[i]->upload_bytes();
   }
   // every solver's correspondences in one pinned block, one upload, one gather launch
-  const size_t off_data = orbx::align256(sizeof(Sim3GatherJob) * (size_t)n);
+  const size_t off_data = orbx::scratch_align(sizeof(Sim3GatherJob) * (size_t)n);
   const size_t bytes = off_data + stage;
   if (dev.pinned_reserve(bytes) != hipSuccess || dev.dstage_reserve(bytes) != hipSuccess) return fail(ORBX_ERR_HIP);
   uint8_t* hp = (uint8_t*)dev.pinned;

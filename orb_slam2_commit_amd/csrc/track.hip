@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/orbx.h"
+#include "orbx_scratch.h"
 
 namespace orbx {
 namespace track {
@@ -212,6 +213,23 @@ __global__ __launch_bounds__(TBS) void k_track_step(const orbx_track_step* __res
 }  // namespace track
 }  // namespace orbx
 
+namespace {
+// the n descriptors in a stream-ordered block and the one launch over them
+template <class T>
+orbx_status run_batch(void (*kernel)(const T*), dim3 grid, const T* problems, int n, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const size_t bytes = sizeof(T) * n;
+  return orbx::with_stream_block(bytes, st, [&](uint8_t* d) {
+    hipError_t e = hipMemcpyAsync(d, problems, bytes, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(kernel, grid, dim3(orbx::track::TBS), 0, st, (const T*)d);
+      e = hipGetLastError();
+    }
+    return e;
+  });
+}
+}  // namespace
+
 extern "C" orbx_status orbx_track_gather_device(const orbx_track_gather* problems, int n, void* stream) {
   if (n < 0 || (n > 0 && !problems)) return ORBX_ERR_ARG;
   if (n == 0) return ORBX_OK;
@@ -221,16 +239,7 @@ extern "C" orbx_status orbx_track_gather_device(const orbx_track_gather* problem
         !p.inv_sigma2 || !p.n_edges || p.fx == 0.0f || p.fy == 0.0f)
       return ORBX_ERR_ARG;
   }
-  hipStream_t st = (hipStream_t)stream;
-  orbx_track_gather* d = nullptr;
-  if (hipMallocAsync((void**)&d, sizeof(orbx_track_gather) * n, st) != hipSuccess) return ORBX_ERR_HIP;
-  hipError_t e = hipMemcpyAsync(d, problems, sizeof(orbx_track_gather) * n, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(orbx::track::k_track_gather, dim3(n), dim3(orbx::track::TBS), 0, st, d);
-    e = hipGetLastError();
-  }
-  const hipError_t e2 = hipFreeAsync(d, st);
-  return (e == hipSuccess && e2 == hipSuccess) ? ORBX_OK : ORBX_ERR_HIP;
+  return run_batch(orbx::track::k_track_gather, dim3(n), problems, n, stream);
 }
 
 extern "C" orbx_status orbx_frame_points_device(const orbx_frame_points* problems, int n, void* stream) {
@@ -244,17 +253,8 @@ extern "C" orbx_status orbx_frame_points_device(const orbx_frame_points* problem
       return ORBX_ERR_ARG;
     cap = p.cap > cap ? p.cap : cap;
   }
-  hipStream_t st = (hipStream_t)stream;
-  orbx_frame_points* d = nullptr;
-  if (hipMallocAsync((void**)&d, sizeof(orbx_frame_points) * n, st) != hipSuccess) return ORBX_ERR_HIP;
-  hipError_t e = hipMemcpyAsync(d, problems, sizeof(orbx_frame_points) * n, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(orbx::track::k_frame_points, dim3((cap + orbx::track::TBS - 1) / orbx::track::TBS, n),
-                       dim3(orbx::track::TBS), 0, st, d);
-    e = hipGetLastError();
-  }
-  const hipError_t e2 = hipFreeAsync(d, st);
-  return (e == hipSuccess && e2 == hipSuccess) ? ORBX_OK : ORBX_ERR_HIP;
+  return run_batch(orbx::track::k_frame_points, dim3((cap + orbx::track::TBS - 1) / orbx::track::TBS, n), problems, n,
+                   stream);
 }
 
 extern "C" orbx_status orbx_track_step_device(const orbx_track_step* problems, int n, void* stream) {
@@ -274,14 +274,5 @@ extern "C" orbx_status orbx_track_step_device(const orbx_track_step* problems, i
         (!p.outlier || !p.ngood || !p.edge_feature || !p.seen || !p.flags || !p.local_flags || !p.occ))
       return ORBX_ERR_ARG;
   }
-  hipStream_t st = (hipStream_t)stream;
-  orbx_track_step* d = nullptr;
-  if (hipMallocAsync((void**)&d, sizeof(orbx_track_step) * n, st) != hipSuccess) return ORBX_ERR_HIP;
-  hipError_t e = hipMemcpyAsync(d, problems, sizeof(orbx_track_step) * n, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(orbx::track::k_track_step, dim3(n), dim3(orbx::track::TBS), 0, st, d);
-    e = hipGetLastError();
-  }
-  const hipError_t e2 = hipFreeAsync(d, st);
-  return (e == hipSuccess && e2 == hipSuccess) ? ORBX_OK : ORBX_ERR_HIP;
+  return run_batch(orbx::track::k_track_step, dim3(n), problems, n, stream);
 }

@@ -234,68 +234,57 @@ extern "C" orbx_status orbx_search_for_triangulation(const orbx_tri_problem* p, 
     for (int i = 0; i < k.n; i++)
       if (k.keys_un[i].octave < 0 || k.keys_un[i].octave > 15) return ORBX_ERR_ARG;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return ORBX_ERR_NODEV;
-  if (device < 0 || device >= ndev || hipSetDevice(device) != hipSuccess) return ORBX_ERR_ARG;
-  size_t off = 0;
-  struct Item { const void* src; size_t bytes; size_t at; };
-  std::vector<Item> items;
-  auto put = [&](const void* src, size_t bytes) -> size_t {
-    off = (off + 255) & ~(size_t)255;
-    items.push_back({src, bytes, off});
-    const size_t at = off;
-    off += bytes;
-    return at;
-  };
-  size_t a[2][8];
+  const orbx_status dv = orbx::select_device(device);
+  if (dv != ORBX_OK) return dv;
+  using orbx::Staging;
+  Staging S(device);  // pooled lease: no per-call allocation (orbx_scratch.h)
+  struct Side {
+    Staging::Slot<orbx_keypoint> keys;
+    Staging::Slot<uint8_t> desc, has_mp;
+    Staging::Slot<float> ur;
+    Staging::Slot<uint32_t> node_id;
+    Staging::Slot<int32_t> node_off, feat;
+  } a[2];
   for (int s = 0; s < 2; s++) {
     const orbx_tri_kf& k = s ? p->kf2 : p->kf1;
-    const size_t nf = k.n_nodes ? (size_t)k.node_off[k.n_nodes] : 0;
-    a[s][0] = put(k.keys_un, (size_t)k.n * sizeof(orbx_keypoint));
-    a[s][1] = put(k.desc, (size_t)k.n * 32);
-    a[s][2] = k.u_right ? put(k.u_right, (size_t)k.n * 4) : 0;
-    a[s][3] = k.has_mp ? put(k.has_mp, (size_t)k.n) : 0;
-    a[s][4] = put(k.node_id, (size_t)k.n_nodes * 4);
-    a[s][5] = put(k.node_off, (size_t)(k.n_nodes + 1) * 4);
-    a[s][6] = put(k.feat, nf * 4);
+    const size_t n = (size_t)k.n, nn = (size_t)k.n_nodes;
+    a[s].keys = S.in(k.keys_un, n);
+    a[s].desc = S.in(k.desc, n * 32);
+    a[s].ur = S.in_opt(k.u_right, n);
+    a[s].has_mp = S.in_opt(k.has_mp, n);
+    a[s].node_id = S.in(k.node_id, nn);
+    a[s].node_off = S.in(k.node_off, nn + 1);
+    a[s].feat = S.in(k.feat, nn ? (size_t)k.node_off[nn] : 0);
   }
-  const size_t a_m = put(nullptr, (size_t)p->kf1.n * 4), a_n = put(nullptr, 4);
-  const size_t a_p = put(nullptr, sizeof(orbx_tri_problem));
-  orbx::ScratchGuard g(device);  // pooled lease: no per-call allocation (orbx_scratch.h)
-  if (!g.l || g.l->reserve(off, off) != hipSuccess) return ORBX_ERR_HIP;
-  uint8_t* hst = g.l->h;
-  std::memset(hst, 0, off);
-  for (const Item& it : items)
-    if (it.src && it.bytes) std::memcpy(hst + it.at, it.src, it.bytes);
-  uint8_t* d = g.l->d;
+  const auto s_p = S.record<orbx_tri_problem>();
+  const auto s_m = S.out<int32_t>((size_t)p->kf1.n), s_n = S.out<int32_t>(1);
+  const orbx_status cs = S.commit();
+  if (cs != ORBX_OK) return cs;
   orbx_tri_problem q = *p;
   for (int s = 0; s < 2; s++) {
-    const orbx_tri_kf& k = s ? p->kf2 : p->kf1;
     orbx_tri_kf& o = s ? q.kf2 : q.kf1;
-    o.keys_un = (const orbx_keypoint*)(d + a[s][0]);
-    o.desc = d + a[s][1];
-    o.u_right = k.u_right ? (const float*)(d + a[s][2]) : nullptr;
-    o.has_mp = k.has_mp ? d + a[s][3] : nullptr;
-    o.node_id = (const uint32_t*)(d + a[s][4]);
-    o.node_off = (const int32_t*)(d + a[s][5]);
-    o.feat = (const int32_t*)(d + a[s][6]);
+    o.keys_un = S.dev(a[s].keys);
+    o.desc = S.dev(a[s].desc);
+    o.u_right = S.dev(a[s].ur);
+    o.has_mp = S.dev(a[s].has_mp);
+    o.node_id = S.dev(a[s].node_id);
+    o.node_off = S.dev(a[s].node_off);
+    o.feat = S.dev(a[s].feat);
   }
-  q.match12 = (int32_t*)(d + a_m);
-  q.nmatches = (int32_t*)(d + a_n);
-  std::memcpy(hst + a_p, &q, sizeof(q));
-  hipStream_t st = g.l->st;
-  hipError_t e = hipMemcpyAsync(d, hst, off, hipMemcpyHostToDevice, st);
+  q.match12 = S.dev(s_m);
+  q.nmatches = S.dev(s_n);
+  S.fill(s_p, q);
+  hipError_t e = S.upload(Staging::Outputs::zeroed);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(orbx::tri::k_search_for_triangulation, dim3(1), dim3(orbx::tri::TBS), 0, st,
-                       (const orbx_tri_problem*)(d + a_p));
+    hipLaunchKernelGGL(orbx::tri::k_search_for_triangulation, dim3(1), dim3(orbx::tri::TBS), 0, S.stream(),
+                       (const orbx_tri_problem*)S.dev(s_p));
     e = hipGetLastError();
   }
-  // match12 and the count are adjacent: one copy back
-  if (e == hipSuccess) e = hipMemcpyAsync(hst + a_m, d + a_m, a_p - a_m, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = g.l->sync();
+  if (e == hipSuccess) e = S.download();
+  if (e == hipSuccess) e = S.sync();
   if (e != hipSuccess) return ORBX_ERR_HIP;
-  if (p->kf1.n) std::memcpy(p->match12, hst + a_m, (size_t)p->kf1.n * 4);
-  std::memcpy(p->nmatches, hst + a_n, 4);
+  S.fetch(s_m, p->match12, (size_t)p->kf1.n);
+  S.fetch(s_n, p->nmatches, 1);
   return ORBX_OK;
 }
 
@@ -305,13 +294,14 @@ extern "C" orbx_status orbx_search_for_triangulation_device(const orbx_tri_probl
   for (int i = 0; i < n; i++)
     if (tri_check(problems[i]) != ORBX_OK) return ORBX_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
-  orbx_tri_problem* dP = nullptr;
-  if (hipMallocAsync((void**)&dP, sizeof(orbx_tri_problem) * n, st) != hipSuccess) return ORBX_ERR_HIP;
-  hipError_t e = hipMemcpyAsync(dP, problems, sizeof(orbx_tri_problem) * n, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(orbx::tri::k_search_for_triangulation, dim3(n), dim3(orbx::tri::TBS), 0, st, dP);
-    e = hipGetLastError();
-  }
-  const hipError_t e2 = hipFreeAsync(dP, st);
-  return (e != hipSuccess || e2 != hipSuccess) ? ORBX_ERR_HIP : ORBX_OK;
+  const size_t bytes = sizeof(orbx_tri_problem) * n;
+  return orbx::with_stream_block(bytes, st, [&](uint8_t* d) {
+    hipError_t e = hipMemcpyAsync(d, problems, bytes, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(orbx::tri::k_search_for_triangulation, dim3(n), dim3(orbx::tri::TBS), 0, st,
+                         (const orbx_tri_problem*)d);
+      e = hipGetLastError();
+    }
+    return e;
+  });
 }

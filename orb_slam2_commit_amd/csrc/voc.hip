@@ -282,7 +282,7 @@ struct orbx_voc {
 
 namespace {
 
-inline size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
+using orbx::scratch_align;
 
 // one integer token; false at end of line
 bool next_int(const char*& p, const char* e, long* out) {
@@ -378,8 +378,8 @@ orbx_status orbx_voc_load_text(const char* text, size_t len, int device, orbx_vo
   v->n_nodes = n;
   v->n_words = n_words;
   v->empty = child_off[1] == 0;
-  const size_t b_desc = a256(32 * (size_t)n), b_w = a256(8 * (size_t)n), b_word = a256(4 * (size_t)n),
-               b_off = a256(4 * (size_t)(n + 1)), b_child = a256(4 * child.size());
+  const size_t b_desc = scratch_align(32 * (size_t)n), b_w = scratch_align(8 * (size_t)n), b_word = scratch_align(4 * (size_t)n),
+               b_off = scratch_align(4 * (size_t)(n + 1)), b_child = scratch_align(4 * child.size());
   std::vector<uint8_t> stage(b_desc + b_w + b_word + b_off + b_child);
   std::memcpy(stage.data(), desc.data(), 32 * (size_t)n);
   std::memcpy(stage.data() + b_desc, weight.data(), 8 * (size_t)n);
@@ -454,9 +454,9 @@ orbx_status orbx_voc_transform(orbx_voc* v, const uint8_t* desc, const int32_t* 
   if (hipSetDevice(v->device) != hipSuccess) return ORBX_ERR_HIP;
   // device scratch: desc | set_off | word | weight | nid | outputs
   const size_t nt = (size_t)total, ns = (size_t)n_sets;
-  const size_t b_desc = a256(32 * nt), b_soff = a256(4 * (ns + 1)), b_word = a256(4 * nt), b_w = a256(8 * nt),
-               b_nid = a256(4 * nt), b_bw = a256(4 * nt), b_bv = a256(8 * nt), b_nb = a256(4 * ns),
-               b_fn = a256(4 * nt), b_fo = a256(4 * (nt + ns)), b_ff = a256(4 * nt), b_nf = a256(4 * ns);
+  const size_t b_desc = scratch_align(32 * nt), b_soff = scratch_align(4 * (ns + 1)), b_word = scratch_align(4 * nt), b_w = scratch_align(8 * nt),
+               b_nid = scratch_align(4 * nt), b_bw = scratch_align(4 * nt), b_bv = scratch_align(8 * nt), b_nb = scratch_align(4 * ns),
+               b_fn = scratch_align(4 * nt), b_fo = scratch_align(4 * (nt + ns)), b_ff = scratch_align(4 * nt), b_nf = scratch_align(4 * ns);
   const size_t need = b_desc + b_soff + b_word + b_w + b_nid + b_bw + b_bv + b_nb + b_fn + b_fo + b_ff + b_nf;
   // a per-call lease (own stream + arena): concurrent callers never share scratch
   orbx::ScratchGuard g(v->device);
@@ -528,7 +528,7 @@ orbx_status orbx_voc_transform_device(orbx_voc* v, const uint8_t* d_desc, int ca
   hipStream_t st = stream == ORBX_STREAM_NULL ? (hipStream_t)0 : stream ? (hipStream_t)stream : v->st;
   const size_t nt = (size_t)n_sets * cap;
   if (nt > (size_t)0x7FFFFFFF) return ORBX_ERR_SIZE;
-  const size_t need = a256(4 * nt) + a256(8 * nt) + a256(4 * nt);  // word | weight | nid
+  const size_t need = scratch_align(4 * nt) + scratch_align(8 * nt) + scratch_align(4 * nt);  // word | weight | nid
   // stream-ordered scratch on the caller's stream: freed after k_voc_build in stream order, so a
   // later call (any thread, any stream) can never overwrite what a queued build still reads
   int P = 1;
@@ -540,8 +540,8 @@ orbx_status orbx_voc_transform_device(orbx_voc* v, const uint8_t* d_desc, int ca
   uint8_t* w = nullptr;
   VOC_CHECK(hipMallocAsync((void**)&w, need, st));
   int* d_word = (int*)w;
-  double* d_wt = (double*)(w + a256(4 * nt));
-  int* d_nid = (int*)(w + a256(4 * nt) + a256(8 * nt));
+  double* d_wt = (double*)(w + scratch_align(4 * nt));
+  int* d_nid = (int*)(w + scratch_align(4 * nt) + scratch_align(8 * nt));
   orbx::VocSetOut O{d_bow_words, d_bow_values, d_n_bow, d_fv_nodes, d_fv_off, d_fv_feat, d_n_fv};
   hipLaunchKernelGGL(orbx::k_voc_descend, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, v->dev,
                      (const uint64_t*)d_desc, (int)nt, levelsup, d_word, d_wt, d_nid, d_count, cap, stride,

@@ -3,7 +3,9 @@ F8-F8e): the problem struct is built once over host arrays, then only the C call
 arrays in and out, PCIe included), median of `reps` calls after warm-up.  The per-frame members
 (SearchByProjection(F, MPs) / (F, LastF) / (F, KF)) at 2,000 features / 3,000 points, the KeyFrame
 ones (Fuse, the Sim3 projections, SearchBySim3, SearchForInitialization) at the sizes of
-tools/matcher_time.py.  Usage: python tools/matcher_latency.py [reps] > profiles/r05_matcher_time.json"""
+tools/matcher_time.py; then the other host forms that stage through orbx::Staging and no other tool
+times per call (SearchForTriangulation, SearchByBoW, ComputeDistinctiveDescriptors, UndistortKeyPoints,
+PoseOptimization at 1000 edges) through their Python mirrors.  Usage: python tools/matcher_latency.py [reps] > profiles/r05_matcher_time.json"""
 import ctypes as C
 import json
 import os
@@ -59,6 +61,30 @@ def main(reps=50):
     kf1, kf2, p1, p2, s, R12, t12 = _sim3_pair_case(950, n=2000, s12=1.1)
     md, p90 = med_ms(lambda: m.SearchBySim3(kf1, kf2, p1, p2, s, R12, t12, 7.5), reps)
     out["calls"]["SearchBySim3 (2000 + 2000 features, th 7.5), Python mirror"] = dict(median_ms=md, p90_ms=p90)
+    # the other per-call host forms, at the sizes of tools/map_time.py, tests/test_bow.py and tools/pose_time.py
+    from test_mapping import TUM1, observations, random_keys
+    from orb_slam2_commit_amd import Optimizer
+    tri = synth.triangulation_problem(900, n1=2000, n2=2000, n_true=900)
+    m6 = ORBmatcher(0.6, True)
+    md, p90 = med_ms(lambda: m6.SearchForTriangulation(tri, False), reps)
+    out["calls"]["SearchForTriangulation (2000 + 2000 features), Python mirror"] = dict(median_ms=md, p90_ms=p90)
+    bow = synth.bow_problem(1, n_a=1500, n_b=1600)
+    m75 = ORBmatcher(0.75, True)
+    md, p90 = med_ms(lambda: m75.SearchByBoW(bow["a"], bow["b"]), reps)
+    out["calls"]["SearchByBoW(KF, F) (1500 + 1600 features), Python mirror"] = dict(median_ms=md, p90_ms=p90)
+    desc, off = observations(5, 8000, max_obs=10)
+    md, p90 = med_ms(lambda: orb.compute_distinctive_descriptors(desc, off), reps)
+    out["calls"]["ComputeDistinctiveDescriptors (8000 MapPoints, %d observations), Python mirror" % int(off[-1])] = dict(
+        median_ms=md, p90_ms=p90)
+    K, dist, w, h = TUM1
+    keys = random_keys(9, 1000, w, h)
+    md, p90 = med_ms(lambda: orb.undistort_keypoints(keys, K, dist), reps)
+    out["calls"]["UndistortKeyPoints (1000 keypoints, TUM fr1), Python mirror"] = dict(median_ms=md, p90_ms=p90)
+    pose = synth.pose_problem(900, n=1000)
+    opt = Optimizer()
+    md, p90 = med_ms(lambda: opt.PoseOptimization(pose), reps)
+    opt.close()
+    out["calls"]["PoseOptimization (1000 edges), Python mirror"] = dict(median_ms=md, p90_ms=p90)
     print(json.dumps(out, indent=1))
 
 

@@ -62,6 +62,9 @@
  *   orbx_local_ba / orbx_ba_*   Optimizer::LocalBundleAdjustment src/Optimizer.cc:530-885, include/Optimizer.h:61
  *                               (g2o graph build, optimize(5), outlier levels, optimize(10), vToErase;
  *                               the Map mutex/recovery part stays on the caller's side)
+ *   orbx_ba_run_global[_bool]   Optimizer::GlobalBundleAdjustemnt / BundleAdjustment src/Optimizer.cc:41-284,
+ *                               include/Optimizer.h:48-54 (one optimize(n) over the whole map; up to 512 free
+ *                               keyframes; the nLoopKF write-back stays on the caller's side)
  *   orbx_kfdb_create            KeyFrameDatabase::KeyFrameDatabase  src/KeyFrameDatabase.cc:33-37, include/KeyFrameDatabase.h:46
  *   orbx_kfdb_add / _erase / _clear   KeyFrameDatabase::add / erase / clear   src/KeyFrameDatabase.cc:40-73
  *   orbx_kfdb_set_neighbours    KeyFrame::GetBestCovisibilityKeyFrames(10) of the keyframes, read at
@@ -432,6 +435,29 @@ orbx_status orbx_ba_run_many(orbx_ba* h, int n, const orbx_ba_problem* problems,
  * directly (no page registration): set it from another thread to interrupt
  * orbx_ba_run(h, ..., flag) like LocalMapping::InterruptBA sets mbAbortBA. */
 orbx_status orbx_ba_stop_flag(orbx_ba* h, volatile int** flag);
+/* Optimizer::GlobalBundleAdjustemnt -> Optimizer::BundleAdjustment (src/Optimizer.cc:41-284) on the same
+ * solver: one optimize(n_iterations) over every edge, no outlier pass and no erase list.  The caller
+ * gathers as :75-218 does -- keyframes that are not bad (fixed for mnId == 0), points that are not bad,
+ * the observations whose keyframe is not bad and has mnId <= maxKFid, edges per point in vpMP order --
+ * and writes back per :228-282 (SetPose / SetWorldPos when nLoopKF == 0, else mTcwGBA / mPosGBA).
+ *   robust          bRobust: Huber kernels with the deltas float(sqrt(5.99)) / float(sqrt(7.815)) (:96-97);
+ *                   0: no edge has a kernel
+ *   result          iterations[0], chi2[0] and trials are the run's; iterations[1] = 0, chi2[1] = 0;
+ *                   ran = 1 always; edge_outlier may be NULL (there is no erase list; given, it is cleared)
+ *   point_included  (optional, n_points) 0 for a point that ended with no edge (vbNotIncludedMP,
+ *                   :209-217): its Xw is returned unchanged.  A camera without edges keeps its pose
+ *                   (through Converter::toSE3Quat / toCvMat, as the reference writes it back).
+ *   stop_flag       polled at the head of every iteration (g2o's terminate()).  There is NO early
+ *                   return: a flag raised before the call gives zero iterations and the write-back
+ *                   still happens -- the outputs are then toCvMat(SE3Quat(toSE3Quat(Tcw))) of the inputs.
+ * The reduced camera system is dense: up to 512 free keyframes (ORBX_ERR_SIZE beyond; a sparse pair
+ * table and factor for larger maps are not built).  Beyond 170 free keyframes it is factored by the
+ * tiled LDLT kernels over many workgroups. */
+orbx_status orbx_ba_run_global(orbx_ba* h, const orbx_ba_problem* problem, int n_iterations, int robust,
+                               orbx_ba_result* result, uint8_t* point_included, const volatile int* stop_flag);
+/* The same with the reference's own flag type (bool* pbStopFlag, LoopClosing's mbStopGBA). */
+orbx_status orbx_ba_run_global_bool(orbx_ba* h, const orbx_ba_problem* problem, int n_iterations, int robust,
+                                    orbx_ba_result* result, uint8_t* point_included, const volatile bool* stop_flag);
 /* One-shot form: create, run, destroy. */
 orbx_status orbx_local_ba(const orbx_ba_problem* problem, orbx_ba_result* result, const volatile int* stop_flag,
                           int device);

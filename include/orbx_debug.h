@@ -121,7 +121,9 @@ int orbx_debug_essgraph_phases(const orbx_essential_graph_problem* problem, cons
  * a zero pivot. */
 int orbx_debug_ldlt(const double* S, const double* b, int N, double* x, int reps, float* ms);
 /* The same with the kernel chosen as orbx_ba_debug_options.ldlt does; stamps (optional, 64 words):
- * the kernel's s_memtime phase stamps of the last launch, when built with -DORBX_LDLT_TS. */
+ * the kernel's s_memtime phase stamps of the last launch, when built with -DORBX_LDLT_TS.  N up to
+ * 3072 for ORBX_BA_LDLT_TILED and ORBX_BA_LDLT_AUTO (*ms is then the whole launch sequence), a padded
+ * size of 1024 for the others (ORBX_ERR_HIP beyond). */
 int orbx_debug_ldlt_ex(const double* S, const double* b, int N, double* x, int reps, float* ms, int kind,
                        unsigned long long* stamps);
 
@@ -131,9 +133,10 @@ int orbx_debug_ldlt_ex(const double* S, const double* b, int N, double* x, int r
  * size it can take); the two hooks reproduce rare events deterministically: nan_trial (the chi2 of
  * that trial of each phase reads NaN, the reference's rho-NaN rejection) and raise_stop_after (the
  * stop flag reads raised after that many trials). */
-#define ORBX_BA_LDLT_AUTO 0    /* 8-wide panels (N < 128), column-step (N <= 192), blocked MFMA beyond */
+#define ORBX_BA_LDLT_AUTO 0    /* 8-wide panels (N < 128), column-step (N <= 192), blocked MFMA to 1024, tiled beyond */
 #define ORBX_BA_LDLT_COLUMN 1  /* the column-step kernel wherever it fits */
 #define ORBX_BA_LDLT_BLOCKED 2 /* the blocked MFMA kernel */
+#define ORBX_BA_LDLT_TILED 3   /* the tiled kernels over many workgroups (AUTO: only beyond a padded size of 1024) */
 typedef struct {
   int ldlt;             /* ORBX_BA_LDLT_* */
   int nan_trial;        /* -1 off */

@@ -7,6 +7,7 @@
 #include <cstring>
 #include <functional>
 #include <initializer_list>
+#include <limits>
 #include <thread>
 #include <vector>
 
@@ -282,6 +283,10 @@ struct LocalBA {
     }
     const auto T2 = now();
     const auto T3 = T2;
+    if (nposes > kTiledMaxPoses) return ORBX_ERR_SIZE;  // before the quadratic tables below
+    long long nslots64 = 0;
+    for (int c1 = 0; c1 < nposes; c1++) nslots64 += (long long)(cam_off[c1 + 1] - cam_off[c1]) * (nposes - c1);
+    if (nslots64 > std::numeric_limits<int>::max()) return ORBX_ERR_SIZE;
     boff.assign(1, 0);
     for (int c1 = 0; c1 < nposes; c1++)
       for (int c2 = c1; c2 < nposes; c2++) boff.push_back(boff.back() + cam_off[c1 + 1] - cam_off[c1]);
@@ -374,6 +379,9 @@ struct LocalBA {
 
   // Sizes known: scratch allocations, readback block, Schur pair table.
   orbx_status finish_structure(int na, int npa, int nposes, int maxc, int nslots, hipStream_t st) {
+    // the ceiling of the dense reduced system (kTiledMaxN), before any buffer is sized; nslots < 0: the
+    // pair table's slot count left the int range (ba_intake, build_structure)
+    if (nposes > kTiledMaxPoses || nslots < 0) return ORBX_ERR_SIZE;
     const int gsplit = std::min(std::max((maxc + kGPpt * kGB - 1) / (kGPpt * kGB), 1), 64);
     const size_t N = 6 * (size_t)nposes;
     BA_CHECK(c.Hpl.alloc(18 * (size_t)na));
@@ -396,7 +404,9 @@ struct LocalBA {
     D.nposes = nposes;
     D.nblk = nposes * (nposes + 1) / 2;
     D.gsplit = gsplit;
-    BA_CHECK(c.gpart.alloc((size_t)(D.nblk * 36 + nposes * 6 + nposes * 27) * gsplit));  // pairs | rhs | camfold pose terms
+    // pairs | rhs | camfold pose terms (64-bit: nblk grows with the square of the poses)
+    const size_t ngpart = ((size_t)D.nblk * 36 + (size_t)nposes * 6 + (size_t)nposes * 27) * (size_t)gsplit;
+    BA_CHECK(c.gpart.alloc(ngpart));
     D.gpart = c.gpart.p;
     // readback block: scal[0..7], then errors partials (2 slots of nbe), then update partials
     D.nbe = std::max((na + LBS - 1) / LBS, 1);
@@ -496,13 +506,14 @@ struct LocalBA {
   // the device LM state (spec_skip) -- phase 1 queues phase 2's outlier marking and structure there
   orbx_status optimize_dev(int iterations, const StopFlag& stop, const DevStop& dstop, hipStream_t st, int* iters,
                            double* final_chi, const std::function<hipError_t()>& spec = nullptr) {
+    if (D.nposes > kTiledMaxPoses) return ORBX_ERR_SIZE;  // (finish_structure refuses it before any buffer is sized)
     const size_t N = 6 * (size_t)D.nposes;
-    if (ldlt_np((int)N) > kLdltMaxNp) return ORBX_ERR_SIZE;
+    if (!LdltPlan::use_tiled((int)N) && ldlt_np((int)N) > kLdltMaxNp) return ORBX_ERR_SIZE;  // a forced kernel
     LdltPlan ldlt;
     BA_CHECK(ldlt.prepare((int)N));
     D.ldlt_pan = ldlt.pan ? 1 : 0;
-    if (!ldlt.col && !ldlt.in_lds) {
-      BA_CHECK(c.Sw.alloc((size_t)ldlt_np((int)N) * ldlt_np((int)N)));
+    if (ldlt.sw_doubles() > 0) {
+      BA_CHECK(c.Sw.alloc(ldlt.sw_doubles()));
       D.Sw = c.Sw.p;
     }
     BA_CHECK(c.lm.alloc(1));

@@ -1,7 +1,8 @@
 // ba_ldlt.h -- LocalBundleAdjustment (localba.hip): dense LDLT and solve of the reduced camera
-// system.  Three kernels -- 16-wide blocked MFMA (k_ba_ldlt), column-step with 4x4 register tiles
-// (k_ba_ldlt_col), 8-wide panels over those tiles (k_ba_ldlt_pan) -- and the plan that picks one
-// by size (LdltPlan).
+// system.  Three single-workgroup kernels -- 16-wide blocked MFMA (k_ba_ldlt), column-step with 4x4
+// register tiles (k_ba_ldlt_col), 8-wide panels over those tiles (k_ba_ldlt_pan) --, the tiled
+// kernels over many workgroups for a global map's system (k_ba_ldlt_tiled_*), and the plan that
+// picks by size (LdltPlan).
 #pragma once
 #include <map>
 #include <mutex>
@@ -766,6 +767,219 @@ __global__ __launch_bounds__(NT) void k_ba_ldlt_pan_many(const BaDev* __restrict
   k_ba_ldlt_pan_body<TPT, NT, R>(Ds[blockIdx.z]);
 }
 
+// ---- reduced camera system beyond one workgroup: 64-wide panels over many workgroups ----
+// k_ba_ldlt_tiled_*: the same right-looking LDL^T without pivoting, for the systems of a global map
+// (GlobalBundleAdjustemnt: N up to kTiledMaxN = 3072, a 75 MB matrix that no single workgroup should
+// walk).  The work matrix A lives in D.Sw: Nr = Np + 16 rows of Np doubles, Np = N padded to a
+// multiple of 64 with an identity block (decoupled, never a zero pivot); row Np is the augmented
+// row b^T (rows Np+1 .. Np+15 are zero: the row tiles stay 16 high), so the forward solve rides on
+// the factorisation as in k_ba_ldlt_col.  Entries are kept unscaled, W = L D.  Per panel j0, three
+// launches ordered by the stream alone:
+//   diag   one workgroup: the 64 x 64 diagonal block in LDS, one barrier per pivot; W11 back into A,
+//          L11 and 1 / d into the panel scratch;
+//   strip  32 rows below the panel per workgroup: W21 L11^T = A21 solved in LDS (W21 back into A,
+//          L21 = W21 D^-1 into the panel scratch Lp);
+//   trail  A22 -= W21 L21^T, one 64 x 64 block of the lower triangle per workgroup, FP64 MFMA
+//          16x16x4 tiles with k_ba_ldlt's operand layout (K = 64: sixteen steps per tile).
+// The augmented row then holds z = L^-1 b, and L^T x = D^-1 z is solved from the last panel up, one
+// launch per panel (back): every workgroup solves the panel's 64 unknowns for itself (the same
+// instructions on the same inputs: the same bits) and takes v_i -= sum_c W_ci x_c for its own 256
+// rows i above the panel, in z's place; x_i = v_i / d_i.  No block waits for another.  Partitions
+// and summation orders are fixed, nothing is accumulated atomically: results are identical from run
+// to run.  Failure rule as the other kernels: an exactly zero pivot fails the solve; the diag
+// launch that meets it clears scal[2] (load set it), and every later launch of that solve returns
+// at once on reading it.
+constexpr int kTB = 64;                  // panel width
+constexpr int kTiledMaxPoses = 512;      // free keyframes of the largest system
+constexpr int kTiledMaxN = 6 * kTiledMaxPoses;
+constexpr int kTiledStripRows = 32;      // rows per workgroup of the strip solve
+constexpr int kTiledNT = 256;
+inline int ldlt_tiled_np(int N) { return (N + kTB - 1) / kTB * kTB; }
+// D.Sw of the tiled kernels, in doubles: A (Nr x Np) | Lp (Nr x 64) | L11 (64 x 64) | 1/d (64)
+inline size_t ldlt_tiled_doubles(int N) {
+  const size_t Np = ldlt_tiled_np(N), Nr = Np + 16;
+  return Nr * Np + Nr * kTB + kTB * kTB + kTB;
+}
+struct TiledWs {
+  double *A, *Lp, *L11, *dinv;
+  int N, Np, Nr;
+};
+__device__ inline TiledWs tiled_ws(const BaDev& D) {
+  TiledWs w;
+  w.N = 6 * D.nposes;
+  w.Np = (w.N + kTB - 1) / kTB * kTB;
+  w.Nr = w.Np + 16;
+  w.A = D.Sw;
+  w.Lp = w.A + (size_t)w.Nr * w.Np;
+  w.L11 = w.Lp + (size_t)w.Nr * kTB;
+  w.dinv = w.L11 + kTB * kTB;
+  return w;
+}
+
+__global__ __launch_bounds__(kTiledNT) void k_ba_ldlt_tiled_load(BaDev D) {
+  if (lm_skip(D)) return;
+  const TiledWs w = tiled_ws(D);
+  const size_t total = (size_t)w.Nr * w.Np;
+  for (size_t idx = (size_t)blockIdx.x * kTiledNT + threadIdx.x; idx < total; idx += (size_t)gridDim.x * kTiledNT) {
+    const int r = (int)(idx / w.Np), c = (int)(idx - (size_t)r * w.Np);
+    double v = 0.0;
+    if (r < w.N)
+      v = c < w.N ? D.S[(size_t)r * w.N + c] : 0.0;
+    else if (r < w.Np)
+      v = r == c ? 1.0 : 0.0;
+    else if (r == w.Np)
+      v = c < w.N ? D.bs[c] : 0.0;
+    w.A[idx] = v;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) D.scal[2] = 1.0;
+}
+
+__global__ __launch_bounds__(kTiledNT) void k_ba_ldlt_tiled_diag(BaDev D, int j0) {
+  if (lm_skip(D) || D.scal[2] == 0.0) return;
+  const TiledWs w = tiled_ws(D);
+  __shared__ double T[kTB][kTB + 1];
+  const int tid = threadIdx.x;
+  for (int idx = tid; idx < kTB * kTB; idx += kTiledNT) {
+    const int r = idx >> 6, c = idx & 63;
+    T[r][c] = w.A[(size_t)(j0 + r) * w.Np + j0 + c];
+  }
+  __syncthreads();
+  for (int c = 0; c < kTB; c++) {
+    const double d = T[c][c];  // (final: every update of column c is behind the last barrier)
+    if (d == 0.0) {            // uniform
+      if (tid == 0) D.scal[2] = 0.0;
+      return;
+    }
+    const double invd = 1.0 / d;
+    for (int idx = tid; idx < kTB * kTB; idx += kTiledNT) {
+      const int r = idx >> 6, k = idx & 63;
+      if (k > c && k <= r) T[r][k] -= T[r][c] * invd * T[k][c];  // column c is not written in step c
+    }
+    __syncthreads();
+  }
+  for (int idx = tid; idx < kTB * kTB; idx += kTiledNT) {
+    const int r = idx >> 6, c = idx & 63;
+    if (c <= r) w.A[(size_t)(j0 + r) * w.Np + j0 + c] = T[r][c];
+    w.L11[idx] = c < r ? T[r][c] * (1.0 / T[c][c]) : (c == r ? 1.0 : 0.0);
+  }
+  if (tid < kTB) w.dinv[tid] = 1.0 / T[tid][tid];
+}
+
+__global__ __launch_bounds__(kTiledNT) void k_ba_ldlt_tiled_strip(BaDev D, int j0) {
+  if (lm_skip(D) || D.scal[2] == 0.0) return;
+  const TiledWs w = tiled_ws(D);
+  __shared__ double Ls[kTB][kTB + 1];
+  __shared__ double T[kTiledStripRows][kTB + 1];
+  __shared__ double dinv[kTB];
+  const int tid = threadIdx.x;
+  const int i0 = j0 + kTB + kTiledStripRows * blockIdx.x;  // the workgroup's first row
+  for (int idx = tid; idx < kTB * kTB; idx += kTiledNT) Ls[idx >> 6][idx & 63] = w.L11[idx];
+  if (tid < kTB) dinv[tid] = w.dinv[tid];
+  for (int idx = tid; idx < kTiledStripRows * kTB; idx += kTiledNT) {
+    const int r = idx >> 6, c = idx & 63;
+    T[r][c] = i0 + r < w.Nr ? w.A[(size_t)(i0 + r) * w.Np + j0 + c] : 0.0;
+  }
+  __syncthreads();
+  // W21 L11^T = A21, right-looking: after step m every entry right of column m has taken W_rm L11_cm
+  for (int m = 0; m + 1 < kTB; m++) {
+    for (int idx = tid; idx < kTiledStripRows * kTB; idx += kTiledNT) {
+      const int r = idx >> 6, c = idx & 63;
+      if (c > m) T[r][c] -= T[r][m] * Ls[c][m];
+    }
+    __syncthreads();
+  }
+  for (int idx = tid; idx < kTiledStripRows * kTB; idx += kTiledNT) {
+    const int r = idx >> 6, c = idx & 63;
+    if (i0 + r < w.Nr) {
+      w.A[(size_t)(i0 + r) * w.Np + j0 + c] = T[r][c];
+      w.Lp[(size_t)(i0 + r) * kTB + c] = T[r][c] * dinv[c];
+    }
+  }
+}
+
+__global__ __launch_bounds__(kTiledNT) void k_ba_ldlt_tiled_trail(BaDev D, int j0) {
+  if (lm_skip(D) || D.scal[2] == 0.0) return;
+  const int bi = blockIdx.x, bk = blockIdx.y;
+  if (bk > bi) return;  // the lower triangle of 64 x 64 blocks
+  const TiledWs w = tiled_ws(D);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int R0 = j0 + kTB + kTB * bi + 16 * wv, Cb = j0 + kTB + kTB * bk;
+  if (R0 >= w.Nr) return;  // (the augmented block row is one tile high)
+  const size_t ld = w.Np;
+  double4_t acc[4];
+#pragma unroll
+  for (int t = 0; t < 4; t++) acc[t] = double4_t{0.0, 0.0, 0.0, 0.0};
+#pragma unroll 4
+  for (int kk = 0; kk < kTB / 4; kk++) {
+    const double av = w.A[(size_t)(R0 + (lane & 15)) * ld + j0 + 4 * kk + (lane >> 4)];  // W[row][k]
+#pragma unroll
+    for (int t = 0; t < 4; t++) {
+      const double bv = w.Lp[(size_t)(Cb + 16 * t + (lane & 15)) * kTB + 4 * kk + (lane >> 4)];  // L[col][k]
+      acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc[t], 0, 0, 0);
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < 4; t++)
+#pragma unroll
+    for (int rr = 0; rr < 4; rr++) {
+      const size_t o = (size_t)(R0 + (lane >> 4) + 4 * rr) * ld + Cb + 16 * t + (lane & 15);
+      w.A[o] -= acc[t][rr];
+    }
+}
+
+__global__ __launch_bounds__(kTiledNT) void k_ba_ldlt_tiled_back(BaDev D, int j0) {
+  if (lm_skip(D) || D.scal[2] == 0.0) return;
+  const TiledWs w = tiled_ws(D);
+  __shared__ double T[kTB][kTB + 1];
+  __shared__ double xs[kTB];
+  const int tid = threadIdx.x;
+  double* v = w.A + (size_t)w.Np * w.Np;  // the augmented row: z, then z minus the solved panels' terms
+  for (int idx = tid; idx < kTB * kTB; idx += kTiledNT) {
+    const int r = idx >> 6, c = idx & 63;
+    T[r][c] = w.A[(size_t)(j0 + r) * w.Np + j0 + c];
+  }
+  __syncthreads();
+  if (tid < 64) {  // wave 0: lane r holds v_r; x_c = v_c / d_c from the bottom up
+    const int r = tid;
+    double val = v[j0 + r], x = 0.0;
+    const double invd = 1.0 / T[r][r];
+#pragma unroll
+    for (int c = kTB - 1; c >= 0; c--) {
+      const double xc = readlane_d(val * invd, c);
+      if (r < c) val -= T[c][r] * xc;
+      if (r == c) x = xc;
+    }
+    xs[r] = x;
+    if (blockIdx.x == 0 && j0 + r < w.N) D.xp[j0 + r] = x;
+  }
+  __syncthreads();
+  const int i = blockIdx.x * kTiledNT + tid;
+  if (i < j0) {
+    double acc = v[i];
+    for (int c = 0; c < kTB; c++) acc -= w.A[(size_t)(j0 + c) * w.Np + i] * xs[c];
+    v[i] = acc;
+  }
+}
+
+// The launches of one tiled solve, in stream order.
+inline void ldlt_tiled_launch(const BaDev& D, hipStream_t st) {
+  const int N = 6 * D.nposes, Np = ldlt_tiled_np(N), Nr = Np + 16;
+  const size_t total = (size_t)Nr * Np;
+  const int gl = (int)std::min<size_t>((total + kTiledNT - 1) / kTiledNT, 4096);
+  hipLaunchKernelGGL(k_ba_ldlt_tiled_load, dim3(gl), dim3(kTiledNT), 0, st, D);
+  for (int j0 = 0; j0 < Np; j0 += kTB) {
+    hipLaunchKernelGGL(k_ba_ldlt_tiled_diag, dim3(1), dim3(kTiledNT), 0, st, D, j0);
+    const int rows = Nr - j0 - kTB;  // below the panel, the augmented tile row included
+    hipLaunchKernelGGL(k_ba_ldlt_tiled_strip, dim3((rows + kTiledStripRows - 1) / kTiledStripRows), dim3(kTiledNT), 0,
+                       st, D, j0);
+    const int mc = (Np - j0 - kTB) / kTB;  // 64 x 64 block columns right of the panel
+    if (mc > 0) hipLaunchKernelGGL(k_ba_ldlt_tiled_trail, dim3(mc + 1, mc), dim3(kTiledNT), 0, st, D, j0);
+  }
+  for (int j0 = Np - kTB; j0 >= 0; j0 -= kTB)
+    hipLaunchKernelGGL(k_ba_ldlt_tiled_back, dim3(std::max((j0 + kTiledNT - 1) / kTiledNT, 1)), dim3(kTiledNT), 0, st,
+                       D, j0);
+}
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device), raised only when a larger
 // size is asked for: the runtime call costs microseconds and used to sit between the launches of
 // every LM phase (the device idled behind it)
@@ -783,14 +997,33 @@ inline hipError_t set_smem_attr(const void* fn, size_t bytes) {
 }
 
 // Launch plan for the reduced system: the 8-wide panel kernel (N < 128), the column-step kernel while
-// the packed factor fits LDS, else the 16-wide blocked MFMA kernel (LDS or global).  The debug options
-// (orbx_debug_ba_options) can force the column-step or the blocked kernel where they fit, for tests.
+// the packed factor fits LDS, else the 16-wide blocked MFMA kernel (LDS or global) up to a padded size
+// of kLdltMaxNp, and the tiled kernels beyond it (up to kTiledMaxN).  The debug options
+// (orbx_debug_ba_options) can force the column-step or the blocked kernel where they fit, and the
+// tiled kernels at any size, for tests.
 struct LdltPlan {
   int N = 0, tpt = 0, nt = 1024;
-  bool col = false, in_lds = false, pan = false;
+  bool col = false, in_lds = false, pan = false, tiled = false;
   size_t smem = 0;
+  // the tiled kernels: beyond the single-workgroup kernels' size, or forced (tests run them small)
+  static bool use_tiled(int N) {
+    const int o = ba_opts().ldlt;
+    return (o == ORBX_BA_LDLT_TILED && N >= 6) || (o == ORBX_BA_LDLT_AUTO && ldlt_np(N) > kLdltMaxNp);
+  }
+  // doubles of D.Sw the chosen kernel needs (0: none)
+  size_t sw_doubles() const {
+    if (tiled) return ldlt_tiled_doubles(N);
+    return !col && !pan && !in_lds ? (size_t)ldlt_np(N) * ldlt_np(N) : 0;
+  }
   hipError_t prepare(int n, bool allow_pan = true) {
     N = n;
+    tiled = use_tiled(N);
+    if (tiled) {  // static LDS only
+      pan = col = in_lds = false;
+      if (N > kTiledMaxN) return hipErrorInvalidValue;
+      smem = 0;
+      return hipSuccess;
+    }
     pan = allow_pan && ldlt_use_pan(N);
     if (pan) {
       col = false;
@@ -832,7 +1065,9 @@ struct LdltPlan {
                        dim3(nt), smem, st, Ds);
   }
   void launch(const BaDev& D, hipStream_t st, int stage_limit = 99) const {
-    if (col || pan) {
+    if (tiled) {
+      ldlt_tiled_launch(D, st);
+    } else if (col || pan) {
       hipLaunchKernelGGL(reinterpret_cast<void (*)(BaDev)>(const_cast<void*>(kernel_ptr())), dim3(1), dim3(nt),
                          smem, st, D);
     } else if (in_lds) {

@@ -9,11 +9,12 @@
 //   ba_linearize.h  k_ba_errors, k_ba_linearize, k_ba_point_sum, k_ba_cam_sum / _fin,
 //                   k_ba_point_schur, k_ba_lin_schur (the three point-side kernels fused)
 //   ba_schur.h      k_ba_pair_table, k_ba_pairs, k_ba_schur_fin, the trial's fold flags
-//   ba_ldlt.h       k_ba_ldlt / k_ba_ldlt_col / k_ba_ldlt_pan and LdltPlan
+//   ba_ldlt.h       k_ba_ldlt / k_ba_ldlt_col / k_ba_ldlt_pan, k_ba_ldlt_tiled_* and LdltPlan
 //   ba_lm.h         k_ba_update, k_ba_restore, k_ba_lm_*, k_ba_errors_ctl (the Levenberg step: orbx_lm.h)
 //   ba_structure.h  k_ba_struct_*, k_ba_prep, k_ba_outliers, k_ba_export
 //   ba_capture.h    k_ba_capture_pre / _post: the test-only capture of one trial (orbx_debug.h)
 //   ba_host.h       struct LocalBA: buffers, phase structure, optimize_dev (one optimize() call)
+//   ba_global.h     run_global_ba: Optimizer::GlobalBundleAdjustemnt, one optimize(n) on the same parts
 //   this file       intake, write-back, run_local_ba, the batched driver, the C ABI, the LDLT probe
 //
 // Per LM iteration (g2o OptimizationAlgorithmLevenberg::solve):
@@ -68,7 +69,13 @@ namespace orbx {
 
 // Problem intake: validation, the phase-1 sizes, one pinned-arena upload of
 // the raw arrays and k_ba_prep (src/Optimizer.cc:603-745's graph assembly).
-orbx_status ba_intake(LocalBA& L, const orbx_ba_problem* pb, hipStream_t st) {
+// kn: the robust kernels the edges start with (LocalBundleAdjustment's by default).
+struct BaKernels {
+  float th_mono, th_stereo;  // Huber deltas as the reference stores them (float)
+  bool robust;
+};
+static const BaKernels kLocalBaKernels = {std::sqrt(5.991f), std::sqrt(7.815f), true};  // src/Optimizer.cc:653-654
+orbx_status ba_intake(LocalBA& L, const orbx_ba_problem* pb, hipStream_t st, const BaKernels& kn = kLocalBaKernels) {
   L.trials = 0;
   for (double& t : L.t_struct) t = 0;
   BaDev& D = L.D;
@@ -124,10 +131,11 @@ orbx_status ba_intake(LocalBA& L, const orbx_ba_problem* pb, hipStream_t st) {
         nposes++;
         maxc = std::max(maxc, L.ccnt[i]);
       }
-    int nslots = 0;
+    long long nslots = 0;  // 64-bit: edges x poses
     for (int i = 0, j = 0; i < nc; i++)
-      if (L.ccnt[i] && !(pb->fixed && pb->fixed[i])) nslots += L.ccnt[i] * (nposes - j++);
-    const int s1[5] = {ne, npts, nposes, maxc, nslots};
+      if (L.ccnt[i] && !(pb->fixed && pb->fixed[i])) nslots += (long long)L.ccnt[i] * (nposes - j++);
+    // (beyond the int range: finish_structure refuses the problem)
+    const int s1[5] = {ne, npts, nposes, maxc, nslots > std::numeric_limits<int>::max() ? -1 : (int)nslots};
     std::memcpy(L.sizes1, s1, sizeof s1);
   }
   if (!L.dev_struct) {  // the host structure build reads them
@@ -197,12 +205,13 @@ orbx_status ba_intake(LocalBA& L, const orbx_ba_problem* pb, hipStream_t st) {
   BA_CHECK(c.Xbak.alloc(3 * (size_t)np));
   BA_CHECK(c.eerr.alloc(3 * (size_t)ne));
   {
-    const float thMono = std::sqrt(5.991f), thStereo = std::sqrt(7.815f);  // src/Optimizer.cc:653-654
+    const float thMono = kn.th_mono, thStereo = kn.th_stereo;
     const int gpre = (std::max(ne, 3 * np) + LBS - 1) / LBS;
     if (gpre > 0)
       hipLaunchKernelGGL(k_ba_prep, dim3(gpre), dim3(LBS), 0, st, ne, np, obs_f, isig_f, Xf, X, est, eobs, einfo,
                          edelta, edsqr, erob, c.eerr.p, thMono, thStereo);
     BA_CHECK(hipGetLastError());
+    if (!kn.robust && ne > 0) BA_CHECK(hipMemsetAsync(erob, 0, ne, st));  // no edge carries a kernel
   }
   BA_CHECK(c.flag.alloc(ne));
   BA_CHECK(c.scal.alloc(8));
@@ -227,7 +236,9 @@ orbx_status ba_intake(LocalBA& L, const orbx_ba_problem* pb, hipStream_t st) {
 
 // Write-back (src/Optimizer.cc:817-885): the erase list, poses and points, issued on st into the
 // write-back arena; the caller syncs st, then ba_writeback_finish fills its arrays.
-orbx_status ba_writeback(LocalBA& L, const orbx_ba_problem* pb, orbx_ba_result* res, bool ran, hipStream_t st) {
+// erase_list false (GlobalBundleAdjustemnt): no vToErase, res->edge_outlier is not touched.
+orbx_status ba_writeback(LocalBA& L, const orbx_ba_problem* pb, orbx_ba_result* res, bool ran, hipStream_t st,
+                         bool erase_list = true) {
   BaDev& D = L.D;
   const int nc = pb->n_cams, np = pb->n_points, ne = pb->n_edges;
   const int ge = (ne + LBS - 1) / LBS;
@@ -254,7 +265,7 @@ orbx_status ba_writeback(LocalBA& L, const orbx_ba_problem* pb, orbx_ba_result* 
   w.Tcw = A.take<float>(12 * (size_t)nc);
   w.Xw = A.take<float>(3 * (size_t)np);
   w.flag = A.take<uint8_t>((size_t)ne);
-  if (ne > 0) hipLaunchKernelGGL(k_ba_outliers, dim3(ge), dim3(LBS), 0, st, D, w.flag, 0);
+  if (ne > 0 && erase_list) hipLaunchKernelGGL(k_ba_outliers, dim3(ge), dim3(LBS), 0, st, D, w.flag, 0);
   const int gx = (std::max(nc, np) + LBS - 1) / LBS;
   hipLaunchKernelGGL(k_ba_export, dim3(std::max(gx, 1)), dim3(LBS), 0, st, D, w.Tcw, w.Xw, w.Tcw_d, w.Xw_d);
   BA_CHECK(hipGetLastError());
@@ -262,12 +273,12 @@ orbx_status ba_writeback(LocalBA& L, const orbx_ba_problem* pb, orbx_ba_result* 
 }
 
 // After the stream has synchronised: the write-back arena's pinned copy into the caller's arrays.
-void ba_writeback_finish(LocalBA& L, const orbx_ba_problem* pb, orbx_ba_result* res, bool ran) {
+void ba_writeback_finish(LocalBA& L, const orbx_ba_problem* pb, orbx_ba_result* res, bool ran, bool erase_list = true) {
   if (!ran) return;
   const int nc = pb->n_cams, np = pb->n_points, ne = pb->n_edges;
   Arena& A = L.wb_arena;
   const LocalBA::Wb& w = L.wb;
-  if (ne > 0) std::memcpy(res->edge_outlier, A.host(w.flag), ne);
+  if (ne > 0 && erase_list) std::memcpy(res->edge_outlier, A.host(w.flag), ne);
   std::memcpy(res->Tcw, A.host(w.Tcw), 12 * sizeof(float) * nc);
   std::memcpy(res->Xw, A.host(w.Xw), 3 * sizeof(float) * np);
   if (res->Tcw_d) std::memcpy(res->Tcw_d, A.host(w.Tcw_d), 12 * sizeof(double) * nc);
@@ -376,6 +387,10 @@ orbx_status run_local_ba(LocalBA& L, const orbx_ba_problem* pb, orbx_ba_result* 
   }
   return ORBX_OK;
 }
+
+}  // namespace orbx
+#include "ba_global.h"  // run_global_ba: Optimizer::GlobalBundleAdjustemnt on the parts above
+namespace orbx {
 
 // ---- batched driver: K independent problems through the same launches ----
 // Every trial kernel runs once for all K problems (blockIdx.z), each block on
@@ -765,7 +780,7 @@ long long orbx_debug_ba_capture_read(orbx_ba* h, int what, void* dst, size_t cap
 
 int orbx_debug_ba_options(orbx_ba* h, const orbx_ba_debug_options* o) {
   if (!h) return ORBX_ERR_ARG;
-  if (o && (o->ldlt < ORBX_BA_LDLT_AUTO || o->ldlt > ORBX_BA_LDLT_BLOCKED)) return ORBX_ERR_ARG;
+  if (o && (o->ldlt < ORBX_BA_LDLT_AUTO || o->ldlt > ORBX_BA_LDLT_TILED)) return ORBX_ERR_ARG;
   h->opts = o ? *o : orbx::kBaOptsDefault;
   return ORBX_OK;
 }
@@ -814,6 +829,39 @@ orbx_status orbx_ba_run_bool(orbx_ba* h, const orbx_ba_problem* p, orbx_ba_resul
   return s;
 }
 
+// orbx_ba_run_global's arguments: as valid_call, but the erase list is optional (there is none)
+static bool valid_global_call(const orbx_ba_problem* p, const orbx_ba_result* r) {
+  if (p->n_cams < 0 || p->n_points < 0 || p->n_edges < 0) return false;
+  if (p->n_cams > 0 && (!p->Tcw || !p->intr || !r->Tcw)) return false;
+  if (p->n_points > 0 && (!p->Xw || !r->Xw)) return false;
+  if (p->n_edges > 0 && (!p->edge_point || !p->edge_cam || !p->obs || !p->inv_sigma2)) return false;
+  return true;
+}
+
+static orbx_status ba_run_global(orbx_ba* h, const orbx_ba_problem* p, int n_iterations, int robust, orbx_ba_result* r,
+                                 uint8_t* point_included, const orbx::StopFlag& f) {
+  if (!h || !p || !r || !valid_global_call(p, r)) return ORBX_ERR_ARG;
+  if (hipSetDevice(h->device) != hipSuccess) return ORBX_ERR_HIP;
+  orbx::BaOptScope scope(&h->opts);
+  const orbx_status s = orbx::run_global_ba(h->L, p, n_iterations, robust != 0, r, point_included, f, h->st);
+  h->L.cap.sel_phase = -1;
+  return s;
+}
+
+orbx_status orbx_ba_run_global(orbx_ba* h, const orbx_ba_problem* p, int n_iterations, int robust, orbx_ba_result* r,
+                               uint8_t* point_included, const volatile int* stop_flag) {
+  orbx::StopFlag f;
+  f.i = stop_flag;
+  return ba_run_global(h, p, n_iterations, robust, r, point_included, f);
+}
+
+orbx_status orbx_ba_run_global_bool(orbx_ba* h, const orbx_ba_problem* p, int n_iterations, int robust,
+                                    orbx_ba_result* r, uint8_t* point_included, const volatile bool* stop_flag) {
+  orbx::StopFlag f;
+  f.b = stop_flag;
+  return ba_run_global(h, p, n_iterations, robust, r, point_included, f);
+}
+
 orbx_status orbx_local_ba(const orbx_ba_problem* p, orbx_ba_result* r, const volatile int* stop_flag, int device) {
   orbx_ba* h = nullptr;
   orbx_status s = orbx_ba_create(device, &h);
@@ -839,7 +887,7 @@ extern "C" int orbx_debug_ldlt(const double* S, const double* b, int N, double* 
 extern "C" int orbx_debug_ldlt_ex(const double* S, const double* b, int N, double* x, int reps, float* ms, int kind,
                                   unsigned long long* stamps) {
   if (!S || !b || !x || N <= 0 || N % 6 || reps < 1) return ORBX_ERR_ARG;
-  if (kind < ORBX_BA_LDLT_AUTO || kind > ORBX_BA_LDLT_BLOCKED) return ORBX_ERR_ARG;
+  if (kind < ORBX_BA_LDLT_AUTO || kind > ORBX_BA_LDLT_TILED) return ORBX_ERR_ARG;
   orbx_ba_debug_options o = orbx::kBaOptsDefault;
   o.ldlt = kind;
   orbx::BaOptScope scope(&o);
@@ -867,13 +915,13 @@ extern "C" int orbx_debug_ldlt_ex(const double* S, const double* b, int N, doubl
     if (e == hipSuccess) e = hipMemset(ddbg, 0, 64 * sizeof(unsigned long long));
   }
   D.dbg = ddbg;
-  if (orbx::ldlt_np(N) > orbx::kLdltMaxNp) e = hipErrorInvalidValue;
+  // (the single-workgroup kernels stop at a padded size of kLdltMaxNp, the tiled ones at kTiledMaxN)
+  if (orbx::LdltPlan::use_tiled(N) ? N > orbx::kTiledMaxN : orbx::ldlt_np(N) > orbx::kLdltMaxNp) e = hipErrorInvalidValue;
   orbx::LdltPlan plan;
   if (e == hipSuccess) e = plan.prepare(N);
   D.ldlt_pan = plan.pan ? 1 : 0;
   double* dSw = nullptr;
-  if (e == hipSuccess && !plan.col && !plan.in_lds)
-    e = hipMalloc((void**)&dSw, (size_t)orbx::ldlt_np(N) * orbx::ldlt_np(N) * sizeof(double));
+  if (e == hipSuccess && plan.sw_doubles() > 0) e = hipMalloc((void**)&dSw, plan.sw_doubles() * sizeof(double));
   D.Sw = dSw;
   float total = 0;
   if (e == hipSuccess) {

@@ -773,6 +773,38 @@ class Optimizer:
         out.update(iterations=tuple(R.iterations), trials=R.trials, chi2=tuple(R.chi2))
         return out
 
+    def GlobalBundleAdjustemnt(self, problem, nIterations=5, stop=False, bRobust=True):
+        """Optimizer::GlobalBundleAdjustemnt -> BundleAdjustment (src/Optimizer.cc:41-284; the reference's
+        spelling): one optimize(nIterations) over every edge of ``problem`` (LocalBundleAdjustment's
+        dict: cameras fixed for mnId == 0, edges per point in point order), Huber kernels with the
+        deltas sqrt(5.99) / sqrt(7.815) when bRobust, none otherwise.  ``stop`` as in
+        LocalBundleAdjustment; a flag raised before the call gives zero iterations and the outputs
+        are the inputs through toSE3Quat / toCvMat (there is no early return).  Up to 512 free
+        keyframes (OrbxError ORBX_ERR_SIZE beyond).
+
+        Returns LocalBundleAdjustment's dict (edge_outlier all zero, iterations[1] = chi2[1] = 0)
+        plus point_included[m] (0: the point had no edge and keeps its position) and ran (1)."""
+        a = _ba_arrays(problem)
+        nc, npt, ne = len(a["Tcw"]), len(a["Xw"]), len(a["edge_point"])
+        P = _lib.BaProblem(nc, ptr(a["Tcw"]), ptr(a["fixed"]), ptr(a["intr"]), npt, ptr(a["Xw"]), ne,
+                           ptr(a["edge_point"]), ptr(a["edge_cam"]), ptr(a["obs"]), ptr(a["inv_sigma2"]))
+        out = dict(Tcw=np.empty((nc, 12), np.float32), Xw=np.empty((npt, 3), np.float32),
+                   edge_outlier=np.zeros(ne, np.uint8), Tcw_d=np.empty((nc, 12)), Xw_d=np.empty((npt, 3)),
+                   point_included=np.zeros(npt, np.uint8))
+        R = _lib.BaResult(ptr(out["Tcw"]), ptr(out["Xw"]), ptr(out["edge_outlier"]), ptr(out["Tcw_d"]),
+                          ptr(out["Xw_d"]))
+        if isinstance(stop, np.ndarray):
+            if stop.dtype != np.int32 or stop.size != 1 or not stop.flags.c_contiguous:
+                raise ValueError("stop flag array must be one contiguous int32")
+            flag = C.c_void_p(stop.ctypes.data)
+        else:
+            self._stop[0] = 1 if stop else 0
+            flag = C.cast(self._stop, C.c_void_p)
+        check(_lib.lib().orbx_ba_run_global(self._h, C.byref(P), int(nIterations), 1 if bRobust else 0, C.byref(R),
+                                            ptr(out["point_included"]), flag), "orbx_ba_run_global")
+        out.update(iterations=tuple(R.iterations), trials=R.trials, chi2=tuple(R.chi2), ran=R.ran)
+        return out
+
     def LocalBundleAdjustmentMany(self, probs, stop=False):
         """K independent problems through one batched LM loop (orbx_ba_run_many); returns the
         list of result dicts, each bit-identical to LocalBundleAdjustment on that problem."""

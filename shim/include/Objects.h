@@ -110,6 +110,10 @@ class MapPoint {
   long unsigned int mnBALocalForKF = 0, mnFuseCandidateForKF = 0;
   // written by LoopClosing::CorrectLoop, read by OptimizeEssentialGraph (include/MapPoint.h:130-133)
   long unsigned int mnCorrectedByKF = 0, mnCorrectedReference = 0;
+  // written by Optimizer::BundleAdjustment with nLoopKF != 0 (include/MapPoint.h:135-136): the global
+  // bundle adjustment's position, applied later by LoopClosing::RunGlobalBundleAdjustment
+  cv::Mat mPosGBA;
+  long unsigned int mnBAGlobalForKF = 0;
   int nObs = 0;
   int mnVisible = 1, mnFound = 1;
   bool mbBad = false;
@@ -225,6 +229,9 @@ class KeyFrame {
 
   long unsigned int mnId = 0;
   long unsigned int mnBALocalForKF = 0, mnBAFixedForKF = 0;
+  // written by Optimizer::BundleAdjustment with nLoopKF != 0 (include/KeyFrame.h:197-199)
+  cv::Mat mTcwGBA;
+  long unsigned int mnBAGlobalForKF = 0;
   // written by KeyFrameDatabase (include/KeyFrame.h:181-194); the two scores are uninitialised in the
   // reference and start at 0 here, as on the device
   long unsigned int mnLoopQuery = 0;

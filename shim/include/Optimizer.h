@@ -76,6 +76,21 @@ class Optimizer {
   void static LocalBundleAdjustment(const LocalBAProblem& problem, bool* pbStopFlag, LocalBAResult& result,
                                     int device = 0);
 
+  // include/Optimizer.h:48-54, src/Optimizer.cc:41-284 (called at src/Tracking.cc CreateInitialMapMonocular
+  // and src/LoopClosing.cc RunGlobalBundleAdjustment): one optimize(nIterations) over every keyframe and
+  // map point given, on the MI355X.  Gathers as :75-218 does -- keyframes that are not bad (fixed for
+  // mnId == 0), points that are not bad, the observations whose keyframe is not bad and has mnId <=
+  // maxKFid -- walking keyframes, points and each point's observations in ASCENDING mnId (the reference
+  // walks its containers in pointer order; the order changes summation order only).  Writes back per
+  // :228-282: nLoopKF == 0 SetPose / SetWorldPos / UpdateNormalAndDepth, otherwise mTcwGBA / mPosGBA /
+  // mnBAGlobalForKF; a point that ended with no edge (vbNotIncludedMP) is left alone.  Up to 512 free
+  // keyframes; throws std::runtime_error on a library error (the object graph is then left as it was).
+  void static BundleAdjustment(const std::vector<KeyFrame*>& vpKF, const std::vector<MapPoint*>& vpMP,
+                               int nIterations = 5, bool* pbStopFlag = NULL, const unsigned long nLoopKF = 0,
+                               const bool bRobust = true);
+  void static GlobalBundleAdjustemnt(Map* pMap, int nIterations = 5, bool* pbStopFlag = NULL,
+                                     const unsigned long nLoopKF = 0, const bool bRobust = true);
+
   // include/Optimizer.h, src/Optimizer.cc:1220-1456 (called at src/LoopClosing.cc:425-444): refines
   // g2oS12 over the matches of vpMatches1 (per keypoint of pKF1, the MapPoint of pKF2 or NULL) on the
   // MI355X.  Gathers as :1267-1384 does, nulls the outliers in vpMatches1, writes g2oS12 only when

@@ -1,6 +1,7 @@
 // shim.cc -- the reference's hot-path classes (ORBextractor, Frame's ORB/stereo part and ComputeBoW,
 // ORBmatcher's SearchByBoW x2 / SearchByProjection x3 / SearchForTriangulation / Fuse /
-// DescriptorDistance, PnPsolver, Optimizer::PoseOptimization / LocalBundleAdjustment,
+// DescriptorDistance, PnPsolver, Optimizer::PoseOptimization / LocalBundleAdjustment /
+// GlobalBundleAdjustemnt,
 // MapPoint::ComputeDistinctiveDescriptors, ORBVocabulary) as thin C++ over the C ABI of liborbx.so
 // (include/orbx.h).  Argument meaning and error behaviour follow the
 // reference; a library error (no device, bad geometry) throws std::runtime_error where the
@@ -1788,6 +1789,123 @@ void Optimizer::OptimizeEssentialGraph(Map* pMap, KeyFrame* pLoopKF, KeyFrame* p
     for (int k = 0; k < 3; k++) cvCorrectedP3Dw.at<float>(k, 0) = Xo[3 * j + k];
     moved[j]->SetWorldPos(cvCorrectedP3Dw);
     moved[j]->UpdateNormalAndDepth();
+  }
+}
+
+void Optimizer::GlobalBundleAdjustemnt(Map* pMap, int nIterations, bool* pbStopFlag, const unsigned long nLoopKF,
+                                       const bool bRobust) {
+  std::vector<KeyFrame*> vpKFs = pMap->GetAllKeyFrames();
+  std::vector<MapPoint*> vpMP = pMap->GetAllMapPoints();
+  BundleAdjustment(vpKFs, vpMP, nIterations, pbStopFlag, nLoopKF, bRobust);
+}
+
+void Optimizer::BundleAdjustment(const std::vector<KeyFrame*>& vpKFsIn, const std::vector<MapPoint*>& vpMPIn,
+                                 int nIterations, bool* pbStopFlag, const unsigned long nLoopKF, const bool bRobust) {
+  // ascending mnId, as OptimizeEssentialGraph walks its containers (the caller's vectors come out of
+  // pointer-ordered sets)
+  std::vector<KeyFrame*> vpKFs(vpKFsIn);
+  std::vector<MapPoint*> vpMP(vpMPIn);
+  std::stable_sort(vpKFs.begin(), vpKFs.end(), [](KeyFrame* a, KeyFrame* b) { return a->mnId < b->mnId; });
+  std::stable_sort(vpMP.begin(), vpMP.end(), [](MapPoint* a, MapPoint* b) { return a->mnId < b->mnId; });
+  // src/Optimizer.cc:75-93: a vertex per keyframe that is not bad, fixed for mnId == 0
+  std::vector<KeyFrame*> cams;
+  std::map<KeyFrame*, int> cam_index;
+  std::vector<float> Tcw, intr;
+  std::vector<uint8_t> fixed;
+  long unsigned int maxKFid = 0;
+  for (KeyFrame* pKF : vpKFs) {
+    if (pKF->isBad()) continue;
+    cam_index[pKF] = (int)cams.size();
+    cams.push_back(pKF);
+    const cv::Mat T = pKF->GetPose();
+    for (int i = 0; i < 12; i++) Tcw.push_back(T.at<float>(i / 4, i % 4));
+    fixed.push_back(pKF->mnId == 0 ? 1 : 0);
+    const float in[5] = {pKF->fx, pKF->fy, pKF->cx, pKF->cy, pKF->mbf};
+    intr.insert(intr.end(), in, in + 5);
+    if (pKF->mnId > maxKFid) maxKFid = pKF->mnId;
+  }
+  // :102-218: a vertex per point that is not bad, an edge per observation by a keyframe that is not bad
+  // and not newer than maxKFid (monocular when mvuRight < 0)
+  std::vector<MapPoint*> points;
+  std::vector<float> Xw, obs, isig;
+  std::vector<int32_t> ep, ec;
+  for (MapPoint* pMP : vpMP) {
+    if (pMP->isBad()) continue;
+    const int p = (int)points.size();
+    points.push_back(pMP);
+    const cv::Mat X = pMP->GetWorldPos();
+    for (int k = 0; k < 3; k++) Xw.push_back(X.at<float>(k, 0));
+    const std::map<KeyFrame*, size_t> observations = pMP->GetObservations();
+    std::vector<std::pair<KeyFrame*, size_t>> vObs(observations.begin(), observations.end());
+    std::stable_sort(vObs.begin(), vObs.end(),
+                     [](const std::pair<KeyFrame*, size_t>& a, const std::pair<KeyFrame*, size_t>& b) {
+                       return a.first->mnId < b.first->mnId;
+                     });
+    for (const auto& ob : vObs) {
+      KeyFrame* pKF = ob.first;
+      if (pKF->isBad() || pKF->mnId > maxKFid) continue;
+      const auto it = cam_index.find(pKF);
+      if (it == cam_index.end()) continue;  // no vertex: g2o refuses the edge
+      const cv::KeyPoint& kpUn = pKF->mvKeysUn[ob.second];
+      ep.push_back(p);
+      ec.push_back(it->second);
+      obs.push_back(kpUn.pt.x);
+      obs.push_back(kpUn.pt.y);
+      obs.push_back(pKF->mvuRight[ob.second]);
+      isig.push_back(pKF->mvInvLevelSigma2[kpUn.octave]);
+    }
+  }
+  const int nc = (int)cams.size(), np = (int)points.size(), ne = (int)ep.size();
+  orbx_ba_problem prob{nc, Tcw.data(), fixed.data(), intr.data(), np, Xw.data(),
+                       ne, ep.data(), ec.data(), obs.data(), isig.data()};
+  std::vector<float> Tout(12 * (size_t)nc + 1), Xout(3 * (size_t)np + 1);
+  std::vector<uint8_t> included((size_t)np + 1);
+  orbx_ba_result res;
+  std::memset(&res, 0, sizeof(res));
+  res.Tcw = Tout.data();
+  res.Xw = Xout.data();
+  // the calling thread keeps one solver (LoopClosing's GBA thread, or Tracking's for the monocular
+  // bootstrap), released when that thread exits
+  struct BaDeleter {
+    void operator()(orbx_ba* h) const { orbx_ba_destroy(h); }
+  };
+  static thread_local std::unique_ptr<orbx_ba, BaDeleter> ba;
+  static thread_local int ba_device = -1;
+  if (ba && ba_device != gOrbxDevice) ba.reset();
+  if (!ba) {
+    orbx_ba* h = nullptr;
+    check(orbx_ba_create(gOrbxDevice, &h), "orbx_ba_create");
+    ba.reset(h);
+    ba_device = gOrbxDevice;
+  }
+  check(orbx_ba_run_global_bool(ba.get(), &prob, nIterations, bRobust ? 1 : 0, &res, included.data(), pbStopFlag),
+        "orbx_ba_run_global");
+  // :228-251 keyframes
+  for (int c = 0; c < nc; c++) {
+    cv::Mat T(4, 4, CV_32F);
+    for (int i = 0; i < 12; i++) T.at<float>(i / 4, i % 4) = Tout[12 * (size_t)c + i];
+    for (int k = 0; k < 4; k++) T.at<float>(3, k) = k == 3 ? 1.f : 0.f;
+    if (nLoopKF == 0) {
+      cams[c]->SetPose(T);
+    } else {
+      cams[c]->mTcwGBA.create(4, 4, CV_32F);
+      T.copyTo(cams[c]->mTcwGBA);
+      cams[c]->mnBAGlobalForKF = nLoopKF;
+    }
+  }
+  // :253-282 points (vbNotIncludedMP: a point that ended with no edge is skipped)
+  for (int p = 0; p < np; p++) {
+    if (!included[p]) continue;
+    cv::Mat X(3, 1, CV_32F);
+    for (int k = 0; k < 3; k++) X.at<float>(k, 0) = Xout[3 * (size_t)p + k];
+    if (nLoopKF == 0) {
+      points[p]->SetWorldPos(X);
+      points[p]->UpdateNormalAndDepth();
+    } else {
+      points[p]->mPosGBA.create(3, 1, CV_32F);
+      X.copyTo(points[p]->mPosGBA);
+      points[p]->mnBAGlobalForKF = nLoopKF;
+    }
   }
 }
 

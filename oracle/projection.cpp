@@ -271,6 +271,7 @@ int local_map(const oracle_proj_problem& P) {
     if (!take) continue;
     const float* tr = P.track + 4 * i;
     const int nPredictedLevel = P.track_level[i];
+    if (nPredictedLevel < 0 || nPredictedLevel >= F.nlevels) continue;  // outside mvScaleFactors: defined here
     float r = tr[3] > 0.998f ? 2.5f : 4.0f;  // RadiusByViewingCos
     if (bFactor) r *= P.th;
     const float rs = r * F.scale_factors[nPredictedLevel];
@@ -351,6 +352,7 @@ int last_frame(const oracle_proj_problem& P) {
     if (u < F.min_x || u > F.max_x) continue;
     if (v < F.min_y || v > F.max_y) continue;
     const int nLastOctave = P.octave[i];
+    if (nLastOctave < 0 || nLastOctave >= F.nlevels) continue;  // outside mvScaleFactors: defined here
     const float radius = P.th * F.scale_factors[nLastOctave];
     std::vector<int> cand;
     if (bForward) cand = fr.area(u, v, radius, nLastOctave);

@@ -1,8 +1,9 @@
 """ORBmatcher::SearchByProjection x3 (+ Frame::isInFrustum, GetFeaturesInArea, PredictScale).
 
 CPU: the C++ oracle (oracle/projection.cpp) against an independent literal
-pure-Python restatement of src/ORBmatcher.cc:46-142, 1489-1646, 1648-1795 and
-src/Frame.cc:254-453 on small problems, plus KATs for log/PredictScale and the
+pure-Python restatement (tests/projection_literal.py) of src/ORBmatcher.cc:46-142,
+1489-1646, 1648-1795 and src/Frame.cc:254-453 on small random problems (crafted
+ones: tests/test_projection_scenes.py), plus KATs for log/PredictScale and the
 grid query.  GPU (-m gpu): the HIP path (orbx_search_by_projection, one block
 per problem, fixed-point sweeps) against the oracle, bit for bit: frame_out,
 point_match, nmatches and (frustum) the track fields as float bits.
@@ -25,364 +26,9 @@ from orb_slam2_commit_amd import synth  # noqa: E402
 f32 = np.float32
 
 
-# ------------------------------------------------------------------ literal Python restatement
-def _mat3x1(T, X):
-    """R*X + t: OpenCV 3.2 cv::gemm small-matrix path -- float dot product left to right, then a
-    correctly rounded float add of t."""
-    out = []
-    for r in range(3):
-        t0 = f32(f32(f32(T[r, 0]) * f32(X[0])) + f32(f32(T[r, 1]) * f32(X[1])))
-        t0 = f32(t0 + f32(f32(T[r, 2]) * f32(X[2])))
-        out.append(f32(float(t0) + float(T[r, 3])))
-    return out
-
-
-def _centre(T):
-    return [f32(-((float(T[0, c]) * float(T[0, 3]) + float(T[1, c]) * float(T[1, 3])) + float(T[2, c]) * float(T[2, 3])))
-            for c in range(3)]
-
-
-def _centre_kf(T):
-    """KeyFrame::GetCameraCenter: Ow = -Rwc*tcw with Rwc a Mat (src/KeyFrame.cc:84-87): cv::gemm's
-    small-matrix path, the dot product in float, alpha = -1."""
-    out = []
-    for c in range(3):
-        t0 = f32(f32(f32(T[0, c]) * f32(T[0, 3])) + f32(f32(T[1, c]) * f32(T[1, 3])))
-        out.append(-f32(t0 + f32(f32(T[2, c]) * f32(T[2, 3]))))
-    return out
-
-
-def _norm3(v):
-    s = float(v[0]) * float(v[0])
-    s = s + float(v[1]) * float(v[1])
-    s = s + float(v[2]) * float(v[2])
-    return f32(math.sqrt(s))
-
-
-def _predict(dmax, dist, logsf, nl):
-    ratio = f32(f32(dmax) / f32(dist))
-    q = f32(f32(oracle.log_det(ratio)) / f32(logsf))
-    n = int(math.ceil(q))
-    return min(max(n, 0), nl - 1)
-
-
-class PyFrame:
-    """Frame::AssignFeaturesToGrid / GetFeaturesInArea, src/Frame.cc:254-271, 388-453."""
-
-    def __init__(self, fr):
-        self.fr = fr
-        k = fr["keys_un"]
-        self.grid = [[[] for _ in range(48)] for _ in range(64)]
-        for i in range(len(k)):
-            # PosInGrid's round() is half-away-from-zero
-            # a KeyFrame's grid is its Frame's, built with the float bounds (grid_min_*); its
-            # GetFeaturesInArea below uses the KeyFrame's integer copies (min_x / min_y)
-            gx0, gy0 = fr.get("grid_min_x", fr["min_x"]), fr.get("grid_min_y", fr["min_y"])
-            vx = float(f32(f32(k["x"][i] - f32(gx0)) * fr["grid_inv_w"]))
-            vy = float(f32(f32(k["y"][i] - f32(gy0)) * fr["grid_inv_h"]))
-            px = int(math.floor(abs(vx) + 0.5)) * (1 if vx >= 0 else -1)
-            py = int(math.floor(abs(vy) + 0.5)) * (1 if vy >= 0 else -1)
-            if 0 <= px < 64 and 0 <= py < 48:
-                self.grid[px][py].append(i)
-
-    def area(self, x, y, r, minL=-1, maxL=-1):
-        fr, k = self.fr, self.fr["keys_un"]
-        x, y, r = f32(x), f32(y), f32(r)
-        x0 = max(0, int(math.floor(f32(f32(f32(x - fr["min_x"]) - r) * fr["grid_inv_w"]))))
-        if x0 >= 64:
-            return []
-        x1 = min(63, int(math.ceil(f32(f32(f32(x - fr["min_x"]) + r) * fr["grid_inv_w"]))))
-        if x1 < 0:
-            return []
-        y0 = max(0, int(math.floor(f32(f32(f32(y - fr["min_y"]) - r) * fr["grid_inv_h"]))))
-        if y0 >= 48:
-            return []
-        y1 = min(47, int(math.ceil(f32(f32(f32(y - fr["min_y"]) + r) * fr["grid_inv_h"]))))
-        if y1 < 0:
-            return []
-        check = minL > 0 or maxL >= 0
-        out = []
-        for ix in range(x0, x1 + 1):
-            for iy in range(y0, y1 + 1):
-                for j in self.grid[ix][iy]:
-                    if check and (k["octave"][j] < minL or (maxL >= 0 and k["octave"][j] > maxL)):
-                        continue
-                    if abs(f32(k["x"][j] - x)) < r and abs(f32(k["y"][j] - y)) < r:
-                        out.append(j)
-        return out
-
-
-def _ham(a, b):
-    return int(np.unpackbits(np.bitwise_xor(a, b)).sum())
-
-
-def _rot_bin(a, b):
-    rot = f32(f32(a) - f32(b))
-    if rot < 0.0:
-        rot = f32(rot + f32(360.0))
-    v = float(f32(rot * f32(1.0 / 30)))
-    b_ = int(math.floor(v + 0.5))
-    return 0 if b_ == 30 else b_
-
-
-def _three_max(counts):
-    m1 = m2 = m3 = 0
-    i1 = i2 = i3 = -1
-    for i, s in enumerate(counts):
-        if s > m1:
-            m3, m2, m1, i3, i2, i1 = m2, m1, s, i2, i1, i
-        elif s > m2:
-            m3, m2, i3, i2 = m2, s, i2, i
-        elif s > m3:
-            m3, i3 = s, i
-    if m2 < f32(0.1) * f32(m1):
-        i2 = i3 = -1
-    elif m3 < f32(0.1) * f32(m1):
-        i3 = -1
-    return i1, i2, i3
-
-
-def py_search(fr, pts, kind, th, nnratio=0.6, check_ori=True, mono=False, orb_dist=100, last_Tcw=None,
-              frustum=False, limit=0.5):
-    F = PyFrame(fr)
-    keys, n = fr["keys_un"], len(fr["keys_un"])
-    occ = fr.get("occ")
-    who = [(-3 if (occ is not None and occ[i]) else -1) for i in range(n)]
-    obs = [bool(occ is not None and occ[i] == 2) for i in range(n)]
-    ur = fr.get("u_right")
-    T = np.asarray(fr["Tcw"], np.float32)
-    Ow = _centre_kf(T) if kind == 3 else _centre(T)  # Fuse: pKF->GetCameraCenter(); else Frame's -Rcw.t()*tcw
-    npnt = len(pts["desc"])
-    pm = [-1] * npnt
-    hist = [[] for _ in range(30)]
-    nm = 0
-    fx, fy, cx, cy, bf = (f32(fr[k]) for k in ("fx", "fy", "cx", "cy", "bf"))
-    sf = fr["scale_factors"]
-    track = np.array(pts["track"], np.float32) if kind == 0 and not frustum else np.zeros((npnt, 4), np.float32)
-    level = np.array(pts["track_level"], np.int32) if kind == 0 and not frustum else np.full(npnt, -1, np.int32)
-    if kind == 0 and frustum:
-        for i in range(npnt):
-            if not (pts["flags"][i] & 1):
-                continue
-            P = pts["pos"][i]
-            Pc = _mat3x1(T, P)
-            if Pc[2] < 0:
-                continue
-            invz = f32(f32(1.0) / Pc[2])
-            u = f32(f32(f32(fx * Pc[0]) * invz) + cx)
-            v = f32(f32(f32(fy * Pc[1]) * invz) + cy)
-            if u < fr["min_x"] or u > fr["max_x"] or v < fr["min_y"] or v > fr["max_y"]:
-                continue
-            PO = [f32(P[j] - Ow[j]) for j in range(3)]
-            d = _norm3(PO)
-            dmin, dmax = pts["dist_minmax"][i]
-            if d < f32(f32(0.8) * dmin) or d > f32(f32(1.2) * dmax):
-                continue
-            Pn = pts["normal"][i]
-            dot = float(PO[0]) * float(Pn[0])
-            dot = dot + float(PO[1]) * float(Pn[1])
-            dot = dot + float(PO[2]) * float(Pn[2])
-            vc = f32(dot / float(d))
-            if vc < f32(limit):
-                continue
-            level[i] = _predict(dmax, d, fr["log_scale_factor"], fr["nlevels"])
-            track[i] = [u, v, f32(u - f32(bf * invz)), vc]
-    if kind == 3:  # Fuse matching half, src/ORBmatcher.cc:944-1054
-        isg = [f32(f32(1.0) / f32(s_ * s_)) for s_ in sf]
-        for i in range(npnt):
-            if not (pts["flags"][i] & 1):
-                continue
-            X = pts["pos"][i]
-            c = _mat3x1(T, X)
-            if c[2] < 0:
-                continue
-            invz = f32(f32(1.0) / c[2])
-            u = f32(f32(fx * f32(c[0] * invz)) + cx)
-            v = f32(f32(fy * f32(c[1] * invz)) + cy)
-            if not (u >= fr["min_x"] and u < fr["max_x"] and v >= fr["min_y"] and v < fr["max_y"]):
-                continue
-            urp = f32(u - f32(bf * invz))
-            PO = [f32(X[j] - Ow[j]) for j in range(3)]
-            d3 = _norm3(PO)
-            dmin, dmax = pts["dist_minmax"][i]
-            if d3 < f32(f32(0.8) * dmin) or d3 > f32(f32(1.2) * dmax):
-                continue
-            Pn = pts["normal"][i]
-            dot = (float(PO[0]) * float(Pn[0]) + float(PO[1]) * float(Pn[1])) + float(PO[2]) * float(Pn[2])
-            if dot < 0.5 * float(d3):
-                continue
-            lv = _predict(dmax, d3, fr["log_scale_factor"], fr["nlevels"])
-            rad = f32(f32(th) * sf[lv])
-            bd, bi = 256, -1
-            for idx in F.area(u, v, rad):
-                kl = int(keys["octave"][idx])
-                if kl < lv - 1 or kl > lv:
-                    continue
-                ex, ey = f32(u - keys["x"][idx]), f32(v - keys["y"][idx])
-                if ur is not None and ur[idx] >= 0:
-                    er = f32(urp - ur[idx])
-                    e2 = f32(f32(f32(ex * ex) + f32(ey * ey)) + f32(er * er))
-                    if float(f32(e2 * isg[kl])) > 7.8:
-                        continue
-                else:
-                    e2 = f32(f32(ex * ex) + f32(ey * ey))
-                    if float(f32(e2 * isg[kl])) > 5.99:
-                        continue
-                d = _ham(pts["desc"][i], fr["desc"][idx])
-                if d < bd:
-                    bd, bi = d, idx
-            if bd <= 50:
-                pm[i] = bi
-                who[bi] = i
-                nm += 1
-        fo = np.array([w if w >= 0 else -1 for w in who], np.int32)
-        return dict(nmatches=nm, frame_out=fo, point_match=np.array(pm, np.int32))
-    if kind in (4, 5):  # SearchByProjection(KeyFrame*, Scw, ...) :327-440 / Fuse(KeyFrame*, Scw, ...) :1094-1236
-        S = T
-        d = float(S[0, 0]) * float(S[0, 0])
-        d = d + float(S[0, 1]) * float(S[0, 1])
-        d = d + float(S[0, 2]) * float(S[0, 2])
-        a = f32(1.0 / float(f32(math.sqrt(d))))  # Mat / scw: convertTo(alpha = 1/scw), float scale
-        T = np.eye(4, dtype=np.float32)
-        T[:3, :] = (S[:3, :] * a).astype(np.float32)
-        Ow = _centre(T)  # -Rcw.t()*tcw
-        for i in range(npnt):
-            if not (pts["flags"][i] & 1):
-                continue
-            X = pts["pos"][i]
-            c = _mat3x1(T, X)
-            if c[2] < 0:
-                continue
-            invz = f32(1.0 / float(c[2])) if kind == 5 else f32(f32(1.0) / c[2])
-            u = f32(f32(fx * f32(c[0] * invz)) + cx)
-            v = f32(f32(fy * f32(c[1] * invz)) + cy)
-            if not (u >= fr["min_x"] and u < fr["max_x"] and v >= fr["min_y"] and v < fr["max_y"]):
-                continue
-            PO = [f32(X[j] - Ow[j]) for j in range(3)]
-            d3 = _norm3(PO)
-            dmin, dmax = pts["dist_minmax"][i]
-            if d3 < f32(f32(0.8) * dmin) or d3 > f32(f32(1.2) * dmax):
-                continue
-            Pn = pts["normal"][i]
-            dot = (float(PO[0]) * float(Pn[0]) + float(PO[1]) * float(Pn[1])) + float(PO[2]) * float(Pn[2])
-            if dot < 0.5 * float(d3):
-                continue
-            lv = _predict(dmax, d3, fr["log_scale_factor"], fr["nlevels"])
-            rad = f32(f32(th) * sf[lv])
-            bd, bi = 256, -1
-            for idx in F.area(u, v, rad):
-                if kind == 4 and who[idx] != -1:  # vpMatched[idx]
-                    continue
-                kl = int(keys["octave"][idx])
-                if kl < lv - 1 or kl > lv:
-                    continue
-                d = _ham(pts["desc"][i], fr["desc"][idx])
-                if d < bd:
-                    bd, bi = d, idx
-            if bd <= 50:
-                pm[i] = bi
-                who[bi] = i
-                nm += 1
-        fo = np.array([w if w >= 0 else -1 for w in who], np.int32)
-        return dict(nmatches=nm, frame_out=fo, point_match=np.array(pm, np.int32))
-    if kind == 1:
-        tlc = _mat3x1(np.asarray(last_Tcw, np.float32), Ow)
-        fwd = tlc[2] > fr["b"] and not mono
-        bwd = -tlc[2] > fr["b"] and not mono
-    for i in range(npnt):
-        fl = pts["flags"][i]
-        dq = pts["desc"][i]
-        if kind == 0:
-            if (level[i] < 0) if frustum else not (fl & 1):
-                continue
-            lv = int(level[i])
-            r = f32(2.5) if track[i, 3] > f32(0.998) else f32(4.0)
-            if f32(th) != f32(1.0):
-                r = f32(r * f32(th))
-            rs = f32(r * sf[lv])
-            cand = F.area(track[i, 0], track[i, 1], rs, lv - 1, lv)
-            bd, bl, bd2, bl2, bi = 256, -1, 256, -1, -1
-            for idx in cand:
-                if who[idx] not in (-1, -2) and obs[idx]:
-                    continue
-                if ur is not None and ur[idx] > 0 and abs(f32(track[i, 2] - ur[idx])) > rs:
-                    continue
-                d = _ham(dq, fr["desc"][idx])
-                if d < bd:
-                    bd2, bd, bl2, bl, bi = bd, d, bl, int(keys["octave"][idx]), idx
-                elif d < bd2:
-                    bl2, bd2 = int(keys["octave"][idx]), d
-            if bd <= 100:
-                if bl == bl2 and f32(bd) > f32(f32(nnratio) * f32(bd2)):
-                    continue
-                who[bi], obs[bi] = i, bool(fl & 2)
-                pm[i] = bi
-                nm += 1
-            continue
-        if not (fl & 1):
-            continue
-        X = pts["pos"][i]
-        c = _mat3x1(T, X)
-        invzc = f32(1.0 / float(c[2]))
-        if kind == 1 and invzc < 0:
-            continue
-        u = f32(f32(f32(fx * c[0]) * invzc) + cx)
-        v = f32(f32(f32(fy * c[1]) * invzc) + cy)
-        if u < fr["min_x"] or u > fr["max_x"] or v < fr["min_y"] or v > fr["max_y"]:
-            continue
-        if kind == 1:
-            o = int(pts["octave"][i])
-            rad = f32(f32(th) * sf[o])
-            if fwd:
-                cand = F.area(u, v, rad, o)
-            elif bwd:
-                cand = F.area(u, v, rad, 0, o)
-            else:
-                cand = F.area(u, v, rad, o - 1, o + 1)
-            thr = 100
-        else:
-            PO = [f32(X[j] - Ow[j]) for j in range(3)]
-            d3 = _norm3(PO)
-            dmin, dmax = pts["dist_minmax"][i]
-            if d3 < f32(f32(0.8) * dmin) or d3 > f32(f32(1.2) * dmax):
-                continue
-            lv = _predict(dmax, d3, fr["log_scale_factor"], fr["nlevels"])
-            rad = f32(f32(th) * sf[lv])
-            cand = F.area(u, v, rad, lv - 1, lv + 1)
-            thr = orb_dist
-        bd, bi = 256, -1
-        for idx in cand:
-            if kind == 1:
-                if who[idx] not in (-1, -2) and obs[idx]:
-                    continue
-                if ur is not None and ur[idx] > 0:
-                    urp = f32(u - f32(bf * invzc))
-                    if abs(f32(urp - ur[idx])) > rad:
-                        continue
-            elif who[idx] not in (-1, -2):
-                continue
-            d = _ham(dq, fr["desc"][idx])
-            if d < bd:
-                bd, bi = d, idx
-        if bd <= thr:
-            who[bi], obs[bi] = i, bool(fl & 2)
-            pm[i] = bi
-            nm += 1
-            if check_ori:
-                hist[_rot_bin(pts["angle"][i], keys["angle"][bi])].append(bi)
-    if kind != 0 and check_ori:
-        sel = _three_max([len(h) for h in hist])
-        for b in range(30):
-            if b in sel:
-                continue
-            for f in hist[b]:
-                who[f] = -2
-                nm -= 1
-    fo = np.array([w if w >= 0 else (-2 if w == -2 else -1) for w in who], np.int32)
-    out = dict(nmatches=nm, frame_out=fo, point_match=np.array(pm, np.int32))
-    if kind == 0:
-        out["track"], out["track_level"] = track, level
-    return out
+# the literal Python restatement lives in tests/projection_literal.py
+from projection_literal import (PyFrame, _ham, _rot_bin, _three_max, py_search,  # noqa: E402,F401
+                                py_search_by_sim3)
 
 
 def _sim3(fr, variant):
@@ -438,14 +84,23 @@ def _same(a, b, kind, frustum=False):
 
 
 # ------------------------------------------------------------------ CPU: oracle pinned
-@pytest.mark.parametrize("kind", [0, 1, 2, 3, 4, 5])
-@pytest.mark.parametrize("variant", [0, 1, 2, 3])
-def test_oracle_vs_python_restatement(kind, variant):
+RESTATEMENT_KINDS, RESTATEMENT_VARIANTS = [0, 1, 2, 3, 4, 5], [0, 1, 2, 3]
+
+
+def restatement_case(kind, variant):
+    """The random problem of test_oracle_vs_python_restatement[variant-kind]: (fr, pts, kw).  Also what
+    tests/test_projection_scenes.py runs its seeded defects on, so the two cannot drift apart."""
     fr = synth.projection_frame(10 + variant, n=400, width=300, height=200)
     pts = synth.projection_points(20 + variant, fr, min(kind, 3), n_points=250, pool=0.3)
     if kind >= 4:
         fr = _sim3(fr, variant)
-    kw = _kw(kind, fr, variant)
+    return fr, pts, _kw(kind, fr, variant)
+
+
+@pytest.mark.parametrize("kind", RESTATEMENT_KINDS)
+@pytest.mark.parametrize("variant", RESTATEMENT_VARIANTS)
+def test_oracle_vs_python_restatement(kind, variant):
+    fr, pts, kw = restatement_case(kind, variant)
     got = oracle.search_by_projection(fr, pts, kind, **kw)
     pk = dict(kw)
     limit = pk.pop("view_cos_limit", 0.5)
@@ -706,64 +361,6 @@ def _sim3_pair_case(seed, n=1200, s12=1.1, ang=0.003, noise=0.6, p_off=0.1, max_
     R12 = np.array([[c, -s, 0], [s, c, 0], [0, 0, 1]], np.float32)
     t12 = np.array([0.01, -0.02, 0.015], np.float32)
     return fr, dict(fr), points(seed + 1), points(seed + 2), f32(s12), R12, t12
-
-
-def py_search_by_sim3(kf1, kf2, pts1, pts2, s12, R12, t12, th):
-    """SearchBySim3 restated statement by statement (src/ORBmatcher.cc:1238-1487)."""
-    a12, a21 = f32(s12), f32(1.0 / float(s12))
-    sR12 = np.zeros((3, 4), np.float32)
-    sR21 = np.zeros((3, 4), np.float32)
-    for r in range(3):
-        for c in range(3):
-            sR12[r, c] = f32(R12[r, c] * a12)          # s12*R12: convertTo(alpha)
-            sR21[r, c] = f32(R12[c, r] * a21)          # (1.0/s12)*R12.t()
-        sR12[r, 3] = t12[r]
-    for r in range(3):                                 # t21 = -sR21*t12 (gemm small path, alpha = -1)
-        t0 = f32(f32(sR21[r, 0] * t12[0]) + f32(sR21[r, 1] * t12[1]))
-        sR21[r, 3] = -f32(t0 + f32(sR21[r, 2] * t12[2]))
-
-    def direction(own, other, pts, A):
-        F = PyFrame(other)
-        To = np.asarray(own["Tcw"], np.float32)
-        keys = other["keys_un"]
-        out = np.full(len(own["desc"]), -1, np.int32)
-        for i in range(len(own["desc"])):
-            if not (pts["flags"][i] & 1):
-                continue
-            c1 = _mat3x1(To, pts["pos"][i])
-            c2 = _mat3x1(A, c1)
-            if c2[2] < 0:
-                continue
-            invz = f32(1.0 / float(c2[2]))
-            u = f32(f32(f32(other["fx"]) * f32(c2[0] * invz)) + f32(other["cx"]))
-            v = f32(f32(f32(other["fy"]) * f32(c2[1] * invz)) + f32(other["cy"]))
-            if not (u >= other["min_x"] and u < other["max_x"] and v >= other["min_y"] and v < other["max_y"]):
-                continue
-            d3 = _norm3(c2)
-            dmin, dmax = pts["dist_minmax"][i]
-            if d3 < f32(f32(0.8) * dmin) or d3 > f32(f32(1.2) * dmax):
-                continue
-            lv = _predict(dmax, d3, other["log_scale_factor"], other["nlevels"])
-            rad = f32(f32(th) * f32(other["scale_factors"][lv]))
-            bd, bi = 1 << 30, -1
-            for idx in F.area(u, v, rad):
-                o = int(keys["octave"][idx])
-                if o < lv - 1 or o > lv:
-                    continue
-                d = _ham(pts["desc"][i], other["desc"][idx])
-                if d < bd:
-                    bd, bi = d, idx
-            if bd <= 100:
-                out[i] = bi
-        return out
-
-    m1 = direction(kf1, kf2, pts1, sR21)
-    m2 = direction(kf2, kf1, pts2, sR12)
-    match12 = np.full(len(kf1["desc"]), -1, np.int32)
-    for i1, idx2 in enumerate(m1):
-        if idx2 >= 0 and m2[idx2] == i1:
-            match12[i1] = idx2
-    return int((match12 >= 0).sum()), match12
 
 
 @pytest.mark.parametrize("seed,s12,th", [(0, 1.1, 7.5), (1, 0.93, 7.5), (2, 1.0, 3.0)])

@@ -17,7 +17,9 @@ enum {
   ORBX_DBG_CANDIDATES = 4,  /* u32 per candidate slot (score<<24|y<<12|x), cand_total slots   */
   ORBX_DBG_OCT_COUNTS = 5,  /* int32 per level                                                */
   ORBX_DBG_OCT_OUT = 6,     /* u32 per octree output slot, oct_total slots                    */
-  ORBX_DBG_LEVEL_INFO = 7   /* int32 x8 per level: w,h,cell_begin,cell_end,oct_off,oct_cap,nfeat,nIni */
+  ORBX_DBG_LEVEL_INFO = 7,  /* int32 x8 per level: w,h,cell_begin,cell_end,oct_off,oct_cap,nfeat,nIni */
+  ORBX_DBG_PATCH_SLOTS = 8  /* int32 x128: k_describe's patch slot s = lane + 64 * load -> row << 2 | chunk
+                               of the row's span, 255 = unused (the table the kernel reads; no image)   */
 };
 
 /* Returns the number of bytes the item occupies (copies min(cap, size)); <0 on error. */
@@ -42,9 +44,12 @@ enum {
                              l / g == (((2l + 1) * magic) >> 32) >> shift for every l < gx*gy*gz */
   ORBX_LP_XTAB = 6,       /* x4 per output column of level a0 >= 1: sx0, sx1, a0, a1 (the resize coefficients) */
   ORBX_LP_YTAB = 7,       /* x4 per output row of level a0 >= 1: sy0, sy1, b0, b1 */
-  ORBX_LP_PATH = 8        /* x8 per level >= 1, the resize kernel chosen for it: path (1: k_resize_strip, 0: k_resize),
+  ORBX_LP_PATH = 8,       /* x8 per level >= 1, the resize kernel chosen for it: path (1: k_resize_strip, 0: k_resize),
                              tile columns, tile rows (its grid), tile width, tile height, LDS row stride,
                              footprint rows staged, strip rows per thread (0 for k_resize) */
+  ORBX_LP_FAST = 9        /* x8 per k_fast launch group: first cell, end cell, then the kernel instance k_fast<S, RP, NK>
+                             (LDS row stride, region rows per compass instruction, window loads per lane) and
+                             its LDS: window tile bytes, score map bytes, bytes per block */
 };
 long long orbx_debug_launch_plan(const orbx_extractor_params* params, int width, int height, int what, int a0,
                                  int a1, int a2, long long* dst, size_t cap);

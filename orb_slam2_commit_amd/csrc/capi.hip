@@ -34,6 +34,7 @@ hipError_t launch_extract_stages(const Geometry& Gh, const Geometry* Gd, const C
                                  int kp_cap, hipStream_t st, StageTimer* T);
 size_t octree_smem_host(int NC, int cell_cap, int kcap);
 hipError_t octree_set_smem_limit(size_t bytes);
+const uint8_t* patch_slot_table();
 }  // namespace orbx
 
 using namespace orbx;
@@ -358,6 +359,12 @@ orbx_status build_plan(const orbx_extractor_params& p, const Tables& t, int W, i
       g.tile_bytes = ((hmax + 6) * g.s + 15) & ~15;
       g.map_bytes = ((hmax + 2) * g.s + 15) & ~15;
       g.smem = g.tile_bytes + g.map_bytes + 2 * wmax * hmax;
+      // window loads per lane: a load covers 64 / (chunks per row) window rows (21 at S = 40 / 48, 12
+      // at S = 80).  The tallest cell the grid above can make is 53 rows (a single cell row, whose
+      // window is clipped to the region: 59 rows; two or more rows give hCell <= 45), so k_fast is
+      // built for 2 or 3 loads at S = 40 / 48 and 4 or 5 at S = 80 (checked below)
+      const int rpi = 64 / ((g.s + 15) / 16);
+      g.nk = std::max(g.s == 80 ? 4 : 2, (hmax + 6 + rpi - 1) / rpi);
     };
     constexpr int kFastLdsFit = 5 * 1024;
     int split = 0, wa = 1, ha = 1;  // levels [0, split) fit kFastLdsFit together
@@ -395,6 +402,8 @@ orbx_status build_plan(const orbx_extractor_params& p, const Tables& t, int W, i
       G.fg[1].c1 = (int)P.cells.size();
       G.n_fg = 2;
     }
+    for (int g = 0; g < G.n_fg; g++)
+      if (G.fg[g].nk > (G.fg[g].s == 80 ? 5 : 3)) return ORBX_ERR_SIZE;  // no k_fast instance stages that many
   }
   // k_resize staging bound: source footprint of every 128x16 output tile
   G.rz_rows = 1;
@@ -1297,6 +1306,10 @@ extern "C" long long orbx_debug_copy(orbx_extractor* h, int what, int image, int
       }
       device_src = false;
       break;
+    case ORBX_DBG_PATCH_SLOTS:
+      host.assign(patch_slot_table(), patch_slot_table() + 128);
+      device_src = false;
+      break;
     default:
       return ORBX_ERR_ARG;
   }
@@ -1432,6 +1445,12 @@ extern "C" long long orbx_debug_launch_plan(const orbx_extractor_params* params,
         const int tw = f ? kRsTW : kRzTW, th = f ? kRsTH : kRzTH;
         out.insert(out.end(), {f ? 1 : 0, (G.lv[l].w + tw - 1) / tw, (G.lv[l].h + th - 1) / th, tw, th,
                                f ? kRsStride : G.rz_stride, f ? kRsRows : G.rz_rows, f ? kRsR : 0});
+      }
+      break;
+    case ORBX_LP_FAST:
+      for (int g = 0; g < G.n_fg; g++) {
+        const Geometry::FastGroup& F = G.fg[g];
+        out.insert(out.end(), {F.c0, F.c1, F.s, F.rp, F.nk, F.tile_bytes, F.map_bytes, F.smem});
       }
       break;
     case ORBX_LP_GRIDS: {

@@ -523,12 +523,17 @@ __global__ __launch_bounds__(BS, ORBX_BLUR_WPE) void k_blur(const Geometry* __re
     constexpr int CPR = kBIn / 16, NQ = TR * CPR, KQ = (NQ + BS - 1) / BS;
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)src, (short)0, w * h, 0x00020000);
     uint32_t v[KQ][4];
+    // only what an output of the level reads is staged: tile rows up to the last output row's + 3
+    // and chunks that begin at or left of column w + 2, the right reflection's reach (the rest
+    // would be reflected re-reads; what is computed from the unstaged LDS bytes lands in the
+    // level's padding)
+    const int ty_last = min(kBlurTileH, h - y0) + 5, j_last = (w + 2 - (x0 - 4)) >> 4;
 #pragma unroll
     for (int k = 0; k < KQ; k++) {
       const int q = k * BS + tid;
       const int ty = q / CPR, j = q - ty * CPR;
       v[k][0] = v[k][1] = v[k][2] = v[k][3] = 0;
-      if (q < NQ) {
+      if (q < NQ && ty <= ty_last && j <= j_last) {
         const int sy = reflect101(y0 - 3 + ty, h);
         const int o = sy * w + x0 - 4 + 16 * j;
         if (o >= 0 && o + 16 <= w * h) {
@@ -550,7 +555,8 @@ __global__ __launch_bounds__(BS, ORBX_BLUR_WPE) void k_blur(const Geometry* __re
     for (int k = 0; k < KQ; k++) {
       const int q = k * BS + tid;
       const int ty = q / CPR, j = q - ty * CPR;
-      if (q < NQ) *(uint4*)&tin[ty * kBIn + 16 * j] = make_uint4(v[k][0], v[k][1], v[k][2], v[k][3]);
+      if (q < NQ && ty <= ty_last && j <= j_last)
+        *(uint4*)&tin[ty * kBIn + 16 * j] = make_uint4(v[k][0], v[k][1], v[k][2], v[k][3]);
     }
   }
   const bool left = x0 < 3, right = x0 + kBlurTileW + 3 > w;
@@ -824,12 +830,13 @@ __device__ unsigned int* fast_probe_buf;
 #endif
 
 // S: LDS row stride of the window tile and the score map (multiple of 16, >= window width);
-// RP: region rows per compass instruction (2 when the widest cell fits 32 lanes)
+// RP: region rows per compass instruction (2 when the widest cell fits 32 lanes);
+// NK: 16-B window loads per lane, enough for the launch group's tallest window (FastGroup::nk)
 #ifndef ORBX_FAST_CPW
 #define ORBX_FAST_CPW 2
 #endif
 constexpr int kFastCPW = ORBX_FAST_CPW;  // FAST cells per wave
-template <int S, int RP>
+template <int S, int RP, int NK>
 __global__ __launch_bounds__(64) void k_fast(const Geometry* __restrict__ G, const CellInfo* __restrict__ cells,
                                              BatchPtrs B, int grp, XcdRemap R) {
   // dynamic LDS sized by the launch group's largest cell (G->fg[grp])
@@ -842,7 +849,8 @@ __global__ __launch_bounds__(64) void k_fast(const Geometry* __restrict__ G, con
   const int img = bi.y, lane = threadIdx.x;
   // 1. window -> registers -> LDS: lane = (row, 16-B chunk); window pixel (r, col) lands at tile[r*S + col]
   constexpr int CPR = (S + 15) / 16, RPI = 64 / CPR;
-  constexpr int KMAX = (kMaxCell + 6 + RPI - 1) / RPI;
+  constexpr int KMAX = NK;  // the host sizes NK by the group's tallest window: NK * RPI >= its rows
+  static_assert(NK >= 1 && NK <= (kMaxCell + 6 + RPI - 1) / RPI, "no window is taller than kMaxCell + 6 rows");
   const int lr = lane / CPR, lj = lane - lr * CPR;
   const bool lane_ok = lr < RPI;
   // every load unconditional (a lane outside the window reads past num_records and gets zeros): no
@@ -919,11 +927,15 @@ __global__ __launch_bounds__(64) void k_fast(const Geometry* __restrict__ G, con
   // rewrites the same values).  Returns the corner count.
   auto detect = [&](int th) -> int {
     int n = 0;
-    for (int y0r = 0; y0r < H; y0r += QU * RP) {
+    // QU * RP region rows per trip; nu: the sub-steps of the trip whose first row is inside the region
+    // (wave-uniform).  Full trips (nu = QU) are branch-free; the peeled last trip skips the others.
+    auto trip = [&](int y0r, auto fullc, int nu) {
+      constexpr bool full = decltype(fullc)::value;
       const int eb = (y0r + ly) * S + lx;
       int cv[QU], c0[QU], c4[QU], c8[QU], c12[QU];
 #pragma unroll
       for (int u = 0; u < QU; u++) {
+        if (!full && u >= nu) break;
         const uint8_t* t = tile + eb + u * RP * S;
         cv[u] = t[3 * S + 3];
         c0[u] = t[6 * S + 3];
@@ -933,6 +945,7 @@ __global__ __launch_bounds__(64) void k_fast(const Geometry* __restrict__ G, con
       }
 #pragma unroll
       for (int u = 0; u < QU; u++) {
+        if (!full && u >= nu) break;
         // two ADJACENT compass points beyond the threshold <=> (p0 | p8) & (p4 | p12) per
         // polarity, i.e. min(max(p0,p8), max(p4,p12)) > c+t or max(min(p0,p8), min(p4,p12)) < c-t:
         // min/max on the raw bytes, one difference per polarity
@@ -945,7 +958,10 @@ __global__ __launch_bounds__(64) void k_fast(const Geometry* __restrict__ G, con
         if (hit) list[n + lane_rank(m)] = (uint16_t)(eb + u * RP * S);
         n += __popcll(m);
       }
-    }
+    };
+    int y0r = 0;
+    for (; y0r + QU * RP <= H; y0r += QU * RP) trip(y0r, std::true_type{}, QU);
+    if (y0r < H) trip(y0r, std::false_type{}, (H - y0r + RP - 1) / RP);
     __syncthreads();
 #ifdef ORBX_FAST_PROBE
     if (th == ini) ts_mid = __builtin_amdgcn_s_memtime(), n_compass = n;
@@ -1053,6 +1069,12 @@ __global__ __launch_bounds__(64) void k_fast(const Geometry* __restrict__ G, con
   }
 #endif
   }  // cells of this wave
+}
+
+// k_fast<S, RP, NK> for a launch group's load count nk = N0 or N0 + 1 (the plan refuses any other)
+template <int S, int RP, int N0>
+static auto fast_kernel(int nk) -> decltype(&k_fast<S, RP, N0>) {
+  return nk <= N0 ? k_fast<S, RP, N0> : k_fast<S, RP, N0 + 1>;
 }
 
 // ----------------------------------------------------------------- octree
@@ -1572,11 +1594,49 @@ constexpr int kPS = 80;  // LDS row stride of the staged patches (bytes): 20 dwo
 // bytes per wave: the blurred patch + the descriptor words
 constexpr int kDescLds = kPatchRows * kPS + 256;
 // half-width hw(r) of patch row r = 0..36 (row offset r - 18) the rotated pattern can reach
+struct PatchHW {
+  int v[kPatchRows];
+};
+constexpr PatchHW kPatchHW = {{6,  8,  10, 11, 12, 13, 14, 15, 16, 16, 17, 17, 18, 18, 18, 18, 18, 18, 18,
+                               18, 18, 18, 18, 18, 18, 17, 17, 16, 16, 15, 14, 13, 12, 11, 10, 8,  6}};
+__constant__ PatchHW c_patch_hw = kPatchHW;
 // describe patch slots: slot s -> (row << 2 | k-th chunk of the row's span), 2 / 3 / 4 slots per row
-// (the most 16-B chunks the row's span covers over the 16 alignments), 124 slots, 0xFF past them
-__constant__ uint8_t c_patch_slot[128] = {0,1,4,5,8,9,10,12,13,14,16,17,18,20,21,22,24,25,26,28,29,30,32,33,34,36,37,38,40,41,42,43,44,45,46,47,48,49,50,51,52,53,54,55,56,57,58,59,60,61,62,63,64,65,66,67,68,69,70,71,72,73,74,75,76,77,78,79,80,81,82,83,84,85,86,87,88,89,90,91,92,93,94,95,96,97,98,99,100,101,102,103,104,105,106,107,108,109,110,112,113,114,116,117,118,120,121,122,124,125,126,128,129,130,132,133,134,136,137,138,140,141,144,145,255,255,255,255};
-__constant__ int c_patch_hw[kPatchRows] = {6,  8,  10, 11, 12, 13, 14, 15, 16, 16, 17, 17, 18, 18, 18, 18, 18, 18, 18,
-                                           18, 18, 18, 18, 18, 18, 17, 17, 16, 16, 15, 14, 13, 12, 11, 10, 8,  6};
+// (the most 16-B chunks the row's span covers over the 16 alignments), 124 slots, 0xFF past them.
+// Order: the four lanes of a quad (slots 4i .. 4i+3) are four consecutive rows of one chunk index --
+// 64 contiguous bytes of the tiled blurred level whenever they fall inside one 8-row tile, two
+// lines otherwise (a row-major quad touches 3-4) -- chunk index by chunk index; the one row each
+// chunk index has left over (37 / 37 / 33 / 17 rows) shares the last quad: 31 quads.
+struct PatchSlots {
+  uint8_t e[128];
+};
+constexpr int patch_row_chunks(int r) {  // most chunks [18+a-hw, 18+a+hw] covers over a = 0..15
+  int m = 0;
+  for (int a = 0; a < 16; a++) {
+    const int n = ((kPatchR + a + kPatchHW.v[r]) >> 4) - ((kPatchR + a - kPatchHW.v[r]) >> 4) + 1;
+    m = n > m ? n : m;
+  }
+  return m;
+}
+constexpr PatchSlots make_patch_slots() {
+  PatchSlots t{};
+  for (int s = 0; s < 128; s++) t.e[s] = 0xFF;
+  int n = 0, nrest = 0;
+  uint8_t rest[12] = {};
+  for (int ch = 0; ch < 4; ch++) {
+    int rows[kPatchRows] = {}, nr = 0;  // rows whose span can reach a ch-th chunk (one contiguous run)
+    for (int r = 0; r < kPatchRows; r++)
+      if (patch_row_chunks(r) > ch) rows[nr++] = r;
+    for (int q = 0; q + 4 <= nr; q += 4)
+      for (int i = 0; i < 4; i++) t.e[n++] = (uint8_t)(rows[q + i] << 2 | ch);
+    for (int q = nr & ~3; q < nr; q++) rest[nrest++] = (uint8_t)(rows[q] << 2 | ch);
+  }
+  for (int i = 0; i < nrest; i++) t.e[n++] = rest[i];
+  return t;
+}
+constexpr PatchSlots kPatchSlots = make_patch_slots();
+static_assert(kPatchSlots.e[123] != 0xFF && kPatchSlots.e[124] == 0xFF, "124 patch slots: two loads per lane");
+__constant__ PatchSlots c_patch_slot = kPatchSlots;
+const uint8_t* patch_slot_table() { return kPatchSlots.e; }
 
 #ifndef ORBX_DESC_K
 #define ORBX_DESC_K 8
@@ -1691,10 +1751,10 @@ __global__ __launch_bounds__(BS) void k_describe(const Geometry* __restrict__ G,
   int srow[kPatchLd], skk[kPatchLd], shw[kPatchLd];
 #pragma unroll
   for (int k = 0; k < kPatchLd; k++) {
-    const int e = c_patch_slot[lane + 64 * k];
+    const int e = c_patch_slot.e[lane + 64 * k];
     srow[k] = e == 0xFF ? -1 : e >> 2;
     skk[k] = e & 3;
-    shw[k] = c_patch_hw[e == 0xFF ? 0 : e >> 2];
+    shw[k] = c_patch_hw.v[e == 0xFF ? 0 : e >> 2];
   }
   uint32_t pv[2][kPatchLd][4];
   int pdst[2][kPatchLd];  // LDS byte offset of each loaded chunk (-1: none)
@@ -1886,9 +1946,10 @@ hipError_t launch_extract_stages(const Geometry& Gh, const Geometry* Gd, const C
     for (int g = 0; g < Gh.n_fg; g++) {
       const Geometry::FastGroup& F = Gh.fg[g];
       if (F.c1 <= F.c0) continue;
-      auto kf = F.s == 40   ? (F.rp == 2 ? k_fast<40, 2> : k_fast<40, 1>)
-                : F.s == 48 ? (F.rp == 2 ? k_fast<48, 2> : k_fast<48, 1>)
-                            : k_fast<80, 1>;
+      // (S, RP, NK) as the plan's layout chose them: S = 48 and 80 hold cells wider than 32 (RP = 1)
+      auto kf = F.s == 40   ? (F.rp == 2 ? fast_kernel<40, 2, 2>(F.nk) : fast_kernel<40, 1, 2>(F.nk))
+                : F.s == 48 ? fast_kernel<48, 1, 2>(F.nk)
+                            : fast_kernel<80, 1, 4>(F.nk);
       hipLaunchKernelGGL(kf, fast_grid[g], dim3(64), F.smem, st, Gd, cells, B, g, fast_rm[g]);
     }
     T->end(ST_FAST, st);

@@ -69,6 +69,7 @@ struct Geometry {
   // region rows per compass instruction rp (2 when the group's cells are <= 32 wide)
   struct FastGroup {
     int c0, c1, s, rp, tile_bytes, map_bytes, smem;
+    int nk;  // 16-B window loads per lane (k_fast's NK): covers the group's tallest window
   } fg[2];
   int n_fg;
   int rz_rows;    // k_resize: max source rows staged per 128x16 output tile

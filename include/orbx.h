@@ -872,6 +872,104 @@ typedef struct {
 orbx_status orbx_search_for_triangulation(const orbx_tri_problem* p, int device); /* host pointers */
 orbx_status orbx_search_for_triangulation_device(const orbx_tri_problem* problems, int n, void* stream);
 
+/* LocalMapping::CreateNewMapPoints() -- src/LocalMapping.cc:281-558, include/LocalMapping.h:95, with
+ * ComputeF12 (:672-699), KeyFrame::SetPose (src/KeyFrame.cc:80-101), ComputeSceneMedianDepth(2)
+ * (:784-819), UnprojectStereo (:759-781) and, per new point, MapPoint::UpdateNormalAndDepth of its two
+ * observations (src/MapPoint.cc:343-393).  The neighbours (GetBestCovisibilityKeyFrames(nn), in that
+ * order) form a chain on the stream: the gates and F12 of every neighbour in one launch, then per
+ * neighbour SearchForTriangulation (matcher(0.6, false): no rotation check, bOnlyStereo = false) and
+ * the per-pair triangulation; an accepted pair gives feature idx1 of the current keyframe a MapPoint,
+ * which the next neighbour's search skips.  Nothing returns to the host in between. */
+#define ORBX_NEW_POINTS_MAX_NEIGHBOURS 20    /* nn of :284-286 for a monocular map */
+#define ORBX_NEW_POINTS_MAX_FEATURES 65535   /* a FeatureVector node position fits the search's 16-bit key */
+typedef struct {
+  orbx_tri_kf kf;           /* mvKeysUn, mDescriptors, mvuRight (NULL: none), has_mp, mFeatVec */
+  const float* keys_xy;     /* mvKeys[i].pt, n x 2: the DISTORTED keypoints UnprojectStereo reads (NULL: keys_un's) */
+  const float* depth;       /* mvDepth, n (NULL: no feature has a depth) */
+  const float* mp_pos;      /* n x 3: GetWorldPos() of the MapPoint of feature i where has_mp[i]; read for a
+                               neighbour when monocular (ComputeSceneMedianDepth), else may be NULL */
+  float Tcw[16];            /* GetPose(), row-major */
+  float fx, fy, cx, cy;     /* invfx = 1.0f / fx, invfy = 1.0f / fy as Frame's constructor computes them */
+  float mb, mbf;
+  int n_levels;             /* mnScaleLevels, 1..16 */
+  float scale_factors[16];  /* mvScaleFactors */
+  float level_sigma2[16];   /* mvLevelSigma2 */
+} orbx_new_points_kf;
+
+typedef struct {
+  orbx_new_points_kf current;        /* mpCurrentKeyFrame */
+  int n_neighbours;                  /* 0..ORBX_NEW_POINTS_MAX_NEIGHBOURS */
+  const orbx_new_points_kf* neighbours;  /* vpNeighKFs (a HOST array in both forms) */
+  int monocular;                     /* mbMonocular */
+  float scale_factor;                /* mpCurrentKeyFrame->mfScaleFactor: ratioFactor = 1.5f * it (:312) */
+} orbx_new_points_problem;
+
+/* per matched pair (debug probe) */
+#define ORBX_NP_NONE 0            /* no pair for this feature */
+#define ORBX_NP_TRIANGULATED 1    /* accepted, linear triangulation (:417-440) */
+#define ORBX_NP_UNPROJECT1 2      /* accepted, mpCurrentKeyFrame->UnprojectStereo (:441-444) */
+#define ORBX_NP_UNPROJECT2 3      /* accepted, pKF2->UnprojectStereo (:445-448) */
+#define ORBX_NP_LOW_PARALLAX 4    /* :449-450 */
+#define ORBX_NP_W_ZERO 5          /* :433 */
+#define ORBX_NP_Z1 6              /* :457 */
+#define ORBX_NP_Z2 7              /* :461 */
+#define ORBX_NP_REPROJ1_MONO 8    /* :476 */
+#define ORBX_NP_REPROJ1_STEREO 9  /* :487 */
+#define ORBX_NP_REPROJ2_MONO 10   /* :503 */
+#define ORBX_NP_REPROJ2_STEREO 11 /* :514 */
+#define ORBX_NP_DIST_ZERO 12      /* :526 */
+#define ORBX_NP_RATIO_BELOW 13    /* :534, ratioDist*ratioFactor < ratioOctave */
+#define ORBX_NP_RATIO_ABOVE 14    /* :534, ratioDist > ratioOctave*ratioFactor */
+#define ORBX_NP_DEPTH_GUARD 15    /* UnprojectStereo chosen for a feature with mvDepth <= 0: the reference
+                                     goes on with an empty Mat (undefined); no point is made */
+/* per neighbour */
+#define ORBX_NP_NB_RAN 0
+#define ORBX_NP_NB_BASELINE 1     /* baseline < pKF2->mb (:339) */
+#define ORBX_NP_NB_RATIO 2        /* baseline / medianDepthKF2 < 0.01 (:351) */
+#define ORBX_NP_NB_NO_DEPTHS 3    /* monocular and pKF2 holds no MapPoint: vDepths[(0-1)/2] is undefined in
+                                     the reference; the neighbour is skipped */
+#define ORBX_NP_NB_STOPPED 4      /* CheckNewKeyFrames() returned true before it (:320) */
+
+/* Host pointers for orbx_create_new_map_points (_bool), device pointers for the _device form.  Point
+ * arrays have room for current.kf.n points (a feature gets at most one); the per-neighbour arrays for
+ * n_neighbours entries.  New points come in the reference's order: neighbour, then ascending idx1. */
+typedef struct {
+  int32_t* n_new;            /* 1: nnew */
+  int32_t* neighbours_done;  /* 1: loop bodies entered (:318-557) before a stop */
+  int32_t* point_idx;        /* x3: neighbour, idx1, idx2 */
+  float* point_pos;          /* x3: x3D */
+  float* point_normal;       /* x3: mNormalVector */
+  float* point_dist;         /* x2: mfMinDistance, mfMaxDistance */
+  int32_t* nb_skip;          /* ORBX_NP_NB_* */
+  int32_t* nb_nmatches;      /* vMatchedIndices.size() (0 when skipped) */
+  float* nb_baseline;
+  float* nb_median_depth;    /* monocular only (0 otherwise) */
+  uint8_t* has_mp1;          /* current.kf.n: the current keyframe's has_mp after the call */
+} orbx_new_points_result;
+
+typedef struct orbx_new_points orbx_new_points;
+orbx_status orbx_new_points_create(int device, orbx_new_points** out);
+orbx_status orbx_new_points_destroy(orbx_new_points* h);
+/* The handle's own flag (pinned, device-readable): the CheckNewKeyFrames() of :320.  The first
+ * neighbour always runs; before every later one the device reads the flag, and once it reads it
+ * non-zero no later neighbour runs (nb_skip = ORBX_NP_NB_STOPPED, neighbours_done says how many did). */
+orbx_status orbx_new_points_stop_flag(orbx_new_points* h, volatile int** flag);
+/* ORBX_ERR_SIZE, before anything is sized, for n_neighbours > ORBX_NEW_POINTS_MAX_NEIGHBOURS or a
+ * keyframe of more than ORBX_NEW_POINTS_MAX_FEATURES features; ORBX_ERR_ARG for negative sizes, missing
+ * arrays, a FeatureVector that is no CSR over the features, octaves outside [0, n_levels).  One copy
+ * in, one copy back. */
+orbx_status orbx_create_new_map_points(orbx_new_points* h, const orbx_new_points_problem* problem,
+                                       const orbx_new_points_result* result);
+/* The same with the reference's flag type (mbAbortBA / CheckNewKeyFrames() are bools): *stop is
+ * followed by the calling thread while it waits, as orbx_ba_run_bool does; NULL: never stops. */
+orbx_status orbx_create_new_map_points_bool(orbx_new_points* h, const orbx_new_points_problem* problem,
+                                            const orbx_new_points_result* result, const volatile bool* stop);
+/* Device arrays (the structs themselves and `neighbours` are host memory), enqueued on `stream`; the
+ * flag read is the handle's own.  result->has_mp1 must hold current.kf.has_mp's values on entry (it is
+ * the chain's table; current.kf.has_mp itself is not read).  The arrays are not validated. */
+orbx_status orbx_create_new_map_points_device(orbx_new_points* h, const orbx_new_points_problem* problem,
+                                              const orbx_new_points_result* result, void* stream);
+
 /* Optimizer::PoseOptimization(Frame*) -- src/Optimizer.cc:287-528, include/Optimizer.h:71:
  * one SE3 vertex, EdgeSE3ProjectXYZOnlyPose (monocular) / EdgeStereoSE3ProjectXYZOnlyPose
  * (mvuRight >= 0) edges with Huber kernels, four rounds of optimize(10) restarting from

@@ -213,6 +213,33 @@ int orbx_debug_initializer_host(const float* keys1_xy, int n1, const float K[9],
                                 uint8_t* triangulated, orbx_initializer_result* result);
 float orbx_debug_acosf_det(float x);
 
+/* CreateNewMapPoints test options of one handle (a production caller never sets them; NULL restores
+ * the defaults).  raise_after_neighbour: the stop flag reads raised at every check after that
+ * neighbour's loop body (-1 off), as LocalBA's raise_stop_after.  probes: the next host calls also
+ * bring back the per-pair and per-neighbour intermediates below (off: they cost nothing). */
+typedef struct {
+  int raise_after_neighbour;
+  int probes;
+} orbx_new_points_debug_options;
+int orbx_debug_new_points_options(orbx_new_points* h, const orbx_new_points_debug_options* options);
+/* The probes of the handle's last host call, n_neighbours rows each; returns the item's size in bytes
+ * (copies min(cap, size)), ORBX_ERR_STATE when that call ran without probes. */
+enum {
+  ORBX_NP_PROBE_EXIT = 0,    /* uint8 x n1 per neighbour: ORBX_NP_* of feature idx1's pair */
+  ORBX_NP_PROBE_COS = 1,     /* float x n1 x 3: cosParallaxRays, cosParallaxStereo1, cosParallaxStereo2 */
+  ORBX_NP_PROBE_F12 = 2,     /* float x 9 (zero for a neighbour the gate skipped) */
+  ORBX_NP_PROBE_MATCH12 = 3  /* int32 x n1: the search's match12 (-1 everywhere for a neighbour that did not run) */
+};
+long long orbx_debug_new_points_probe(orbx_new_points* h, int what, void* dst, size_t cap);
+/* Neighbour `neighbour`'s share of CreateNewMapPoints with the kernels' own routines compiled for the
+ * host (no device is touched): the gate (skip code, baseline, median depth, F12) and, when it ran, the
+ * per-pair routine on the caller's match12 (n1 entries, -1 none).  Per feature of the current keyframe:
+ * exit (n1), cos (n1 x 3), pos / normal (n1 x 3), dist (n1 x 2); values are written where exit is an
+ * accepted code.  The caller owns the chain (has_mp between neighbours) and the search. */
+int orbx_debug_new_points_host(const orbx_new_points_problem* problem, int neighbour, const int32_t* match12,
+                               int32_t* skip, float* baseline, float* median_depth, float F12[9], uint8_t* exit_code,
+                               float* cos3, float* pos, float* normal, float* dist);
+
 #ifdef __cplusplus
 }
 #endif

@@ -148,6 +148,28 @@ class TriProblem(C.Structure):
                 ("check_ori", C.c_int), ("match12", C.c_void_p), ("nmatches", C.c_void_p)]
 
 
+class NewPointsKF(C.Structure):  # orbx_new_points_kf (LocalMapping::CreateNewMapPoints)
+    _fields_ = [("kf", TriKF), ("keys_xy", C.c_void_p), ("depth", C.c_void_p), ("mp_pos", C.c_void_p),
+                ("Tcw", C.c_float * 16), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("mb", C.c_float), ("mbf", C.c_float), ("n_levels", C.c_int), ("scale_factors", C.c_float * 16),
+                ("level_sigma2", C.c_float * 16)]
+
+
+class NewPointsProblem(C.Structure):  # orbx_new_points_problem
+    _fields_ = [("current", NewPointsKF), ("n_neighbours", C.c_int), ("neighbours", C.POINTER(NewPointsKF)),
+                ("monocular", C.c_int), ("scale_factor", C.c_float)]
+
+
+class NewPointsResult(C.Structure):  # orbx_new_points_result
+    _fields_ = [(k, C.c_void_p) for k in ("n_new", "neighbours_done", "point_idx", "point_pos", "point_normal",
+                                          "point_dist", "nb_skip", "nb_nmatches", "nb_baseline", "nb_median_depth",
+                                          "has_mp1")]
+
+
+class NewPointsDebugOptions(C.Structure):  # include/orbx_debug.h orbx_new_points_debug_options
+    _fields_ = [("raise_after_neighbour", C.c_int), ("probes", C.c_int)]
+
+
 class FramePoints(C.Structure):
     _fields_ = [("kps", C.c_void_p), ("depth", C.c_void_p), ("count", C.c_void_p), ("cap", C.c_int),
                 ("Twc", C.c_float * 12), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
@@ -287,6 +309,12 @@ SIGNATURES = {
     "orbx_sim3_from_tcw": ([P, P], None),
     "orbx_search_for_triangulation": ([C.POINTER(TriProblem), C.c_int], C.c_int),
     "orbx_search_for_triangulation_device": ([C.POINTER(TriProblem), C.c_int, P], C.c_int),
+    "orbx_new_points_create": ([C.c_int, C.POINTER(C.c_void_p)], C.c_int),
+    "orbx_new_points_destroy": ([P], C.c_int),
+    "orbx_new_points_stop_flag": ([P, C.POINTER(C.POINTER(C.c_int))], C.c_int),
+    "orbx_create_new_map_points": ([P, C.POINTER(NewPointsProblem), C.POINTER(NewPointsResult)], C.c_int),
+    "orbx_create_new_map_points_bool": ([P, C.POINTER(NewPointsProblem), C.POINTER(NewPointsResult), P], C.c_int),
+    "orbx_create_new_map_points_device": ([P, C.POINTER(NewPointsProblem), C.POINTER(NewPointsResult), P], C.c_int),
     "orbx_distinctive_descriptors": ([P, P, C.c_int, P, P, C.c_int], C.c_int),
     "orbx_distinctive_descriptors_device": ([P, P, C.c_int, P, P, P], C.c_int),
     "orbx_undistort_keypoints": ([P, C.c_int, C.POINTER(Camera), P, C.c_int], C.c_int),
@@ -360,6 +388,9 @@ SIGNATURES = {
     "orbx_debug_ba_options": ([P, C.POINTER(BaDebugOptions)], C.c_int),
     "orbx_debug_ba_capture_select": ([P, C.c_int, C.c_int, C.c_int], C.c_int),
     "orbx_debug_ba_capture_read": ([P, C.c_int, P, C.c_size_t], C.c_longlong),
+    "orbx_debug_new_points_options": ([P, C.POINTER(NewPointsDebugOptions)], C.c_int),
+    "orbx_debug_new_points_probe": ([P, C.c_int, P, C.c_size_t], C.c_longlong),
+    "orbx_debug_new_points_host": ([C.POINTER(NewPointsProblem), C.c_int, P, P, P, P, P, P, P, P, P, P], C.c_int),
     "orbx_debug_hbm_copy": ([P, P, C.c_size_t, C.c_int, C.POINTER(C.c_float)], C.c_int),
 }
 

@@ -732,7 +732,8 @@ long long orbx_sizeof(const char* type) {
   ORBX_SIZEOF(orbx_camera) ORBX_SIZEOF(orbx_sim3_problem) ORBX_SIZEOF(orbx_init_problem)
   ORBX_SIZEOF(orbx_sim3_solver_problem) ORBX_SIZEOF(orbx_sim3_params) ORBX_SIZEOF(orbx_sim3_result)
   ORBX_SIZEOF(orbx_optimize_sim3_problem) ORBX_SIZEOF(orbx_essential_graph_problem)
-  ORBX_SIZEOF(orbx_essential_graph_result)
+  ORBX_SIZEOF(orbx_essential_graph_result) ORBX_SIZEOF(orbx_new_points_kf)
+  ORBX_SIZEOF(orbx_new_points_problem) ORBX_SIZEOF(orbx_new_points_result)
 #undef ORBX_SIZEOF
   return -1;
 }

@@ -153,7 +153,7 @@ __device__ __forceinline__ void sincos_det(float xf, const double* __restrict__ 
 
 // Double sin/cos by Cody-Waite reduction + Taylor polynomials: basic IEEE operations only, so the
 // CPU restatements reproduce it bit for bit (SE3Quat::exp in poseopt.hip, cv::Rodrigues in sim3.hip).
-__device__ __forceinline__ void sincos_d(double x, double* s_out, double* c_out) {
+__host__ __device__ __forceinline__ void sincos_d(double x, double* s_out, double* c_out) {
   const double kInvPio2 = 6.36619772367581382433e-01;
   const double kPio2Hi = 1.57079632673412561417e+00;
   const double kPio2Lo = 6.07710050650619224932e-11;

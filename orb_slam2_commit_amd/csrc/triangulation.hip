@@ -199,6 +199,12 @@ __global__ __launch_bounds__(TBS) void k_search_for_triangulation(const orbx_tri
   if (tid == 0) *P.nmatches = s_count - s_drop;
 }
 
+// the same kernel over device-resident problems, for a caller inside the library (newpoints.hip)
+hipError_t launch_search(const orbx_tri_problem* device_problems, int n, hipStream_t st) {
+  hipLaunchKernelGGL(k_search_for_triangulation, dim3(n), dim3(TBS), 0, st, device_problems);
+  return hipGetLastError();
+}
+
 }  // namespace tri
 }  // namespace orbx
 

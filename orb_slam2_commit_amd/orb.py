@@ -1633,3 +1633,167 @@ class KeyFrameDatabase:
                                                           ptr(conn), len(conn), float(minScore), ptr(cand),
                                                           int(cand.numel()), ptr(n_cand), _stream_ptr(stream, True)),
               "orbx_kfdb_loop_candidates_device")
+
+
+def new_points_problem(prob):
+    """orbx_new_points_problem from a dict(current, neighbours, monocular, scale_factor); every keyframe
+    is a dict(keys_un, desc, u_right, has_mp, node_id, node_off, feat, keys_xy, depth, mp_pos, Tcw, fx, fy,
+    cx, cy, mb, mbf, scale_factors, level_sigma2) of host numpy arrays (synth.new_points_problem's
+    layout) or device tensors.  Returns (problem, keep-alive)."""
+    keep = []
+
+    def arr(x, dt):
+        if x is None or not isinstance(x, np.ndarray):
+            return x
+        a = np.ascontiguousarray(x, dt)
+        keep.append(a)
+        return a
+
+    def kf(d, k):
+        t = k.kf
+        t.n = len(d["desc"])
+        t.keys_un, t.desc = ptr(arr(d["keys_un"], KEYPOINT_DTYPE)), ptr(arr(d["desc"], np.uint8))
+        t.u_right, t.has_mp = ptr(arr(d.get("u_right"), np.float32)), ptr(arr(d.get("has_mp"), np.uint8))
+        t.n_nodes = len(d["node_id"])
+        t.node_id, t.node_off = ptr(arr(d["node_id"], np.uint32)), ptr(arr(d["node_off"], np.int32))
+        t.feat = ptr(arr(d["feat"], np.int32))
+        k.keys_xy, k.depth = ptr(arr(d.get("keys_xy"), np.float32)), ptr(arr(d.get("depth"), np.float32))
+        k.mp_pos = ptr(arr(d.get("mp_pos"), np.float32))
+        k.Tcw[:] = _f32(d["Tcw"]).reshape(16).tolist()
+        for f in ("fx", "fy", "cx", "cy", "mb", "mbf"):
+            setattr(k, f, float(d[f]))
+        nl = len(d["scale_factors"])
+        k.n_levels = nl
+        sf, sg = np.zeros(16, np.float32), np.zeros(16, np.float32)
+        sf[:nl], sg[:nl] = d["scale_factors"], d["level_sigma2"]
+        k.scale_factors[:] = sf.tolist()
+        k.level_sigma2[:] = sg.tolist()
+
+    p = _lib.NewPointsProblem()
+    kf(prob["current"], p.current)
+    nn = len(prob["neighbours"])
+    nbs = (_lib.NewPointsKF * max(1, nn))()
+    for i, d in enumerate(prob["neighbours"]):
+        kf(d, nbs[i])
+    keep.append(nbs)
+    p.n_neighbours, p.neighbours = nn, C.cast(nbs, C.POINTER(_lib.NewPointsKF))
+    p.monocular, p.scale_factor = int(bool(prob["monocular"])), float(prob["scale_factor"])
+    return p, keep
+
+
+NEW_POINTS_PROBES = {"exit": (0, np.uint8, ()), "cos": (1, np.float32, (3,)), "F12": (2, np.float32, None),
+                     "match12": (3, np.int32, ())}
+
+
+class LocalMapping:
+    """LocalMapping(pMap, bMonocular)'s CreateNewMapPoints (src/LocalMapping.cc:281-558) on an explicit
+    problem: the current keyframe and its GetBestCovisibilityKeyFrames(nn) neighbours, gathered as the
+    reference reads them.  One call: one copy in, the chain of neighbours on the device, one copy back.
+    The caller then makes the MapPoints in the returned order (:539-553)."""
+
+    def __init__(self, monocular, device=0):
+        self.mbMonocular = bool(monocular)
+        self.device = device
+        self._h = C.c_void_p()
+        check(_lib.lib().orbx_new_points_create(device, C.byref(self._h)), "orbx_new_points_create")
+        f = C.POINTER(C.c_int)()
+        check(_lib.lib().orbx_new_points_stop_flag(self._h, C.byref(f)), "orbx_new_points_stop_flag")
+        self._flag = f
+
+    def close(self):
+        if self._h:
+            _lib.lib().orbx_new_points_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def InsertKeyFrame(self, raised=True):
+        """What CheckNewKeyFrames() (:320) reads: a queued keyframe raises the handle's flag."""
+        self._flag[0] = 1 if raised else 0
+
+    def CheckNewKeyFrames(self):
+        return self._flag[0] != 0
+
+    def debug_options(self, raise_after_neighbour=-1, probes=False):
+        o = _lib.NewPointsDebugOptions(int(raise_after_neighbour), int(bool(probes)))
+        check(_lib.lib().orbx_debug_new_points_options(self._h, C.byref(o)), "orbx_debug_new_points_options")
+
+    @staticmethod
+    def _outputs(n1, nn):
+        return dict(n_new=np.zeros(1, np.int32), neighbours_done=np.zeros(1, np.int32),
+                    point_idx=np.zeros((max(1, n1), 3), np.int32), point_pos=np.zeros((max(1, n1), 3), np.float32),
+                    point_normal=np.zeros((max(1, n1), 3), np.float32),
+                    point_dist=np.zeros((max(1, n1), 2), np.float32), nb_skip=np.zeros(max(1, nn), np.int32),
+                    nb_nmatches=np.zeros(max(1, nn), np.int32), nb_baseline=np.zeros(max(1, nn), np.float32),
+                    nb_median_depth=np.zeros(max(1, nn), np.float32), has_mp1=np.zeros(max(1, n1), np.uint8))
+
+    @staticmethod
+    def _result(out, n1, nn):
+        n = int(out["n_new"][0])
+        return dict(n_new=n, neighbours_done=int(out["neighbours_done"][0]), points=out["point_idx"][:n].copy(),
+                    pos=out["point_pos"][:n].copy(), normal=out["point_normal"][:n].copy(),
+                    dist=out["point_dist"][:n].copy(), nb_skip=out["nb_skip"][:nn].copy(),
+                    nb_nmatches=out["nb_nmatches"][:nn].copy(), nb_baseline=out["nb_baseline"][:nn].copy(),
+                    nb_median=out["nb_median_depth"][:nn].copy(), has_mp1=out["has_mp1"][:n1].copy())
+
+    def CreateNewMapPoints(self, problem, stop=False, use_bool=False):
+        """problem: synth.new_points_problem's dict.  stop: raise the flag before the call (the first
+        neighbour still runs, :320).  use_bool: go through the bool* entry point.  Returns dict(n_new,
+        neighbours_done, points [n, 3] (neighbour, idx1, idx2), pos, normal, dist [n, 2] (min, max),
+        nb_skip, nb_nmatches, nb_baseline, nb_median, has_mp1)."""
+        prob = dict(problem, monocular=self.mbMonocular)
+        p, keep = new_points_problem(prob)
+        n1, nn = p.current.kf.n, p.n_neighbours
+        out = self._outputs(n1, nn)
+        r = _lib.NewPointsResult()
+        for k in out:
+            setattr(r, k, ptr(out[k]))
+        L = _lib.lib()
+        if use_bool:
+            b = C.c_bool(bool(stop))
+            check(L.orbx_create_new_map_points_bool(self._h, C.byref(p), C.byref(r), C.addressof(b)),
+                  "orbx_create_new_map_points_bool")
+        else:
+            old = self._flag[0]
+            if stop:
+                self._flag[0] = 1
+            try:
+                check(L.orbx_create_new_map_points(self._h, C.byref(p), C.byref(r)), "orbx_create_new_map_points")
+            finally:
+                self._flag[0] = old
+        return self._result(out, n1, nn)
+
+    def probes(self, n1, nn):
+        """The probes of the last host call (debug_options(probes=True)): exit [nn, n1], cos [nn, n1, 3],
+        F12 [nn, 3, 3], match12 [nn, n1]."""
+        out = {}
+        for k, (what, dt, _) in NEW_POINTS_PROBES.items():
+            shape = (nn, 3, 3) if k == "F12" else ((nn, n1, 3) if k == "cos" else (nn, n1))
+            a = np.zeros(shape, dt)
+            got = _lib.lib().orbx_debug_new_points_probe(self._h, what, ptr(a) if a.size else None, a.nbytes)
+            if got != a.nbytes:
+                raise _lib.OrbxError(int(got) if got < 0 else _lib.ORBX_OK, "orbx_debug_new_points_probe")
+            out[k] = a
+        return out
+
+
+def new_points_host(problem, neighbour, match12=None):
+    """orbx_debug_new_points_host: neighbour `neighbour`'s gate and, with a match12, its pairs, by the
+    kernels' routines compiled for the host (no device)."""
+    p, keep = new_points_problem(problem)
+    n1 = p.current.kf.n
+    skip, base, med = np.zeros(1, np.int32), np.zeros(1, np.float32), np.zeros(1, np.float32)
+    F12 = np.zeros((3, 3), np.float32)
+    ex, cos = np.zeros(max(1, n1), np.uint8), np.zeros((max(1, n1), 3), np.float32)
+    pos, nrm = np.zeros((max(1, n1), 3), np.float32), np.zeros((max(1, n1), 3), np.float32)
+    dist = np.zeros((max(1, n1), 2), np.float32)
+    m = None if match12 is None else np.ascontiguousarray(match12, np.int32)
+    check(_lib.lib().orbx_debug_new_points_host(C.byref(p), int(neighbour), ptr(m), ptr(skip), ptr(base), ptr(med),
+                                                ptr(F12), ptr(ex), ptr(cos), ptr(pos), ptr(nrm), ptr(dist)),
+          "orbx_debug_new_points_host")
+    return dict(skip=int(skip[0]), baseline=base[0], median=med[0], F12=F12, exit=ex[:n1], cos=cos[:n1], pos=pos[:n1],
+                normal=nrm[:n1], dist=dist[:n1])

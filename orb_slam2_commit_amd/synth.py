@@ -563,3 +563,74 @@ def triangulation_problem(seed, n1=1500, n2=1500, n_true=700, n_nodes=100, noise
                 C1w=(-R1.T @ t1).astype(np.float32), T2w=T2.astype(np.float32), fx=np.float32(K["fx"]),
                 fy=np.float32(K["fy"]), cx=np.float32(K["cx"]), cy=np.float32(K["cy"]), scale_factors2=sf,
                 level_sigma2_2=(sf * sf).astype(np.float32), true_pairs=(i1, i2))
+
+
+def new_points_problem(seed, n_neighbours=3, n=2000, n_scene=1200, p_seen=0.6, n_nodes=100, monocular=False,
+                       noise_bits=20, p_mp=0.35, p_stereo=0.6, step=(0.8, 0.0, 0.3), pixel_noise=0.7,
+                       width=1241, height=376):
+    """LocalMapping::CreateNewMapPoints' inputs (src/LocalMapping.cc:281-558) on triangulation_problem's
+    two-view generator: one current keyframe of n features and n_neighbours neighbours that share its
+    scene.  n_scene features of the current keyframe see a true 3D point; each neighbour (a step of
+    (j+1) * step away, slightly rotated) sees a fraction p_seen of them (same FeatureVector node,
+    descriptor with noise bits flipped, pixel noise), the rest of its features are random.  Stereo
+    features carry their depth z (the true one for a scene feature, a random one otherwise; mvuRight =
+    u - mbf / z); every feature's mp_pos is its unprojection at z, read where has_mp is set
+    (ComputeSceneMedianDepth).  mvKeys
+    differ from mvKeysUn by a smooth radial shift.  Layout: orb.new_points_problem's dict."""
+    rng = np.random.default_rng(seed)
+    K = KITTI_K
+    mbf, mb = K["bf"], K["bf"] / K["fx"]
+    sf = scale_factors()
+    ids = np.sort(rng.choice(10 ** 6, n_nodes, replace=False)).astype(np.uint32)
+    from ._lib import KEYPOINT_DTYPE
+
+    def keyframe(T, x, y, octave, desc, node, z):
+        m = len(x)
+        k = np.zeros(m, KEYPOINT_DTYPE)
+        k["x"], k["y"], k["octave"] = x, y, octave
+        k["angle"] = rng.uniform(0, 360, m)
+        k["size"], k["class_id"] = 31, -1
+        stereo = (rng.random(m) < p_stereo) & (not monocular)
+        depth = np.where(stereo, z, -1.0).astype(np.float32)
+        ur = np.where(stereo, k["x"] - mbf / z, -1.0).astype(np.float32)
+        has_mp = (rng.random(m) < p_mp).astype(np.uint8)
+        Xc = np.stack([(k["x"] - K["cx"]) * z / K["fx"], (k["y"] - K["cy"]) * z / K["fy"], z], 1).astype(np.float64)
+        Xw = (Xc - T[:3, 3]) @ T[:3, :3]
+        r2 = ((k["x"] - K["cx"]) ** 2 + (k["y"] - K["cy"]) ** 2) / (K["fx"] ** 2)
+        xy = np.stack([k["x"] + (k["x"] - K["cx"]) * 0.01 * r2, k["y"] + (k["y"] - K["cy"]) * 0.01 * r2], 1)
+        order = np.argsort(node, kind="stable")
+        counts = np.bincount(node, minlength=n_nodes)
+        present = counts > 0
+        return dict(keys_un=k, desc=desc, u_right=ur, has_mp=has_mp, node_id=ids[present],
+                    node_off=np.concatenate([[0], np.cumsum(counts[present])]).astype(np.int32),
+                    feat=order.astype(np.int32), keys_xy=xy.astype(np.float32), depth=depth,
+                    mp_pos=Xw.astype(np.float32), Tcw=T.astype(np.float32), fx=np.float32(K["fx"]),
+                    fy=np.float32(K["fy"]), cx=np.float32(K["cx"]), cy=np.float32(K["cy"]), mb=np.float32(mb),
+                    mbf=np.float32(mbf), scale_factors=sf, level_sigma2=(sf * sf).astype(np.float32))
+
+    def random_feats(m):
+        return (rng.uniform(0, width - 1, m), rng.uniform(0, height - 1, m),
+                rng.choice(8, size=m, p=_LEVEL_SHARE / _LEVEL_SHARE.sum()),
+                rng.integers(0, 256, (m, 32), dtype=np.uint8), rng.integers(0, n_nodes, m), rng.uniform(3, 40, m))
+
+    T1 = _pose(rng, 0.02, 0.2).astype(np.float64)
+    x1, y1, o1, d1, node1, z1 = random_feats(n)
+    cur = keyframe(T1, x1, y1, o1, d1, node1, z1)
+    scene = rng.choice(n, min(n_scene, n), replace=False)
+    neighbours = []
+    for j in range(n_neighbours):
+        T2 = T1.copy()
+        T2[:3, :3] = _rot_small(rng, 0.03) @ T1[:3, :3]
+        T2[:3, 3] = T1[:3, 3] - T2[:3, :3] @ (np.array(step, np.float64) * (j + 1))
+        x2, y2, o2, d2, node2, z2 = random_feats(n)
+        seen = scene[rng.random(len(scene)) < p_seen]
+        i2 = rng.choice(n, len(seen), replace=False)
+        Xc2 = cur["mp_pos"][seen].astype(np.float64) @ T2[:3, :3].T + T2[:3, 3]
+        ok = Xc2[:, 2] > 1.0
+        seen, i2, Xc2 = seen[ok], i2[ok], Xc2[ok]
+        x2[i2] = K["fx"] * Xc2[:, 0] / Xc2[:, 2] + K["cx"] + rng.normal(0, pixel_noise, len(seen))
+        y2[i2] = K["fy"] * Xc2[:, 1] / Xc2[:, 2] + K["cy"] + rng.normal(0, pixel_noise, len(seen))
+        o2[i2], z2[i2], node2[i2] = o1[seen], Xc2[:, 2], node1[seen]
+        d2[i2] = _flip_bits(rng, d1[seen], rng.integers(0, noise_bits + 1, len(seen)))
+        neighbours.append(keyframe(T2, x2, y2, o2, d2, node2, z2))
+    return dict(current=cur, neighbours=neighbours, monocular=bool(monocular), scale_factor=np.float32(1.2))

@@ -269,6 +269,10 @@ class KeyFrame {
 
 class Map {
  public:
+  void AddMapPoint(MapPoint* pMP) {    // src/Map.cc:48-52
+    std::unique_lock<std::mutex> lock(mMutexMap);
+    mspMapPoints.insert(pMP);
+  }
   void EraseMapPoint(MapPoint* pMP) {  // src/Map.cc EraseMapPoint
     std::unique_lock<std::mutex> lock(mMutexMap);
     mspMapPoints.erase(pMP);

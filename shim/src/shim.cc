@@ -33,6 +33,7 @@
 #include "Optimizer.h"
 #include "PnPsolver.h"
 #include "Initializer.h"
+#include "LocalMapping.h"
 #include "Sim3Solver.h"
 #include "orbx.h"
 #include "orbx_shim.h"
@@ -1008,6 +1009,123 @@ int ORBmatcher::SearchForTriangulation(KeyFrame* pKF1, KeyFrame* pKF2, cv::Mat F
   for (int i = 0; i < pKF1->N; i++)
     if (m12[i] >= 0) vMatchedPairs.push_back(std::make_pair((size_t)i, (size_t)m12[i]));
   return nm;
+}
+
+// ------------------------------------------------------------------ LocalMapping::CreateNewMapPoints
+LocalMapping::LocalMapping(Map* pMap, const float bMonocular) : mpMap(pMap), mbMonocular(bMonocular != 0.f) {}
+
+LocalMapping::~LocalMapping() {
+  if (mpGpu) orbx_new_points_destroy(mpGpu);
+}
+
+void LocalMapping::InsertKeyFrame(KeyFrame* pKF) {
+  std::unique_lock<std::mutex> lock(mMutexNewKFs);
+  mlNewKeyFrames.push_back(pKF);
+  mbAbortBA = true;
+  if (mpFlag) *mpFlag = 1;
+}
+
+bool LocalMapping::CheckNewKeyFrames() {
+  std::unique_lock<std::mutex> lock(mMutexNewKFs);
+  return !mlNewKeyFrames.empty();
+}
+
+void LocalMapping::CreateNewMapPoints() {
+  if (!mpGpu) {
+    check(orbx_new_points_create(gOrbxDevice, &mpGpu), "orbx_new_points_create");
+    check(orbx_new_points_stop_flag(mpGpu, &mpFlag), "orbx_new_points_stop_flag");
+  }
+  {
+    std::unique_lock<std::mutex> lock(mMutexNewKFs);
+    *mpFlag = mlNewKeyFrames.empty() ? 0 : 1;
+  }
+  const int nn = mbMonocular ? 20 : 10;
+  const std::vector<KeyFrame*> vpNeighKFs = mpCurrentKeyFrame->GetBestCovisibilityKeyFrames(nn);
+  struct Side {  // one keyframe's arrays, alive for the call
+    std::vector<uint8_t> has_mp;
+    std::vector<uint32_t> ids;
+    std::vector<int32_t> off, feat;
+    std::vector<float> xy, pos;
+    cv::Mat desc;
+    orbx_new_points_kf kf(KeyFrame* K, bool positions) {
+      const int n = K->N;
+      has_mp.assign(n > 0 ? n : 1, 0);
+      pos.assign(3 * (size_t)(n > 0 ? n : 1), 0.f);
+      xy.assign(2 * (size_t)(n > 0 ? n : 1), 0.f);
+      for (int i = 0; i < n; i++) {
+        MapPoint* pMP = K->GetMapPoint(i);
+        has_mp[i] = pMP != nullptr;
+        if (pMP && positions) {
+          const cv::Mat x = pMP->GetWorldPos();
+          for (int k = 0; k < 3; k++) pos[3 * i + k] = x.at<float>(k, 0);
+        }
+        const cv::KeyPoint& kp = (int)K->mvKeys.size() == n ? K->mvKeys[i] : K->mvKeysUn[i];
+        xy[2 * i] = kp.pt.x;
+        xy[2 * i + 1] = kp.pt.y;
+      }
+      off.push_back(0);
+      for (const auto& node : K->mFeatVec) {
+        ids.push_back(node.first);
+        for (unsigned int f : node.second) feat.push_back((int32_t)f);
+        off.push_back((int32_t)feat.size());
+      }
+      desc = continuous(K->mDescriptors);
+      orbx_new_points_kf o;
+      std::memset(&o, 0, sizeof(o));
+      o.kf = orbx_tri_kf{n, reinterpret_cast<const orbx_keypoint*>(K->mvKeysUn.data()), n > 0 ? desc.data : nullptr,
+                         (int)K->mvuRight.size() == n && n > 0 ? K->mvuRight.data() : nullptr, has_mp.data(),
+                         (int)ids.size(), ids.data(), off.data(), feat.data()};
+      o.keys_xy = xy.data();
+      o.depth = (int)K->mvDepth.size() == n && n > 0 ? K->mvDepth.data() : nullptr;
+      if (o.kf.u_right && !o.depth) throw std::invalid_argument("CreateNewMapPoints: mvuRight without mvDepth");
+      o.mp_pos = pos.data();
+      copy_mat44(K->GetPose(), o.Tcw);
+      o.fx = K->fx, o.fy = K->fy, o.cx = K->cx, o.cy = K->cy, o.mb = K->mb, o.mbf = K->mbf;
+      const int nl = K->mnScaleLevels;
+      if (nl < 1 || nl > 16 || (int)K->mvScaleFactors.size() < nl || (int)K->mvLevelSigma2.size() < nl)
+        throw std::invalid_argument("CreateNewMapPoints: scale tables");
+      o.n_levels = nl;
+      for (int l = 0; l < nl; l++) {
+        o.scale_factors[l] = K->mvScaleFactors[l];
+        o.level_sigma2[l] = K->mvLevelSigma2[l];
+      }
+      return o;
+    }
+  };
+  std::vector<Side> sides(vpNeighKFs.size() + 1);
+  std::vector<orbx_new_points_kf> nb(vpNeighKFs.size() > 0 ? vpNeighKFs.size() : 1);
+  orbx_new_points_problem p;
+  std::memset(&p, 0, sizeof(p));
+  p.current = sides[0].kf(mpCurrentKeyFrame, false);
+  for (size_t i = 0; i < vpNeighKFs.size(); i++) nb[i] = sides[i + 1].kf(vpNeighKFs[i], mbMonocular);
+  p.n_neighbours = (int)vpNeighKFs.size();
+  p.neighbours = nb.data();
+  p.monocular = mbMonocular;
+  p.scale_factor = mpCurrentKeyFrame->mfScaleFactor;
+  const size_t n1 = (size_t)(mpCurrentKeyFrame->N > 0 ? mpCurrentKeyFrame->N : 1), nnb = nb.size();
+  int32_t n_new = 0, done = 0;
+  std::vector<int32_t> idx(3 * n1), skip(nnb), nm(nnb);
+  std::vector<float> pos(3 * n1), normal(3 * n1), dist(2 * n1), base(nnb), med(nnb);
+  std::vector<uint8_t> has1(n1);
+  const orbx_new_points_result r{&n_new,      &done,      idx.data(),  pos.data(), normal.data(), dist.data(),
+                                 skip.data(), nm.data(), base.data(), med.data(), has1.data()};
+  check(orbx_create_new_map_points(mpGpu, &p, &r), "orbx_create_new_map_points");
+  mnNeighboursDone = done;
+  for (int k = 0; k < n_new; k++) {  // :539-553, in the reference's order
+    KeyFrame* pKF2 = vpNeighKFs[idx[3 * k]];
+    const size_t idx1 = (size_t)idx[3 * k + 1], idx2 = (size_t)idx[3 * k + 2];
+    cv::Mat x3D(3, 1, CV_32F);
+    for (int c = 0; c < 3; c++) x3D.at<float>(c, 0) = pos[3 * k + c];
+    MapPoint* pMP = new MapPoint(x3D, mpCurrentKeyFrame, mpMap);
+    pMP->AddObservation(mpCurrentKeyFrame, idx1);
+    pMP->AddObservation(pKF2, idx2);
+    mpCurrentKeyFrame->AddMapPoint(pMP, idx1);
+    pKF2->AddMapPoint(pMP, idx2);
+    pMP->ComputeDistinctiveDescriptors();
+    pMP->UpdateNormalAndDepth();
+    if (mpMap) mpMap->AddMapPoint(pMP);
+    mlpRecentAddedMapPoints.push_back(pMP);
+  }
 }
 
 // ------------------------------------------------------------------ MapPoint / ORBVocabulary

@@ -1,6 +1,5 @@
 // bow.hip -- ORBmatcher::SearchByBoW (src/ORBmatcher.cc:175-325 KF-Frame,
-// :589-736 KF-KF) and ComputeThreeMaxima (:1797-1839), batched: one block per
-// problem.
+// :589-736 KF-KF), batched: one block per problem; ComputeThreeMaxima (:1797-1839) is orbx_match.h's.
 //
 // Every feature belongs to exactly one FeatureVector node, so the "already
 // matched" state is node-local: nodes run in parallel (one wave each), the
@@ -14,20 +13,12 @@
 #include "orbx_device.h"
 #include "orbx_internal.h"
 #include "orbx_bow.h"
+#include "orbx_match.h"
 
 namespace orbx {
 
 constexpr int BBS = 256;
 constexpr int kOwn = 4;  // second-side features per lane held in registers (256 per node)
-
-__device__ __forceinline__ int rot_bin(float a, float b) {
-  const float factor = 1.0f / 30;
-  float rot = a - b;
-  if (rot < 0.0) rot += 360.0f;
-  int bin = (int)__builtin_roundf(rot * factor);
-  if (bin == 30) bin = 0;
-  return bin;
-}
 
 __global__ __launch_bounds__(BBS) void k_search_by_bow(const BowProblem* __restrict__ probs) {
   __shared__ int32_t smatch[kMaxBowFeatures];
@@ -143,32 +134,8 @@ __global__ __launch_bounds__(BBS) void k_search_by_bow(const BowProblem* __restr
   }
   __syncthreads();
   if (tid == 0) {
-    int ind1 = -1, ind2 = -1, ind3 = -1;
-    if (P.check_ori) {
-      int max1 = 0, max2 = 0, max3 = 0;
-      for (int i = 0; i < 30; i++) {
-        const int s = hist[i];
-        if (s > max1) {
-          max3 = max2; max2 = max1; max1 = s;
-          ind3 = ind2; ind2 = ind1; ind1 = i;
-        } else if (s > max2) {
-          max3 = max2; max2 = s;
-          ind3 = ind2; ind2 = i;
-        } else if (s > max3) {
-          max3 = s;
-          ind3 = i;
-        }
-      }
-      if (max2 < 0.1f * (float)max1) {
-        ind2 = -1;
-        ind3 = -1;
-      } else if (max3 < 0.1f * (float)max1) {
-        ind3 = -1;
-      }
-    }
-    sel[0] = ind1;
-    sel[1] = ind2;
-    sel[2] = ind3;
+    sel[0] = sel[1] = sel[2] = -1;
+    if (P.check_ori) three_maxima(hist, sel);
     sel[3] = 0;
   }
   __syncthreads();

@@ -23,7 +23,8 @@
 //
 // Arithmetic: the OpenCV 3.2 calls restated operation by operation (parity), float and
 // double exactly where the library uses them, -ffp-contract=off; acos through acosf_det.  The Jacobi
-// SVD is orbx_cvsvd.h's, the template PnP instantiates at double.  Every
+// SVD is orbx_cvsvd.h's, the template PnP instantiates at double; gemm, inv, det, convertTo, norm and dot
+// on 3x3 / 3x1 Mats are orbx_cv.h's.  Every
 // routine is __host__ __device__: orbx_debug_initializer_host runs the same code on the host.
 // tests/initializer_literal.py is the same sequence in numpy, and both equal it bit for bit.
 //
@@ -41,6 +42,7 @@
 
 #include "../../include/orbx.h"
 #include "../../include/orbx_debug.h"
+#include "orbx_cv.h"
 #include "orbx_cvsvd.h"
 #include "orbx_device.h"
 #include "orbx_ransac.h"
@@ -88,65 +90,7 @@ struct InitRt {  // one motion hypothesis of CheckRT
 // in its rolled form (kSmall = false): the matrices are run-time indexed memory, LDS on the device.
 using cvsvd::jacobi_svd;
 
-// det3 (lapack.cpp) of a 3x3 CV_32F, in double
-INIT_HD double init_det3(const float* m) {
-  return m[0] * ((double)m[4] * m[8] - (double)m[5] * m[7]) - m[1] * ((double)m[3] * m[8] - (double)m[5] * m[6]) +
-         m[2] * ((double)m[3] * m[7] - (double)m[4] * m[6]);
-}
-
-// Mat::inv() (DECOMP_LU) of a 3x3 CV_32F: the n == 3 special case; det == 0 gives zeros
-INIT_HD void init_inv3(const float* S, float* D) {
-  double d = init_det3(S);
-  if (d != 0.) {
-    d = 1. / d;
-    D[0] = (float)(((double)S[4] * S[8] - (double)S[5] * S[7]) * d);
-    D[1] = (float)(((double)S[2] * S[7] - (double)S[1] * S[8]) * d);
-    D[2] = (float)(((double)S[1] * S[5] - (double)S[2] * S[4]) * d);
-    D[3] = (float)(((double)S[5] * S[6] - (double)S[3] * S[8]) * d);
-    D[4] = (float)(((double)S[0] * S[8] - (double)S[2] * S[6]) * d);
-    D[5] = (float)(((double)S[2] * S[3] - (double)S[0] * S[5]) * d);
-    D[6] = (float)(((double)S[3] * S[7] - (double)S[4] * S[6]) * d);
-    D[7] = (float)(((double)S[1] * S[6] - (double)S[0] * S[7]) * d);
-    D[8] = (float)(((double)S[0] * S[4] - (double)S[1] * S[3]) * d);
-  } else {
-#pragma unroll
-    for (int k = 0; k < 9; k++) D[k] = 0.f;
-  }
-}
-
-// cv::gemm's small-matrix path, 3x3 by 3x3: a float dot product left to right, then
-// (float)(t0*alpha + 0.0) in double
-INIT_HD void init_gemm33(const float* A, const float* B, double alpha, float* D) {
-#pragma unroll
-  for (int i = 0; i < 3; i++)
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-      const float t0 = A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j] + A[3 * i + 2] * B[6 + j];
-      D[3 * i + j] = (float)((double)t0 * alpha + 0.0);
-    }
-}
-
-// ... 3x3 by 3x1
-INIT_HD void init_gemm31(const float* A, const float* x, float* d) {
-#pragma unroll
-  for (int i = 0; i < 3; i++) {
-    const float t0 = A[3 * i] * x[0] + A[3 * i + 1] * x[1] + A[3 * i + 2] * x[2];
-    d[i] = (float)((double)t0 * 1.0 + 0.0);
-  }
-}
-
-// convertTo(alpha): x*(float)alpha + 0.0f, a copy when |alpha - 1| < DBL_EPSILON
-INIT_HD float init_scale(float x, double alpha) {
-  return __builtin_fabs(alpha - 1) < DBL_EPSILON ? x : x * (float)alpha + 0.0f;
-}
-
-// cv::norm(NORM_L2) of 3 floats
-INIT_HD double init_norm3(const float* v) {
-  double s = 0;
-#pragma unroll
-  for (int k = 0; k < 3; k++) s += (double)v[k] * (double)v[k];
-  return __builtin_sqrt(s);
-}
+// gemm, inv, det, convertTo, norm and dot on 3x3 / 3x1 Mats are orbx_cv.h's (row stride 3 throughout).
 
 // cv::SVD::compute(A, w, u, vt, FULL_UV) of a 3x3 CV_32F.  ws: 18 floats + W: 3 doubles of
 // run-time indexed memory (LDS on the device); u, w, vt: the results
@@ -193,9 +137,9 @@ INIT_HD void init_solve(const InitJob& J, int it, int model, float* ws, double* 
     float Hn[9], P[9], H21[9], H12[9];
 #pragma unroll
     for (int k = 0; k < 9; k++) Hn[k] = Vt[72 + k];
-    init_gemm33(J.T2inv, Hn, 1.0, P);
-    init_gemm33(P, J.T1, 1.0, H21);
-    init_inv3(H21, H12);
+    cvmat::gemm33<3>(J.T2inv, Hn, 1.0, P);
+    cvmat::gemm33<3>(P, J.T1, 1.0, H21);
+    cvmat::inv3<3>(H21, H12);
 #pragma unroll
     for (int k = 0; k < 9; k++) M[k] = H21[k], M[9 + k] = H12[k];
   } else {
@@ -218,10 +162,10 @@ INIT_HD void init_solve(const InitJob& J, int it, int model, float* ws, double* 
     w[0] = tmp[18], w[1] = tmp[19], w[2] = 0.f;
     const float D[9] = {w[0], 0.f, 0.f, 0.f, w[1], 0.f, 0.f, 0.f, w[2]};
     float P[9], Fn[9], F21[9];
-    init_gemm33(u, D, 1.0, P);
-    init_gemm33(P, vt, 1.0, Fn);
-    init_gemm33(J.T2t, Fn, 1.0, P);
-    init_gemm33(P, J.T1, 1.0, F21);
+    cvmat::gemm33<3>(u, D, 1.0, P);
+    cvmat::gemm33<3>(P, vt, 1.0, Fn);
+    cvmat::gemm33<3>(J.T2t, Fn, 1.0, P);
+    cvmat::gemm33<3>(P, J.T1, 1.0, F21);
 #pragma unroll
     for (int k = 0; k < 9; k++) M[k] = F21[k], M[9 + k] = 0.f;
   }
@@ -347,40 +291,31 @@ INIT_HD void init_motion(const InitJob& J, InitRec* rec, float* ws, double* W, i
         for (int k = 0; k < 3; k++) s += (double)K[3 * k + i] * (double)F[3 * k + j];
         P[3 * i + j] = (float)(s * 1.0);
       }
-    init_gemm33(P, K, 1.0, E);
+    cvmat::gemm33<3>(P, K, 1.0, E);
     // DecomposeE
     for (int k = 0; k < 9; k++) ws[kInitSvd3Ws + 30 + k] = E[k];
     init_svd3(ws + kInitSvd3Ws + 30, s3, W, uu, uu + 9, uu + 12);
 #pragma unroll
     for (int k = 0; k < 9; k++) u[k] = uu[k], vt[k] = uu[12 + k];
     float t[3] = {u[2], u[5], u[8]};
-    const double nt = init_norm3(t);
+    const double nt = cvmat::norm3(t);
 #pragma unroll
-    for (int k = 0; k < 3; k++) t[k] = init_scale(t[k], 1.0 / nt);
+    for (int k = 0; k < 3; k++) t[k] = cvmat::scale(t[k], 1.0 / nt);
     const float Wm[9] = {0.f, -1.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f, 1.f};
     float R1[9], R2[9];
-    init_gemm33(u, Wm, 1.0, P);
-    init_gemm33(P, vt, 1.0, R1);
-    if (init_det3(R1) < 0)
+    cvmat::gemm33<3>(u, Wm, 1.0, P);
+    cvmat::gemm33<3>(P, vt, 1.0, R1);
+    if (cvmat::det3<3>(R1) < 0)
 #pragma unroll
-      for (int k = 0; k < 9; k++) R1[k] = init_scale(R1[k], -1.0);
-    // u*W.t(): GEMM_2_T, the products summed in double
+      for (int k = 0; k < 9; k++) R1[k] = cvmat::scale(R1[k], -1.0);
+    cvmat::gemm33_bt<3>(u, Wm, 1.0, P);  // u*W.t(): GEMM_2_T
+    cvmat::gemm33<3>(P, vt, 1.0, R2);
+    if (cvmat::det3<3>(R2) < 0)
 #pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-      for (int j = 0; j < 3; j++) {
-        double s = 0;
-#pragma unroll
-        for (int k = 0; k < 3; k++) s += (double)u[3 * i + k] * (double)Wm[3 * j + k];
-        P[3 * i + j] = (float)(s * 1.0);
-      }
-    init_gemm33(P, vt, 1.0, R2);
-    if (init_det3(R2) < 0)
-#pragma unroll
-      for (int k = 0; k < 9; k++) R2[k] = init_scale(R2[k], -1.0);
+      for (int k = 0; k < 9; k++) R2[k] = cvmat::scale(R2[k], -1.0);
     float t2[3];
 #pragma unroll
-    for (int k = 0; k < 3; k++) t2[k] = init_scale(t[k], -1.0);
+    for (int k = 0; k < 3; k++) t2[k] = cvmat::scale(t[k], -1.0);
 #pragma unroll
     for (int k = 0; k < 9; k++) {
       rec->R[0][k] = R1[k];
@@ -402,16 +337,16 @@ INIT_HD void init_motion(const InitJob& J, InitRec* rec, float* ws, double* W, i
   float H[9], invK[9], P[9], A[9];
 #pragma unroll
   for (int k = 0; k < 9; k++) H[k] = rec->H21[k];
-  init_inv3(K, invK);
-  init_gemm33(invK, H, 1.0, P);
-  init_gemm33(P, K, 1.0, A);
+  cvmat::inv3<3>(K, invK);
+  cvmat::gemm33<3>(invK, H, 1.0, P);
+  cvmat::gemm33<3>(P, K, 1.0, A);
   for (int k = 0; k < 9; k++) ws[kInitSvd3Ws + 30 + k] = A[k];
   init_svd3(ws + kInitSvd3Ws + 30, s3, W, uu, uu + 9, uu + 12);
 #pragma unroll
   for (int k = 0; k < 9; k++) u[k] = uu[k], vt[k] = uu[12 + k];
 #pragma unroll
   for (int k = 0; k < 3; k++) w[k] = uu[9 + k];
-  const float s = (float)(init_det3(u) * init_det3(vt));
+  const float s = (float)(cvmat::det3<3>(u) * cvmat::det3<3>(vt));
   const float d1 = w[0], d2 = w[1], d3 = w[2];
   if ((double)(d1 / d2) < 1.00001 || (double)(d2 / d3) < 1.00001) return;
   const float aux1 = __builtin_sqrtf((d1 * d1 - d2 * d2) / (d1 * d1 - d3 * d3));
@@ -432,21 +367,21 @@ INIT_HD void init_motion(const InitJob& J, InitRec* rec, float* ws, double* W, i
     if (i < 4) {
       Rp[0] = ct, Rp[2] = -st[j], Rp[6] = st[j], Rp[8] = ct;
       const double f = (double)(d1 - d3);
-      tp[0] = init_scale(x1[j], f), tp[1] = init_scale(0.f, f), tp[2] = init_scale(-x3[j], f);
+      tp[0] = cvmat::scale(x1[j], f), tp[1] = cvmat::scale(0.f, f), tp[2] = cvmat::scale(-x3[j], f);
     } else {
       Rp[0] = cp, Rp[2] = sp[j], Rp[4] = -1.f, Rp[6] = sp[j], Rp[8] = -cp;
       const double f = (double)(d1 + d3);
-      tp[0] = init_scale(x1[j], f), tp[1] = init_scale(0.f, f), tp[2] = init_scale(x3[j], f);
+      tp[0] = cvmat::scale(x1[j], f), tp[1] = cvmat::scale(0.f, f), tp[2] = cvmat::scale(x3[j], f);
     }
     float R[9], t[3];
-    init_gemm33(u, Rp, (double)s, P);
-    init_gemm33(P, vt, 1.0, R);
-    init_gemm31(u, tp, t);
-    const double nt = init_norm3(t);
+    cvmat::gemm33<3>(u, Rp, (double)s, P);
+    cvmat::gemm33<3>(P, vt, 1.0, R);
+    cvmat::gemm31<3>(u, tp, 1.0, t);
+    const double nt = cvmat::norm3(t);
 #pragma unroll
     for (int k = 0; k < 9; k++) rec->R[i][k] = R[k];
 #pragma unroll
-    for (int k = 0; k < 3; k++) rec->t[i][k] = init_scale(t[k], 1.0 / nt);
+    for (int k = 0; k < 3; k++) rec->t[i][k] = cvmat::scale(t[k], 1.0 / nt);
   }
   rec->n_hyp = 8;
 }
@@ -510,11 +445,7 @@ INIT_HD void init_rt_setup(const float* K, float th2, const float* R, const floa
       for (int k = 0; k < 3; k++) s += (double)K[3 * i + k] * (double)(j < 3 ? R[3 * k + j] : t[k]);
       C->P2[4 * i + j] = (float)(s * 1.0);
     }
-  for (int i = 0; i < 3; i++) {
-    double s = 0;
-    for (int k = 0; k < 3; k++) s += (double)R[3 * k + i] * (double)t[k];
-    C->O2[i] = (float)(s * -1.0);
-  }
+  cvmat::gemm31_at<3, true>(R, t, -1.0, C->O2);
   C->fx = K[0], C->fy = K[4], C->cx = K[2], C->cy = K[5];
   C->th2 = th2;
 }
@@ -534,28 +465,21 @@ INIT_HD int init_rt_point(const InitRt& C, float x1, float y1, float x2, float y
   }
   jacobi_svd<float, 4, 4, 0, true, false>(At, W, Vt);
   const double iw = 1.0 / (double)Vt[15];
-  X[0] = init_scale(Vt[12], iw);
-  X[1] = init_scale(Vt[13], iw);
-  X[2] = init_scale(Vt[14], iw);
+  X[0] = cvmat::scale(Vt[12], iw);
+  X[1] = cvmat::scale(Vt[13], iw);
+  X[2] = cvmat::scale(Vt[14], iw);
   *cosp = 0.f;
   if (!__builtin_isfinite(X[0]) || !__builtin_isfinite(X[1]) || !__builtin_isfinite(X[2])) return 0;
   const float n1[3] = {X[0] - 0.f, X[1] - 0.f, X[2] - 0.f};
-  const float dist1 = (float)init_norm3(n1);
+  const float dist1 = (float)cvmat::norm3(n1);
   const float n2[3] = {X[0] - C.O2[0], X[1] - C.O2[1], X[2] - C.O2[2]};
-  const float dist2 = (float)init_norm3(n2);
-  double dot = 0;
-#pragma unroll
-  for (int k = 0; k < 3; k++) dot += (double)n1[k] * (double)n2[k];
-  const float cosParallax = (float)(dot / (double)(dist1 * dist2));
+  const float dist2 = (float)cvmat::norm3(n2);
+  const float cosParallax = (float)(cvmat::dot<3>(n1, n2) / (double)(dist1 * dist2));
   *cosp = cosParallax;
   const bool low = (double)cosParallax < 0.99998;
   if (X[2] <= 0 && low) return 0;
   float X2[3];
-#pragma unroll
-  for (int r = 0; r < 3; r++) {
-    const float t0 = C.R[3 * r] * X[0] + C.R[3 * r + 1] * X[1] + C.R[3 * r + 2] * X[2];
-    X2[r] = (float)((double)t0 * 1.0 + (double)C.t[r] * 1.0);
-  }
+  cvmat::gemm31_add<3>(C.R, X, 1.0, C.t, X2);
   if (X2[2] <= 0 && low) return 0;
   const float invZ1 = (float)(1.0 / (double)X[2]);
   const float im1x = C.fx * X[0] * invZ1 + C.cx, im1y = C.fy * X[1] * invZ1 + C.cy;
@@ -821,7 +745,7 @@ orbx_status init_prepare(const orbx_initializer* h, const float* keys2_xy, int n
   InitJob& J = c.J;
   std::memset(&J, 0, sizeof(J));
   std::memcpy(J.T1, h->T1, sizeof(J.T1));
-  orbx::init_inv3(T2, J.T2inv);
+  orbx::cvmat::inv3<3>(T2, J.T2inv);
   for (int r = 0; r < 3; r++)
     for (int k = 0; k < 3; k++) J.T2t[3 * r + k] = T2[3 * k + r];
   std::memcpy(J.K, h->K, sizeof(J.K));

@@ -29,7 +29,8 @@
 // launches, one readback.
 //
 // Arithmetic: OpenCV 3.2's calls restated operation by operation as tests/newpoints_literal.py lists
-// them, -ffp-contract=off.  cos / atan2 at :410-412 are the float overloads (DBoW2's
+// them (the small Mat arithmetic is orbx_cv.h's, the ordered compaction orbx_device.h's compact_chunk),
+// -ffp-contract=off.  cos / atan2 at :410-412 are the float overloads (DBoW2's
 // TemplatedVocabulary.h puts `using namespace std` in front of the translation unit, so
 // atan2(float, float) and cos(float) resolve to std's float forms): (float)atan2_det in double, the
 // doubling in float, (float) of sincos_d's cosine.  Every routine is __host__ __device__:
@@ -46,6 +47,7 @@
 
 #include "../../include/orbx.h"
 #include "../../include/orbx_debug.h"
+#include "orbx_cv.h"
 #include "orbx_cvsvd.h"
 #include "orbx_device.h"
 #include "orbx_scratch.h"
@@ -61,6 +63,7 @@ hipError_t launch_search(const orbx_tri_problem* device_problems, int n, hipStre
 namespace cnmp {
 
 using cvsvd::jacobi_svd;
+using namespace cvmat;  // OpenCV 3.2's gemm, inv, convertTo, norm and dot (orbx_cv.h), row stride 3 throughout
 typedef orbx_new_points_kf Kf;
 
 struct Pose {  // KeyFrame::SetPose
@@ -93,77 +96,6 @@ struct Job {
   float *pr_cos, *pr_f12;
 };
 
-// ------------------------------------------------------------------ OpenCV 3.2 pieces
-// cv::gemm's small-matrix path, 3x3 by 3x1: a float dot product left to right, then
-// (float)(t0*alpha + c*beta) in double (c absent: + 0.0)
-CN_HD void cn_gemm31(const float* A, const float* x, double alpha, const float* c, float* d) {
-#pragma unroll
-  for (int i = 0; i < 3; i++) {
-    const float t0 = A[3 * i] * x[0] + A[3 * i + 1] * x[1] + A[3 * i + 2] * x[2];
-    d[i] = (float)((double)t0 * alpha + (c ? (double)c[i] * 1.0 : 0.0));
-  }
-}
-// ... 3x3 by 3x3
-CN_HD void cn_gemm33(const float* A, const float* B, float* D) {
-#pragma unroll
-  for (int i = 0; i < 3; i++)
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-      const float t0 = A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j] + A[3 * i + 2] * B[6 + j];
-      D[3 * i + j] = (float)((double)t0 * 1.0 + 0.0);
-    }
-}
-// A * B.t() (a transpose flag leaves the small path): GEMMSingleMul<float,double>, the products summed
-// in double from 0 in order, (float)(sum*alpha)
-CN_HD void cn_gemm33_bt(const float* A, const float* B, double alpha, float* D) {
-#pragma unroll
-  for (int i = 0; i < 3; i++)
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-      double s = 0;
-#pragma unroll
-      for (int k = 0; k < 3; k++) s += (double)A[3 * i + k] * (double)B[3 * j + k];
-      D[3 * i + j] = (float)(s * alpha);
-    }
-}
-// Mat::inv() (DECOMP_LU) of a 3x3 CV_32F: the n == 3 special case; det == 0 gives zeros
-CN_HD void cn_inv3(const float* S, float* D) {
-  double d = S[0] * ((double)S[4] * S[8] - (double)S[5] * S[7]) - S[1] * ((double)S[3] * S[8] - (double)S[5] * S[6]) +
-             S[2] * ((double)S[3] * S[7] - (double)S[4] * S[6]);
-  if (d != 0.) {
-    d = 1. / d;
-    D[0] = (float)(((double)S[4] * S[8] - (double)S[5] * S[7]) * d);
-    D[1] = (float)(((double)S[2] * S[7] - (double)S[1] * S[8]) * d);
-    D[2] = (float)(((double)S[1] * S[5] - (double)S[2] * S[4]) * d);
-    D[3] = (float)(((double)S[5] * S[6] - (double)S[3] * S[8]) * d);
-    D[4] = (float)(((double)S[0] * S[8] - (double)S[2] * S[6]) * d);
-    D[5] = (float)(((double)S[2] * S[3] - (double)S[0] * S[5]) * d);
-    D[6] = (float)(((double)S[3] * S[7] - (double)S[4] * S[6]) * d);
-    D[7] = (float)(((double)S[1] * S[6] - (double)S[0] * S[7]) * d);
-    D[8] = (float)(((double)S[0] * S[4] - (double)S[1] * S[3]) * d);
-  } else {
-#pragma unroll
-    for (int k = 0; k < 9; k++) D[k] = 0.f;
-  }
-}
-// convertTo(alpha): x*(float)alpha + 0.0f, a copy when |alpha - 1| < DBL_EPSILON
-CN_HD float cn_scale(float x, double alpha) {
-  return __builtin_fabs(alpha - 1) < DBL_EPSILON ? x : x * (float)alpha + 0.0f;
-}
-// cv::norm(NORM_L2) of 3 floats; Mat::dot of 3 floats
-CN_HD double cn_norm3(const float* v) {
-  double s = 0;
-#pragma unroll
-  for (int k = 0; k < 3; k++) s += (double)v[k] * (double)v[k];
-  return __builtin_sqrt(s);
-}
-CN_HD double cn_dot3(const float* a, const float* b) {
-  double s = 0;
-#pragma unroll
-  for (int k = 0; k < 3; k++) s += (double)a[k] * (double)b[k];
-  return s;
-}
-
 // ------------------------------------------------------------------ the gate
 // KeyFrame::SetPose: Rwc = Rcw.t() (a Mat of its own), Ow = -Rwc*tcw = gemm(Rwc, tcw, alpha = -1)
 CN_HD void cn_pose(const Kf& K, Pose* P) {
@@ -176,15 +108,15 @@ CN_HD void cn_pose(const Kf& K, Pose* P) {
     }
     P->tcw[r] = K.Tcw[4 * r + 3];
   }
-  cn_gemm31(P->Rwc, P->tcw, -1.0, nullptr, P->Ow);
+  gemm31<3>(P->Rwc, P->tcw, -1.0, P->Ow);
   P->invfx = 1.0f / K.fx;
   P->invfy = 1.0f / K.fy;
 }
 // ComputeSceneMedianDepth's z = Rcw2.dot(x3Dw) + zcw
-CN_HD float cn_depth(const Pose& P, const float* x) { return (float)(cn_dot3(P.Rcw + 6, x) + (double)P.tcw[2]); }
+CN_HD float cn_depth(const Pose& P, const float* x) { return (float)(dot<3>(P.Rcw + 6, x) + (double)P.tcw[2]); }
 CN_HD float cn_baseline(const Pose& P1, const Pose& P2) {
   const float v[3] = {P2.Ow[0] - P1.Ow[0], P2.Ow[1] - P1.Ow[1], P2.Ow[2] - P1.Ow[2]};
-  return (float)cn_norm3(v);
+  return (float)norm3(v);
 }
 CN_HD int cn_gate_code(int monocular, float baseline, float mb2, int n_depths, float median) {
   if (!monocular) return baseline < mb2 ? ORBX_NP_NB_BASELINE : ORBX_NP_NB_RAN;
@@ -196,18 +128,18 @@ CN_HD int cn_gate_code(int monocular, float baseline, float mb2, int n_depths, f
 // folds -R1w*R2w.t()*t2w+t1w; K1.t().inv()*t12x*R12*K2.inv() left to right
 CN_HD void cn_f12(const Kf& K1, const Pose& P1, const Kf& K2, const Pose& P2, float* F) {
   float R12[9], M[9], t12[3];
-  cn_gemm33_bt(P1.Rcw, P2.Rcw, 1.0, R12);
-  cn_gemm33_bt(P1.Rcw, P2.Rcw, -1.0, M);
-  cn_gemm31(M, P2.tcw, 1.0, P1.tcw, t12);
+  gemm33_bt<3>(P1.Rcw, P2.Rcw, 1.0, R12);
+  gemm33_bt<3>(P1.Rcw, P2.Rcw, -1.0, M);
+  gemm31_add<3>(M, P2.tcw, 1.0, P1.tcw, t12);
   const float tx[9] = {0.f, -t12[2], t12[1], t12[2], 0.f, -t12[0], -t12[1], t12[0], 0.f};
   const float K1t[9] = {K1.fx, 0.f, 0.f, 0.f, K1.fy, 0.f, K1.cx, K1.cy, 1.f};
   const float K2m[9] = {K2.fx, 0.f, K2.cx, 0.f, K2.fy, K2.cy, 0.f, 0.f, 1.f};
   float A[9], B[9], C[9], K2i[9];
-  cn_inv3(K1t, A);
-  cn_gemm33(A, tx, B);
-  cn_gemm33(B, R12, C);
-  cn_inv3(K2m, K2i);
-  cn_gemm33(C, K2i, F);
+  inv3<3>(K1t, A);
+  gemm33<3>(A, tx, 1.0, B);
+  gemm33<3>(B, R12, 1.0, C);
+  inv3<3>(K2m, K2i);
+  gemm33<3>(C, K2i, 1.0, F);
 }
 // what SearchForTriangulation reads beside the two keyframes
 CN_HD void cn_fill_tri(const Kf& K2, const Pose& P1, const float* F, int ran, orbx_tri_problem* T) {
@@ -236,7 +168,7 @@ CN_HD void cn_unproject(const Kf& K, const Pose& P, int i, float z, float* X) {
   const float u = K.keys_xy ? K.keys_xy[2 * i] : K.kf.keys_un[i].x;
   const float v = K.keys_xy ? K.keys_xy[2 * i + 1] : K.kf.keys_un[i].y;
   const float xc[3] = {(u - K.cx) * z * P.invfx, (v - K.cy) * z * P.invfy, z};
-  cn_gemm31(P.Rwc, xc, 1.0, P.Ow, X);
+  gemm31_add<3>(P.Rwc, xc, 1.0, P.Ow, X);
 }
 // x*P.row(2) - P.row(r): addWeighted, (a*x + b*(-1.0f)) + 0.0f; a - b when x == 1
 CN_HD float cn_row(float x, float p2, float pr) { return x == 1.f ? p2 - pr : (p2 * x + pr * -1.0f) + 0.0f; }
@@ -254,9 +186,9 @@ CN_HD int cn_pair(const Kf& K1, const Pose& P1, const Kf& K2, const Pose& P2, fl
   const float xn1[3] = {(kp1.x - K1.cx) * P1.invfx, (kp1.y - K1.cy) * P1.invfy, 1.0f};
   const float xn2[3] = {(kp2.x - K2.cx) * P2.invfx, (kp2.y - K2.cy) * P2.invfy, 1.0f};
   float ray1[3], ray2[3];
-  cn_gemm31(P1.Rwc, xn1, 1.0, nullptr, ray1);
-  cn_gemm31(P2.Rwc, xn2, 1.0, nullptr, ray2);
-  const float cosParallaxRays = (float)(cn_dot3(ray1, ray2) / (cn_norm3(ray1) * cn_norm3(ray2)));
+  gemm31<3>(P1.Rwc, xn1, 1.0, ray1);
+  gemm31<3>(P2.Rwc, xn2, 1.0, ray2);
+  const float cosParallaxRays = (float)(dot<3>(ray1, ray2) / (norm3(ray1) * norm3(ray2)));
   float cosParallaxStereo = cosParallaxRays + 1;
   float cosParallaxStereo1 = cosParallaxStereo, cosParallaxStereo2 = cosParallaxStereo;
   const float depth1 = K1.depth ? K1.depth[idx1] : -1.f, depth2 = K2.depth ? K2.depth[idx2] : -1.f;
@@ -280,9 +212,9 @@ CN_HD int cn_pair(const Kf& K1, const Pose& P1, const Kf& K2, const Pose& P2, fl
     jacobi_svd<float, 4, 4, 0, true, false>(At, W, Vt);
     if (Vt[15] == 0) return ORBX_NP_W_ZERO;
     const double iw = 1.0 / (double)Vt[15];
-    X[0] = cn_scale(Vt[12], iw);
-    X[1] = cn_scale(Vt[13], iw);
-    X[2] = cn_scale(Vt[14], iw);
+    X[0] = scale(Vt[12], iw);
+    X[1] = scale(Vt[13], iw);
+    X[2] = scale(Vt[14], iw);
     how = ORBX_NP_TRIANGULATED;
   } else if (bStereo1 && cosParallaxStereo1 < cosParallaxStereo2) {
     if (!(depth1 > 0)) return ORBX_NP_DEPTH_GUARD;
@@ -296,14 +228,14 @@ CN_HD int cn_pair(const Kf& K1, const Pose& P1, const Kf& K2, const Pose& P2, fl
     return ORBX_NP_LOW_PARALLAX;
   }
 
-  const float z1 = (float)(cn_dot3(P1.Rcw + 6, X) + (double)P1.tcw[2]);
+  const float z1 = (float)(dot<3>(P1.Rcw + 6, X) + (double)P1.tcw[2]);
   if (z1 <= 0) return ORBX_NP_Z1;
-  const float z2 = (float)(cn_dot3(P2.Rcw + 6, X) + (double)P2.tcw[2]);
+  const float z2 = (float)(dot<3>(P2.Rcw + 6, X) + (double)P2.tcw[2]);
   if (z2 <= 0) return ORBX_NP_Z2;
 
   const float sigmaSquare1 = K1.level_sigma2[kp1.octave];
-  const float x1 = (float)(cn_dot3(P1.Rcw, X) + (double)P1.tcw[0]);
-  const float y1 = (float)(cn_dot3(P1.Rcw + 3, X) + (double)P1.tcw[1]);
+  const float x1 = (float)(dot<3>(P1.Rcw, X) + (double)P1.tcw[0]);
+  const float y1 = (float)(dot<3>(P1.Rcw + 3, X) + (double)P1.tcw[1]);
   const float invz1 = (float)(1.0 / (double)z1);
   if (!bStereo1) {
     const float u1 = K1.fx * x1 * invz1 + K1.cx, v1 = K1.fy * y1 * invz1 + K1.cy;
@@ -318,8 +250,8 @@ CN_HD int cn_pair(const Kf& K1, const Pose& P1, const Kf& K2, const Pose& P2, fl
       return ORBX_NP_REPROJ1_STEREO;
   }
   const float sigmaSquare2 = K2.level_sigma2[kp2.octave];
-  const float x2 = (float)(cn_dot3(P2.Rcw, X) + (double)P2.tcw[0]);
-  const float y2 = (float)(cn_dot3(P2.Rcw + 3, X) + (double)P2.tcw[1]);
+  const float x2 = (float)(dot<3>(P2.Rcw, X) + (double)P2.tcw[0]);
+  const float y2 = (float)(dot<3>(P2.Rcw + 3, X) + (double)P2.tcw[1]);
   const float invz2 = (float)(1.0 / (double)z2);
   if (!bStereo2) {
     const float u2 = K2.fx * x2 * invz2 + K2.cx, v2 = K2.fy * y2 * invz2 + K2.cy;
@@ -335,10 +267,10 @@ CN_HD int cn_pair(const Kf& K1, const Pose& P1, const Kf& K2, const Pose& P2, fl
   }
 
   const float normal1[3] = {X[0] - P1.Ow[0], X[1] - P1.Ow[1], X[2] - P1.Ow[2]};
-  const double n1d = cn_norm3(normal1);
+  const double n1d = norm3(normal1);
   const float dist1 = (float)n1d;
   const float normal2[3] = {X[0] - P2.Ow[0], X[1] - P2.Ow[1], X[2] - P2.Ow[2]};
-  const double n2d = cn_norm3(normal2);
+  const double n2d = norm3(normal2);
   const float dist2 = (float)n2d;
   if (dist1 == 0 || dist2 == 0) return ORBX_NP_DIST_ZERO;
   const float ratioDist = dist2 / dist1;
@@ -354,7 +286,7 @@ CN_HD int cn_pair(const Kf& K1, const Pose& P1, const Kf& K2, const Pose& P2, fl
   for (int k = 0; k < 3; k++) {
     const float s1 = (0.f * 1.0f + normal1[k] * b1) + 0.0f;
     const float s2 = (s1 * 1.0f + normal2[k] * b2) + 0.0f;
-    o->normal[k] = cn_scale(s2, 1.0 / 2);
+    o->normal[k] = scale(s2, 1.0 / 2);
     o->X[k] = X[k];
   }
   o->dmax = dist1 * K1.scale_factors[kp1.octave];
@@ -428,24 +360,6 @@ __global__ __launch_bounds__(kThreads) void k_cnmp_gate(const Job* jp) {
   }
 }
 
-// exclusive position of a set flag among the block's threads in thread order, and the block's count
-__device__ __forceinline__ int cn_block_scan(bool f, int* s_w, int* total) {
-  const unsigned long long m = __ballot(f);
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int pre = __popcll(m & ((1ull << lane) - 1ull));
-  if (lane == 0) s_w[wid] = __popcll(m);
-  __syncthreads();
-  int off = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < kThreads / 64; w++) {
-    if (w < wid) off += s_w[w];
-    tot += s_w[w];
-  }
-  __syncthreads();
-  *total = tot;
-  return off + pre;
-}
-
 __global__ __launch_bounds__(kThreads) void k_cnmp_points(const Job* jp, int nbi) {
   const Job& J = *jp;
   __shared__ float sA[kThreads * 33];
@@ -475,12 +389,8 @@ __global__ __launch_bounds__(kThreads) void k_cnmp_points(const Job* jp, int nbi
     for (int base = 0; base < n1; base += kThreads) {
       const int i = base + tid;
       const bool f = i < n1 && m12[i] >= 0 && m12[i] < K2.kf.n;
-      int tot;
-      const int pos = cn_block_scan(f, s_w, &tot);
-      if (f) J.pairs[np + pos] = i;
-      np += tot;
-    }
-    __syncthreads();  // the block's J.pairs stores before its loads
+      compact_chunk<kThreads>(f, s_w, np, [&](int slot) { J.pairs[slot] = i; });
+    }  // (the chunk's closing barrier: the block's J.pairs stores before its loads)
     int n_new = *J.n_new;
     for (int kb = 0; kb < np; kb += kThreads) {
       const int k = kb + tid;
@@ -500,10 +410,11 @@ __global__ __launch_bounds__(kThreads) void k_cnmp_points(const Job* jp, int nbi
         }
       }
       const bool acc = code >= ORBX_NP_TRIANGULATED && code <= ORBX_NP_UNPROJECT2;
-      int tot;
-      const int pos = cn_block_scan(acc, s_w, &tot);
-      if (acc && n_new + pos < n1) {  // (a feature gets one point at most: the bound always holds)
-        const size_t s = (size_t)(n_new + pos);
+      int end = n_new, slot = n1;  // end: n_new + the chunk's accepted pairs
+      compact_chunk<kThreads>(acc, s_w, end, [&](int s) { slot = s; });
+      if (slot < n1) {  // (a feature gets one point at most: the bound always holds); the point's stores
+                        // follow the chunk's closing barrier, which need not wait for them
+        const size_t s = (size_t)slot;
         J.pt_idx[3 * s] = nbi;
         J.pt_idx[3 * s + 1] = idx1;
         J.pt_idx[3 * s + 2] = idx2;
@@ -515,8 +426,8 @@ __global__ __launch_bounds__(kThreads) void k_cnmp_points(const Job* jp, int nbi
         J.pt_dist[2 * s + 1] = o.dmax;
         J.has_mp1[idx1] = 1;
       }
-      n_new = n_new + tot < n1 ? n_new + tot : n1;  // (saturates with the guard above: n_new never counts a
-                                                    // point that was not written)
+      n_new = end < n1 ? end : n1;  // (saturates with the guard above: n_new never counts a point that was
+                                    // not written)
     }
     if (tid == 0) {
       *J.n_new = n_new;

@@ -350,4 +350,24 @@ __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
   return v;
 }
 
+// Ordered compaction of one chunk of kBS items (one per thread, every thread of the block calls):
+// thread tid's kept item goes to slot base + (the kept items of lower threads); put(slot) stores it.
+// base advances by the chunk's kept count.  A slot never lies above the item's own position in the
+// list, so a caller may compact in place.  scan: kBS / 64 ints of LDS.
+template <int kBS, class Put>
+__device__ __forceinline__ void compact_chunk(bool keep, int* scan, int& base, Put put) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const uint64_t m = __ballot(keep);
+  const int pre = __popcll(m & ((1ull << lane) - 1));
+  if (lane == 0) scan[wid] = __popcll(m);
+  __syncthreads();  // (every item of this chunk has been read by now)
+  int off = base;
+  for (int w = 0; w < wid; w++) off += scan[w];
+  if (keep) put(off + pre);
+  int tot = 0;
+  for (int w = 0; w < kBS / 64; w++) tot += scan[w];
+  base += tot;
+  __syncthreads();
+}
+
 }  // namespace orbx

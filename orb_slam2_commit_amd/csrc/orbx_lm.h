@@ -2,8 +2,8 @@
 // vertex, optsim3.hip's Sim3 vertex): Eigen's quaternion product / rotation / matrix conversions and
 // the Eigen::LDLT<MatrixXd> restatement of oracle/poseopt.cpp, as a template on the system size;
 // and the Levenberg step itself (lm::Step, start / trial / iteration_end), which essgraph.hip's pose
-// graph and LocalBA's device control (ba_lm.h) run too, with the upper-triangle scatter and the ordered
-// block compaction of the single-vertex kernels.
+// graph and LocalBA's device control (ba_lm.h) run too, with the upper-triangle scatter of the
+// single-vertex kernels.
 // The operation sequences are the oracle's; nothing here may be re-associated.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -344,26 +344,6 @@ __host__ __device__ __forceinline__ void tri_rc(int q, int& r, int& c) {
     r++;
   }
   c += r;
-}
-
-// Ordered compaction of one chunk of kBS items (one per thread, every thread of the block calls):
-// thread tid's kept item goes to slot base + (the kept items of lower threads); put(slot) stores it.
-// base advances by the chunk's kept count.  A slot never lies above the item's own position in the
-// list, so a caller may compact in place.  scan: kBS / 64 ints of LDS.
-template <int kBS, class Put>
-__device__ __forceinline__ void compact_chunk(bool keep, int* scan, int& base, Put put) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const uint64_t m = __ballot(keep);
-  const int pre = __popcll(m & ((1ull << lane) - 1));
-  if (lane == 0) scan[wid] = __popcll(m);
-  __syncthreads();  // (every item of this chunk has been read by now)
-  int off = base;
-  for (int w = 0; w < wid; w++) off += scan[w];
-  if (keep) put(off + pre);
-  int tot = 0;
-  for (int w = 0; w < kBS / 64; w++) tot += scan[w];
-  base += tot;
-  __syncthreads();
 }
 
 }  // namespace lm

@@ -36,6 +36,7 @@
 
 #include "../../include/orbx.h"
 #include "orbx_cvsvd.h"
+#include "orbx_device.h"
 #include "orbx_ransac.h"
 
 namespace orbx {
@@ -648,29 +649,16 @@ struct PnpRefJob {
 template <bool kLds>
 __device__ __forceinline__ void pnp_refine_body(const PnpRefJob& J) {
   __shared__ EpnpSmall S;
-  __shared__ int wsum[4], base;
+  __shared__ int wsum[kRefThreads / 64];
   extern __shared__ __attribute__((aligned(16))) double dyn[];
   const PnpIn& in = J.in;
   const int tid = threadIdx.x;
   // ordered compaction of the best inlier set
-  if (tid == 0) base = 0;
-  __syncthreads();
-  for (int i0 = 0; i0 < in.N; i0 += 256) {
+  int n = 0;
+  for (int i0 = 0; i0 < in.N; i0 += kRefThreads) {
     const int i = i0 + tid;
-    const int f = (i < in.N && J.best[i]) ? 1 : 0;
-    const unsigned long long bal = __ballot(f);
-    const int lane = tid & 63, wv = tid >> 6;
-    const int pre = __popcll(bal & ((1ull << lane) - 1));
-    if (lane == 0) wsum[wv] = __popcll(bal);
-    __syncthreads();
-    int off = base;
-    for (int w = 0; w < wv; w++) off += wsum[w];
-    if (f) J.idx[off + pre] = i;
-    __syncthreads();
-    if (tid == 0) base += wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    __syncthreads();
+    compact_chunk<kRefThreads>(i < in.N && J.best[i], wsum, n, [&](int slot) { J.idx[slot] = i; });
   }
-  const int n = base;
   const int cap = kLds ? kRefineLdsPts : in.N;
   double* alphas = kLds ? dyn : J.work;
   double* tmp = alphas + 4 * (size_t)cap;

@@ -42,6 +42,8 @@
 #include "orbx_device.h"
 #include "orbx_internal.h"
 #include "orbx_proj.h"
+#include "orbx_cv.h"
+#include "orbx_match.h"
 
 namespace orbx {
 
@@ -53,7 +55,7 @@ constexpr int kThHigh = 100;
 
 // Deterministic natural log rounded to float (same operation sequence as the
 // oracle's log_det): frexp, 2*atanh series to s^25.
-__device__ float log_det(float xf) {
+__device__ float logf_det(float xf) {
   if (!(xf > 0.0f)) return xf == 0.0f ? -__builtin_inff() : __builtin_nanf("");
   if (__builtin_isinf(xf)) return __builtin_inff();
   int e;
@@ -75,7 +77,7 @@ __device__ float log_det(float xf) {
 // MapPoint::PredictScale(dist, Frame*), src/MapPoint.cc:424-440
 __device__ int predict_scale(float max_distance, float dist, float log_sf, int nlevels) {
   const float ratio = max_distance / dist;
-  const float q = log_det(ratio) / log_sf;
+  const float q = logf_det(ratio) / log_sf;
   int n;
   if (q != q) n = 0;
   else if (q > 1e6f) n = nlevels - 1;
@@ -86,48 +88,20 @@ __device__ int predict_scale(float max_distance, float dist, float log_sf, int n
   return n;
 }
 
-// `R*X + t` on 3x1 CV_32F Mats: cv::gemm(R, X, 1, t, 1) takes OpenCV 3.2's small-matrix path
-// (matmul.cpp: flags == 0, 2 <= len <= 4): the dot product in float, left to right, then
-// (float)(t0*alpha + c*beta) in double -- a correctly rounded float add of t.  (-R^T t, with
-// GEMM_1_T set, is the general GEMMSingleMul<float,double> path: double accumulation, below.)
-__device__ __forceinline__ void mat3x1(const float* T, const float* X, float* out) {
-#pragma unroll
-  for (int r = 0; r < 3; r++) {
-    const float t0 = T[4 * r + 0] * X[0] + T[4 * r + 1] * X[1] + T[4 * r + 2] * X[2];
-    out[r] = (float)((double)t0 + (double)T[4 * r + 3]);
-  }
-}
-// KeyFrame::GetCameraCenter (Fuse): Ow = -Rwc*tcw with Rwc a Mat -- cv::gemm's small-matrix path
+// `R*X + t`, `-Rwc*tcw`, `-mRcw.t()*mtcw` and cv::norm are orbx_cv.h's (the small-matrix gemm, and the
+// general GEMMSingleMul<float,double> path that a transpose flag selects).
+using cvmat::pose_apply;
+// KeyFrame::GetCameraCenter (Fuse): Ow = -Rwc*tcw with Rwc a Mat of its own -- cv::gemm's
+// small-matrix path, here without the `+ 0.0` of an absent C
 __device__ __forceinline__ void camera_centre_kf(const float* T, float* Ow) {
-#pragma unroll
-  for (int c = 0; c < 3; c++) {
-    const float t0 = T[c] * T[3] + T[4 + c] * T[7] + T[8 + c] * T[11];
-    Ow[c] = (float)((double)t0 * -1.0);
-  }
+  const float Rwc[9] = {T[0], T[4], T[8], T[1], T[5], T[9], T[2], T[6], T[10]};
+  const float tcw[3] = {T[3], T[7], T[11]};
+  cvmat::gemm31<3, cvmat::kBare>(Rwc, tcw, -1.0, Ow);
 }
-// Frame's mOw = -mRcw.t()*mtcw: GEMM_1_T, the general GEMMSingleMul<float,double> path
+// Frame's mOw = -mRcw.t()*mtcw: GEMM_1_T, the sum started at its first product
 __device__ __forceinline__ void camera_centre(const float* T, float* Ow) {
-#pragma unroll
-  for (int c = 0; c < 3; c++) {
-    double s = (double)T[c] * T[3];
-    s = s + (double)T[4 + c] * T[7];
-    s = s + (double)T[8 + c] * T[11];
-    Ow[c] = (float)(-s);
-  }
-}
-__device__ __forceinline__ float norm3(const float* v) {
-  double s = (double)v[0] * v[0];
-  s = s + (double)v[1] * v[1];
-  s = s + (double)v[2] * v[2];
-  return (float)__builtin_sqrt(s);
-}
-
-__device__ __forceinline__ int rot_bin(float a, float b) {
-  float rot = a - b;
-  if (rot < 0.0) rot += 360.0f;
-  int bin = (int)__builtin_roundf(rot * (1.0f / 30));
-  if (bin == 30) bin = 0;
-  return bin;
+  const float tcw[3] = {T[3], T[7], T[11]};
+  cvmat::gemm31_at<4, false>(T, tcw, -1.0, Ow);
 }
 
 // The per-point search window (everything the reference derives before its
@@ -168,14 +142,14 @@ __device__ Query setup_query(const ProjProblem& P, int i, const float* Tcw, cons
   float c[3];
   if (P.kind == ORBX_PROJ_BY_SIM3) {  // one direction of SearchBySim3, src/ORBmatcher.cc:1283-1340
     float c1[3];
-    mat3x1(Tcw, X, c1);          // R1w*p3Dw + t1w (the point's own KeyFrame)
-    mat3x1(P.last_Tcw, c1, c);   // sR21*p3Dc1 + t21
+    pose_apply(Tcw, X, c1);          // R1w*p3Dw + t1w (the point's own KeyFrame)
+    pose_apply(P.last_Tcw, c1, c);   // sR21*p3Dc1 + t21
     if (c[2] < 0.0f) return q;
     const float invz = (float)(1.0 / (double)c[2]);
     const float x = c[0] * invz, y = c[1] * invz;
     const float u = F.fx * x + F.cx, v = F.fy * y + F.cy;
     if (!(u >= F.min_x && u < F.max_x && v >= F.min_y && v < F.max_y)) return q;  // KeyFrame::IsInImage
-    const float d3 = norm3(c);
+    const float d3 = (float)cvmat::norm3(c);
     const float dmin = P.dist_minmax[2 * i], dmax = P.dist_minmax[2 * i + 1];
     if (d3 < 0.8f * dmin || d3 > 1.2f * dmax) return q;
     const int lvl = predict_scale(dmax, d3, F.log_scale_factor, F.nlevels);
@@ -189,7 +163,7 @@ __device__ Query setup_query(const ProjProblem& P, int i, const float* Tcw, cons
     q.active = true;
     return q;
   }
-  mat3x1(Tcw, X, c);
+  pose_apply(Tcw, X, c);
   if (P.kind == ORBX_PROJ_FUSE || P.kind == ORBX_PROJ_SIM3 || P.kind == ORBX_PROJ_FUSE_SIM3) {
     // src/ORBmatcher.cc:960-1006, :352-391, :1117-1160
     if (c[2] < 0.0f) return q;
@@ -198,7 +172,7 @@ __device__ Query setup_query(const ProjProblem& P, int i, const float* Tcw, cons
     const float u = F.fx * x + F.cx, v = F.fy * y + F.cy;
     if (!(u >= F.min_x && u < F.max_x && v >= F.min_y && v < F.max_y)) return q;  // KeyFrame::IsInImage
     const float PO[3] = {X[0] - Ow[0], X[1] - Ow[1], X[2] - Ow[2]};
-    const float d3 = norm3(PO);
+    const float d3 = (float)cvmat::norm3(PO);
     const float dmin = P.dist_minmax[2 * i], dmax = P.dist_minmax[2 * i + 1];
     if (d3 < 0.8f * dmin || d3 > 1.2f * dmax) return q;
     const float* Pn = P.normal + 3 * i;
@@ -246,7 +220,7 @@ __device__ Query setup_query(const ProjProblem& P, int i, const float* Tcw, cons
     q.th = kThHigh;
   } else {
     const float PO[3] = {X[0] - Ow[0], X[1] - Ow[1], X[2] - Ow[2]};
-    const float d3 = norm3(PO);
+    const float d3 = (float)cvmat::norm3(PO);
     const float dmin = P.dist_minmax[2 * i], dmax = P.dist_minmax[2 * i + 1];
     if (d3 < 0.8f * dmin || d3 > 1.2f * dmax) return q;
     const int lvl = predict_scale(dmax, d3, F.log_scale_factor, F.nlevels);
@@ -301,7 +275,7 @@ __device__ __forceinline__ void proj_centre(const ProjProblem& P, const float* s
   fwd = bwd = false;
   if (P.kind == ORBX_PROJ_LAST_FRAME) {
     float tlc[3];
-    mat3x1(P.last_Tcw, Ow, tlc);  // twc = Ow
+    pose_apply(P.last_Tcw, Ow, tlc);  // twc = Ow
     fwd = tlc[2] > P.f.b && !P.mono;
     bwd = -tlc[2] > P.f.b && !P.mono;
   }
@@ -361,7 +335,7 @@ __device__ __forceinline__ void proj_frustum(const ProjProblem& P, int i, const 
   if (P.flags[i] & 1) {
     const float* X = P.pos + 3 * i;
     float c[3];
-    mat3x1(s_Tcw, X, c);
+    pose_apply(s_Tcw, X, c);
     if (!(c[2] < 0.0f)) {
       const float invz = 1.0f / c[2];
       const float u = F.fx * c[0] * invz + F.cx;
@@ -369,7 +343,7 @@ __device__ __forceinline__ void proj_frustum(const ProjProblem& P, int i, const 
       if (!(u < F.min_x || u > F.max_x) && !(v < F.min_y || v > F.max_y) && u == u && v == v) {
         const float dmin = P.dist_minmax[2 * i], dmax = P.dist_minmax[2 * i + 1];
         const float PO[3] = {X[0] - Ow[0], X[1] - Ow[1], X[2] - Ow[2]};
-        const float dist = norm3(PO);
+        const float dist = (float)cvmat::norm3(PO);
         if (!(dist < 0.8f * dmin || dist > 1.2f * dmax)) {
           const float* Pn = P.normal + 3 * i;
           double dot = (double)PO[0] * Pn[0];
@@ -547,31 +521,7 @@ __device__ void proj_final(const ProjProblem& P, int nF, int nP, int* s_fw, int*
   }
   atomicAdd(s_count, cnt);
   __syncthreads();
-  if (rot && tid == 0) {  // ComputeThreeMaxima, src/ORBmatcher.cc:1797-1839
-    int m1 = 0, m2 = 0, m3 = 0, i1 = -1, i2 = -1, i3 = -1;
-    for (int b = 0; b < 30; b++) {
-      const int s = s_hist[b];
-      if (s > m1) {
-        m3 = m2; m2 = m1; m1 = s;
-        i3 = i2; i2 = i1; i1 = b;
-      } else if (s > m2) {
-        m3 = m2; m2 = s;
-        i3 = i2; i2 = b;
-      } else if (s > m3) {
-        m3 = s;
-        i3 = b;
-      }
-    }
-    if (m2 < 0.1f * (float)m1) {
-      i2 = -1;
-      i3 = -1;
-    } else if (m3 < 0.1f * (float)m1) {
-      i3 = -1;
-    }
-    s_sel[0] = i1;
-    s_sel[1] = i2;
-    s_sel[2] = i3;
-  }
+  if (rot && tid == 0) three_maxima(s_hist, s_sel);
   __syncthreads();
   if (rot) {
     int drop = 0;
@@ -989,31 +939,7 @@ __device__ void init_final(const orbx_init_problem& P, const InitLds& S, int* s_
     }
   }
   __syncthreads();
-  if (P.check_ori && tid == 0) {  // ComputeThreeMaxima
-    int m1 = 0, m2 = 0, m3 = 0, i1 = -1, i2 = -1, i3 = -1;
-    for (int b = 0; b < 30; b++) {
-      const int sz = s_hist[b];
-      if (sz > m1) {
-        m3 = m2; m2 = m1; m1 = sz;
-        i3 = i2; i2 = i1; i1 = b;
-      } else if (sz > m2) {
-        m3 = m2; m2 = sz;
-        i3 = i2; i2 = b;
-      } else if (sz > m3) {
-        m3 = sz;
-        i3 = b;
-      }
-    }
-    if (m2 < 0.1f * (float)m1) {
-      i2 = -1;
-      i3 = -1;
-    } else if (m3 < 0.1f * (float)m1) {
-      i3 = -1;
-    }
-    s_sel[0] = i1;
-    s_sel[1] = i2;
-    s_sel[2] = i3;
-  }
+  if (P.check_ori && tid == 0) three_maxima(s_hist, s_sel);
   __syncthreads();
   int cnt = 0;
 #pragma unroll
@@ -1367,20 +1293,20 @@ extern "C" orbx_status orbx_search_by_projection_device(const orbx_proj_problem*
 namespace {
 // sR12 = s12*R12, sR21 = (1.0/s12)*R12.t(), t21 = -sR21*t12 (src/ORBmatcher.cc:1252-1254): a Mat times
 // a scalar is convertTo(alpha) -- x * (float)alpha + 0.0f in float; R12.t() scaled is transpose then
-// convertTo; -A*b is cv::gemm's small-matrix path (float dot, then (float)((double)t0 * -1.0))
+// convertTo, here always the product; -A*b is cv::gemm's small-matrix path without the `+ 0.0` of an
+// absent C
 void sim3_pair(float s12, const float* R12, const float* t12, float* sR12_t12, float* sR21_t21) {
-  const float a12 = (float)(double)s12, a21 = (float)(1.0 / (double)s12);
+  using namespace orbx::cvmat;
   for (int r = 0; r < 3; r++) {
     for (int c = 0; c < 3; c++) {
-      sR12_t12[4 * r + c] = R12[3 * r + c] * a12 + 0.0f;
-      sR21_t21[4 * r + c] = R12[3 * c + r] * a21 + 0.0f;
+      sR12_t12[4 * r + c] = scale<false>(R12[3 * r + c], (double)s12);
+      sR21_t21[4 * r + c] = scale<false>(R12[3 * c + r], 1.0 / (double)s12);
     }
     sR12_t12[4 * r + 3] = t12[r];
   }
-  for (int r = 0; r < 3; r++) {
-    const float t0 = sR21_t21[4 * r] * t12[0] + sR21_t21[4 * r + 1] * t12[1] + sR21_t21[4 * r + 2] * t12[2];
-    sR21_t21[4 * r + 3] = (float)((double)t0 * -1.0);
-  }
+  float t21[3];
+  gemm31<4, kBare>(sR21_t21, t12, -1.0, t21);
+  for (int r = 0; r < 3; r++) sR21_t21[4 * r + 3] = t21[r];
   for (int k = 12; k < 16; k++) sR12_t12[k] = sR21_t21[k] = k == 15 ? 1.0f : 0.0f;
 }
 }  // namespace

@@ -33,6 +33,7 @@
 
 #include "../../include/orbx.h"
 #include "../../include/orbx_debug.h"
+#include "orbx_cv.h"
 #include "orbx_device.h"
 #include "orbx_ransac.h"
 
@@ -233,15 +234,7 @@ __device__ void sim3_compute(const Sim3In& in, const int* __restrict__ idx, floa
   sim3_centroid(P2, Pr2, O2);
   // Step 2: M = Pr2 * Pr1.t(), GEMMSingleMul<float,double>: the sum in double, rounded once
   float M[9];
-#pragma unroll
-  for (int i = 0; i < 3; i++)
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-      double s0 = 0;
-#pragma unroll
-      for (int k = 0; k < 3; k++) s0 += (double)Pr2[3 * i + k] * (double)Pr1[3 * j + k];
-      M[3 * i + j] = (float)(s0 * 1.0);
-    }
+  cvmat::gemm33_bt<3>(Pr2, Pr1, 1.0, M);
   // Step 3: N (float sums, left to right)
   const float N11 = M[0] + M[4] + M[8], N12 = M[5] - M[7], N13 = M[6] - M[2], N14 = M[1] - M[3];
   const float N22 = M[0] - M[4] - M[8], N23 = M[1] + M[3], N24 = M[6] + M[2];
@@ -254,13 +247,11 @@ __device__ void sim3_compute(const Sim3In& in, const int* __restrict__ idx, floa
   jacobi4(sA, sW, sV, sInd);
   const float q0 = sV[0];
   float vec[3] = {sV[1], sV[2], sV[3]};
-  const double nrm = __builtin_sqrt((double)vec[0] * (double)vec[0] + (double)vec[1] * (double)vec[1] +
-                                    (double)vec[2] * (double)vec[2]);
+  const double nrm = cvmat::norm3(vec);
   const double ang = atan2_det(nrm, (double)q0);
-  // vec = 2*ang*vec/norm(vec): one MatExpr scale alpha = (2*ang) * (1./norm), convertTo
-  const float alpha = (float)((2 * ang) * (1. / nrm));
+  // vec = 2*ang*vec/norm(vec): one MatExpr scale alpha = (2*ang) * (1./norm), convertTo (always the product)
 #pragma unroll
-  for (int i = 0; i < 3; i++) vec[i] = vec[i] * alpha + 0.0f;
+  for (int i = 0; i < 3; i++) vec[i] = cvmat::scale<false>(vec[i], (2 * ang) * (1. / nrm));
   // cv::Rodrigues
   float R[9];
   {
@@ -283,21 +274,13 @@ __device__ void sim3_compute(const Sim3In& in, const int* __restrict__ idx, floa
       for (int k = 0; k < 9; k++) R[k] = (float)(c * ((k % 4) == 0 ? 1. : 0.) + c1 * rrt[k] + s * r_x[k]);
     }
   }
-  // Step 5: P3 = R * Pr2 (small-matrix gemm: float sums, + 0)
+  // Step 5: P3 = R * Pr2
   float P3[9];
-#pragma unroll
-  for (int i = 0; i < 3; i++)
-#pragma unroll
-    for (int j = 0; j < 3; j++)
-      P3[3 * i + j] = (R[3 * i] * Pr2[j] + R[3 * i + 1] * Pr2[3 + j] + R[3 * i + 2] * Pr2[6 + j]) + 0.0f;
+  cvmat::gemm33<3>(R, Pr2, 1.0, P3);
   // Step 6
   float s12;
   if (!in.fix_scale) {
-    // Mat::dot, 9 elements: double products, summed four at a time then the tail
-    double nom = 0;
-    nom += (double)Pr1[0] * P3[0] + (double)Pr1[1] * P3[1] + (double)Pr1[2] * P3[2] + (double)Pr1[3] * P3[3];
-    nom += (double)Pr1[4] * P3[4] + (double)Pr1[5] * P3[5] + (double)Pr1[6] * P3[6] + (double)Pr1[7] * P3[7];
-    nom += (double)Pr1[8] * P3[8];
+    const double nom = cvmat::dot<9>(Pr1, P3);  // (two sums of four, then the tail)
     double den = 0;
 #pragma unroll
     for (int k = 0; k < 9; k++) den += (double)(P3[k] * P3[k]);
@@ -307,29 +290,20 @@ __device__ void sim3_compute(const Sim3In& in, const int* __restrict__ idx, floa
   }
   // Step 7: t12 = O1 - s*R*O2, one gemm with alpha = -s, beta = 1
   float t12[3];
-#pragma unroll
-  for (int i = 0; i < 3; i++) {
-    const float t0 = R[3 * i] * O2[0] + R[3 * i + 1] * O2[1] + R[3 * i + 2] * O2[2];
-    t12[i] = (float)((double)t0 * (-(double)s12) + (double)O1[i] * 1.0);
-  }
-  // Step 8.1: T12 = [s*R | t12]
+  cvmat::gemm31_add<3>(R, O2, -(double)s12, O1, t12);
+  // Step 8.1: T12 = [s*R | t12] (always the product)
   float sR[9];
 #pragma unroll
-  for (int k = 0; k < 9; k++) sR[k] = R[k] * s12 + 0.0f;
+  for (int k = 0; k < 9; k++) sR[k] = cvmat::scale<false>(R[k], (double)s12);
   // Step 8.2: T21 = [(1/s)*R.t() | -sRinv*t12]; the transpose alone when the scale is exactly 1
   const double ia = 1.0 / (double)s12;
-  const float iaf = (float)ia;
   float sRinv[9];
 #pragma unroll
   for (int i = 0; i < 3; i++)
 #pragma unroll
-    for (int j = 0; j < 3; j++) sRinv[3 * i + j] = ia != 1.0 ? R[3 * j + i] * iaf + 0.0f : R[3 * j + i];
+    for (int j = 0; j < 3; j++) sRinv[3 * i + j] = ia != 1.0 ? cvmat::scale<false>(R[3 * j + i], ia) : R[3 * j + i];
   float tinv[3];
-#pragma unroll
-  for (int i = 0; i < 3; i++) {
-    const float t0 = sRinv[3 * i] * t12[0] + sRinv[3 * i + 1] * t12[1] + sRinv[3 * i + 2] * t12[2];
-    tinv[i] = (float)((double)t0 * -1.0 + 0.0);
-  }
+  cvmat::gemm31<3>(sRinv, t12, -1.0, tinv);
 #pragma unroll
   for (int r = 0; r < 3; r++) {
 #pragma unroll
@@ -354,11 +328,7 @@ __device__ void sim3_compute(const Sim3In& in, const int* __restrict__ idx, floa
 __device__ __forceinline__ void sim3_project(const float* __restrict__ T, const float X[3], float fx, float fy,
                                              float cx, float cy, float* u, float* v) {
   float P[3];
-#pragma unroll
-  for (int r = 0; r < 3; r++) {
-    const float t0 = T[4 * r] * X[0] + T[4 * r + 1] * X[1] + T[4 * r + 2] * X[2];
-    P[r] = (float)((double)t0 * 1.0 + (double)T[4 * r + 3] * 1.0);
-  }
+  cvmat::pose_apply(T, X, P);
   const float invz = 1 / P[2];
   const float x = P[0] * invz, y = P[1] * invz;
   *u = fx * x + cx;

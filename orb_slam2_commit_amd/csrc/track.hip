@@ -17,6 +17,8 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/orbx.h"
+#include "orbx_cv.h"
+#include "orbx_device.h"
 #include "orbx_scratch.h"
 
 namespace orbx {
@@ -27,12 +29,10 @@ constexpr int TBS = 256;
 __global__ __launch_bounds__(TBS) void k_track_gather(const orbx_track_gather* __restrict__ probs) {
   const orbx_track_gather& P = probs[blockIdx.x];
   __shared__ int wsum[TBS / 64];
-  __shared__ int base;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int tid = threadIdx.x;
   const int n = *P.f_count;
   const float invfx = 1.0f / P.fx, invfy = 1.0f / P.fy;  // Frame/KeyFrame invfx = 1.0f/fx
-  if (tid == 0) base = 0;
-  __syncthreads();
+  int base = 0;
   for (int i0 = 0; i0 < n; i0 += TBS) {
     const int i = i0 + tid;
     int k = -1;
@@ -40,25 +40,12 @@ __global__ __launch_bounds__(TBS) void k_track_gather(const orbx_track_gather* _
       k = P.match[i];
       if (k >= 0 && !(P.kf_depth[k] > 0.0f)) k = -1;  // no MapPoint behind that KeyFrame feature
     }
-    const bool e = k >= 0;
-    const unsigned long long b = __ballot(e);
-    const int pre = __popcll(b & ((1ull << lane) - 1));
-    if (lane == 0) wsum[wv] = __popcll(b);
-    __syncthreads();
-    int off = base;
-    for (int w = 0; w < wv; w++) off += wsum[w];
-    if (e) {
-      const int o = off + pre;
+    compact_chunk<TBS>(k >= 0, wsum, base, [&](int o) {
       const orbx_keypoint kf = P.kf_kps[k];
       const float z = P.kf_depth[k];
-      const float x = (kf.x - P.cx) * z * invfx;
-      const float y = (kf.y - P.cy) * z * invfy;
+      const float xc[3] = {(kf.x - P.cx) * z * invfx, (kf.y - P.cy) * z * invfy, z};
       float X[3];
-#pragma unroll
-      for (int r = 0; r < 3; r++) {  // mRwc*x3Dc+mOw: cv::gemm's small-matrix path (float dot, then + Ow)
-        const float t0 = P.Twc[4 * r] * x + P.Twc[4 * r + 1] * y + P.Twc[4 * r + 2] * z;
-        X[r] = (float)((double)t0 + (double)P.Twc[4 * r + 3]);
-      }
+      cvmat::pose_apply(P.Twc, xc, X);  // mRwc*x3Dc+mOw
       const orbx_keypoint f = P.f_kps[i];
       P.obs[3 * o] = f.x;
       P.obs[3 * o + 1] = f.y;
@@ -68,14 +55,7 @@ __global__ __launch_bounds__(TBS) void k_track_gather(const orbx_track_gather* _
       P.Xw[3 * o + 2] = X[2];
       P.inv_sigma2[o] = P.inv_level_sigma2[f.octave];
       if (P.edge_feature) P.edge_feature[o] = i;
-    }
-    __syncthreads();
-    if (tid == 0) {
-      int t = base;
-      for (int w = 0; w < TBS / 64; w++) t += wsum[w];
-      base = t;
-    }
-    __syncthreads();
+    });
   }
   if (tid == 0) *P.n_edges = base;
 }
@@ -102,17 +82,12 @@ __global__ __launch_bounds__(TBS) void k_frame_points(const orbx_frame_points* _
   const float invfx = 1.0f / P.fx, invfy = 1.0f / P.fy;
   const float x = (kp.x - P.cx) * z * invfx;
   const float y = (kp.y - P.cy) * z * invfy;
+  const float xc[3] = {x, y, z};
   float X[3], PC[3];
+  cvmat::pose_apply(P.Twc, xc, X);
 #pragma unroll
-  for (int r = 0; r < 3; r++) {
-    const float t0 = P.Twc[4 * r] * x + P.Twc[4 * r + 1] * y + P.Twc[4 * r + 2] * z;
-    X[r] = (float)((double)t0 + (double)P.Twc[4 * r + 3]);
-    PC[r] = X[r] - P.Twc[4 * r + 3];
-  }
-  double ss = (double)PC[0] * PC[0];
-  ss = ss + (double)PC[1] * PC[1];
-  ss = ss + (double)PC[2] * PC[2];
-  const double nrm = __builtin_sqrt(ss);
+  for (int r = 0; r < 3; r++) PC[r] = X[r] - P.Twc[4 * r + 3];
+  const double nrm = cvmat::norm3(PC);
   const float sc = (float)(1.0 / nrm);
   const float dist = (float)nrm;
   const int lvl = min(max(kp.octave, 0), P.nlevels - 1);
@@ -128,23 +103,14 @@ __global__ __launch_bounds__(TBS) void k_frame_points(const orbx_frame_points* _
 
 // ---- TrackWithMotionModel / TrackLocalMap bookkeeping (orbx_track_step) ----------------------
 // Edges of the frame's current MapPoint table, in feature order (src/Optimizer.cc:318-410): an
-// ordered block compaction as in k_track_gather.
-__device__ void track_edges(const orbx_track_step& P, int n, bool lost, int* wsum, int* base) {
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  if (tid == 0) *base = 0;
-  __syncthreads();
+// ordered block compaction (compact_chunk) as in k_track_gather.
+__device__ void track_edges(const orbx_track_step& P, int n, bool lost, int* wsum) {
+  const int tid = threadIdx.x;
+  int base = 0;
   for (int i0 = 0; i0 < (lost ? 0 : n); i0 += TBS) {
     const int i = i0 + tid;
     const int k = i < n ? P.fmap[i] : -1;
-    const bool e = k >= 0;
-    const unsigned long long b = __ballot(e);
-    const int pre = __popcll(b & ((1ull << lane) - 1));
-    if (lane == 0) wsum[wv] = __popcll(b);
-    __syncthreads();
-    int off = *base;
-    for (int w = 0; w < wv; w++) off += wsum[w];
-    if (e) {
-      const int o = off + pre;
+    compact_chunk<TBS>(k >= 0, wsum, base, [&](int o) {
       const orbx_keypoint f = P.kps[i];
       P.obs[3 * o] = f.x;
       P.obs[3 * o + 1] = f.y;
@@ -153,22 +119,14 @@ __device__ void track_edges(const orbx_track_step& P, int n, bool lost, int* wsu
       for (int c = 0; c < 3; c++) P.Xw[3 * o + c] = P.pos[3 * k + c];
       P.inv_sigma2[o] = P.inv_level_sigma2[f.octave];
       P.edge_feature[o] = i;
-    }
-    __syncthreads();
-    if (tid == 0) {
-      int t = *base;
-      for (int w = 0; w < TBS / 64; w++) t += wsum[w];
-      *base = t;
-    }
-    __syncthreads();
+    });
   }
-  if (tid == 0) *P.n_edges = *base;
+  if (tid == 0) *P.n_edges = base;
 }
 
 __global__ __launch_bounds__(TBS) void k_track_step(const orbx_track_step* __restrict__ probs) {
   const orbx_track_step& P = probs[blockIdx.x];
   __shared__ int wsum[TBS / 64];
-  __shared__ int base;
   __shared__ int s_lost;
   const int tid = threadIdx.x;
   const int n = min(max(*P.count, 0), P.cap);
@@ -185,7 +143,7 @@ __global__ __launch_bounds__(TBS) void k_track_step(const orbx_track_step* __res
     }
     __syncthreads();
     if (tid == 0) *P.lost = s_lost;
-    track_edges(P, n, s_lost != 0, wsum, &base);
+    track_edges(P, n, s_lost != 0, wsum);
   } else if (P.op == ORBX_TRACK_AFTER_POSE) {
     // :1093-1107 outliers leave the frame; :1135 nmatchesMap >= 10; :1408-1430 SearchLocalPoints' inputs
     if (tid == 0) s_lost = (*P.lost != 0 || *P.ngood < P.min_good) ? 1 : 0;
@@ -206,7 +164,7 @@ __global__ __launch_bounds__(TBS) void k_track_step(const orbx_track_step* __res
         if (k >= 0) P.fmap[i] = k;
       }
     __syncthreads();
-    track_edges(P, n, s_lost != 0, wsum, &base);
+    track_edges(P, n, s_lost != 0, wsum);
   }
 }
 

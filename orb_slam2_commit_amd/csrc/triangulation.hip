@@ -1,6 +1,6 @@
 // triangulation.hip -- ORBmatcher::SearchForTriangulation
-// (src/ORBmatcher.cc:738-925) with CheckDistEpipolarLine (:153-173) and
-// ComputeThreeMaxima (:1797-1839), batched: one block per KeyFrame pair.
+// (src/ORBmatcher.cc:738-925) with CheckDistEpipolarLine (:153-173), batched: one block per KeyFrame
+// pair; ComputeThreeMaxima (:1797-1839) is orbx_match.h's.
 //
 // In this reference commit vbMatched2 is never set (:760, :810), so each KF1
 // feature's match depends only on its own FeatureVector node: waves take the
@@ -20,20 +20,14 @@
 #include "orbx_scratch.h"
 #include "orbx_device.h"
 #include "orbx_internal.h"
+#include "orbx_cv.h"
+#include "orbx_match.h"
 
 namespace orbx {
 namespace tri {
 
 constexpr int TBS = 256;
 constexpr int kOwn = 4;  // KF2 node features per lane held in registers
-
-__device__ __forceinline__ int rot_bin(float a, float b) {
-  float rot = a - b;
-  if (rot < 0.0) rot += 360.0f;
-  int bin = (int)__builtin_roundf(rot * (1.0f / 30));
-  if (bin == 30) bin = 0;
-  return bin;
-}
 
 __global__ __launch_bounds__(TBS) void k_search_for_triangulation(const orbx_tri_problem* __restrict__ probs) {
   __shared__ int s_hist[32];
@@ -50,11 +44,7 @@ __global__ __launch_bounds__(TBS) void k_search_for_triangulation(const orbx_tri
   }
   // epipole of KF1 in KF2 (src/ORBmatcher.cc:748-756)
   float C2[3];
-#pragma unroll
-  for (int r = 0; r < 3; r++) {  // R2w*Cw+t2w: cv::gemm's small-matrix path (float dot, then + t)
-    const float t0 = P.T2w[4 * r] * P.C1w[0] + P.T2w[4 * r + 1] * P.C1w[1] + P.T2w[4 * r + 2] * P.C1w[2];
-    C2[r] = (float)((double)t0 + (double)P.T2w[4 * r + 3]);
-  }
+  cvmat::pose_apply(P.T2w, P.C1w, C2);  // R2w*Cw+t2w
   const float invz = 1.0f / C2[2];
   const float ex = P.fx * C2[0] * invz + P.cx;
   const float ey = P.fy * C2[1] * invz + P.cy;
@@ -157,31 +147,7 @@ __global__ __launch_bounds__(TBS) void k_search_for_triangulation(const orbx_tri
   __threadfence_block();
   __syncthreads();
   if (P.check_ori) {
-    if (tid == 0) {
-      int m1 = 0, m2 = 0, m3 = 0, i1 = -1, i2 = -1, i3 = -1;
-      for (int b = 0; b < 30; b++) {
-        const int s = s_hist[b];
-        if (s > m1) {
-          m3 = m2; m2 = m1; m1 = s;
-          i3 = i2; i2 = i1; i1 = b;
-        } else if (s > m2) {
-          m3 = m2; m2 = s;
-          i3 = i2; i2 = b;
-        } else if (s > m3) {
-          m3 = s;
-          i3 = b;
-        }
-      }
-      if (m2 < 0.1f * (float)m1) {
-        i2 = -1;
-        i3 = -1;
-      } else if (m3 < 0.1f * (float)m1) {
-        i3 = -1;
-      }
-      s_sel[0] = i1;
-      s_sel[1] = i2;
-      s_sel[2] = i3;
-    }
+    if (tid == 0) three_maxima(s_hist, s_sel);
     __syncthreads();
     int drop = 0;
     for (int i = tid; i < K1.n; i += TBS) {

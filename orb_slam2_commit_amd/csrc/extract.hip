@@ -743,8 +743,13 @@ __global__ __launch_bounds__(BS, ORBX_BLUR_WPE) void k_blur(const Geometry* __re
 //   2. compass quick test (two adjacent of ring pixels 0,4,8,12 beyond t), as
 //      min(max(p0,p8), max(p4,p12)) > c+t or max(min(p0,p8), min(p4,p12)) < c-t
 //      (six min/max on the raw bytes; 0.855 -> 0.820 ms against the earlier packed
-//      sign-bit form), survivors compacted by ballot rank as tile offsets e = y*S + x
-//      (the 7x7 neighbourhood's top-left);
+//      sign-bit form), on TWO rows of a column per lane: the sub-steps u and u + 1 of a trip sit in
+//      the low and high 16 bits of each register (ds_read_u8 x 2 + v_perm per byte pair), so the
+//      six min/max, the two differences and their maximum are nine v_pk_*_{u,i}16 for 128
+//      pixels; each half then has one SDWA compare against t whose scalar mask, and-ed with the
+//      cell's column mask (one ballot per cell), is both the ballot and the branch condition.
+//      Survivors are compacted by ballot rank as tile offsets e = y*S + x (the 7x7
+//      neighbourhood's top-left), low half first, so the list stays row-major;
 //   3. cornerScore and the corner test in ONE pass on the compacted list:
 //      ring pixel p is packed as the f16 pair (1024+p, 1279-p) (one v_mad_i32_i24:
 //      bits 0x6400+p / 0x64FF-p), the 9-arc maximum of both halves is two rounds
@@ -818,6 +823,17 @@ __device__ __forceinline__ int as_int(s16x2 v) { return __builtin_bit_cast(int, 
 __device__ __forceinline__ int lane_rank(uint64_t m) {
   return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
+// two bytes as a 16-bit pair, packed where the bytes are loaded: left to itself the compiler packs
+// them at their use, in a later block, where it no longer knows the loads zero-extended (a v_and per
+// byte) and keeps both bytes live until then
+__device__ __forceinline__ u16x2 pair16(uint8_t lo, uint8_t hi) {
+  uint32_t v = __builtin_bit_cast(uint32_t, u16x2{lo, hi});
+  asm("" : "+v"(v));
+  return __builtin_bit_cast(u16x2, v);
+}
+// the lane mask of a condition as it stands in its scalar pair (__ballot goes through an integer
+// compare, which materialises a condition that is not itself a compare: v_cndmask + v_cmp_ne)
+__device__ __forceinline__ uint64_t ballot64(bool p) { return __builtin_amdgcn_ballot_w64(p); }
 
 // Phase probe (build with -DORBX_FAST_PROBE only; tools/fast_probe.py): per-phase s_memtime
 // deltas of every cell wave, stored (plain vector stores, no contention) to a host-provided
@@ -915,8 +931,12 @@ __global__ __launch_bounds__(64) void k_fast(const Geometry* __restrict__ G, con
   __syncthreads();
   const int ini = min(max(G->ini_th, 0), 255), mint = min(max(G->min_th, 0), 255);
   const int ly = RP == 2 ? (lane >> 5) : 0, lx = RP == 2 ? (lane & 31) : lane;
-  const int cw = lx - W;
+  // the lanes whose column is inside the region (W only: once per cell), and those of them on a
+  // compass instruction's first row
+  const bool col_ok = lx < W, col_ok0 = col_ok && ly == 0;
+  const uint64_t colm = ballot64(col_ok), colm0 = colm & 0xFFFFFFFFull;
   constexpr int QU = 8 / RP;
+  static_assert(QU % 2 == 0, "the compass trip pairs its sub-steps");
 #ifdef ORBX_FAST_PROBE
   unsigned long long ts_mid = 0;
   int n_compass = 0, n_even8 = 0, n_corner_ini = 0;
@@ -929,34 +949,56 @@ __global__ __launch_bounds__(64) void k_fast(const Geometry* __restrict__ G, con
     int n = 0;
     // QU * RP region rows per trip; nu: the sub-steps of the trip whose first row is inside the region
     // (wave-uniform).  Full trips (nu = QU) are branch-free; the peeled last trip skips the others.
+    // Sub-steps u and u + 1 (RP rows apart: the same lane, the same column) share one set of
+    // registers, u in the low and u + 1 in the high 16 bits, so the byte arithmetic of 128 pixels is
+    // one packed 16-bit instruction; each half then has its own compare, ballot and row-major stores.
     auto trip = [&](int y0r, auto fullc, int nu) {
       constexpr bool full = decltype(fullc)::value;
       const int eb = (y0r + ly) * S + lx;
-      int cv[QU], c0[QU], c4[QU], c8[QU], c12[QU];
+      u16x2 cv[QU / 2], c0[QU / 2], c4[QU / 2], c8[QU / 2], c12[QU / 2];
 #pragma unroll
-      for (int u = 0; u < QU; u++) {
-        if (!full && u >= nu) break;
-        const uint8_t* t = tile + eb + u * RP * S;
-        cv[u] = t[3 * S + 3];
-        c0[u] = t[6 * S + 3];
-        c4[u] = t[3 * S + 6];
-        c8[u] = t[3];
-        c12[u] = t[3 * S];
+      for (int p = 0; p < QU / 2; p++) {
+        if (!full && 2 * p >= nu) break;
+        // an unpaired last sub-step reads its high half from rows past the window: at most three
+        // rows, which lie in the score map behind the tile, and that half is never looked at
+        const uint8_t* t = tile + eb + 2 * p * RP * S;
+        const uint8_t* t2 = t + RP * S;
+        cv[p] = pair16(t[3 * S + 3], t2[3 * S + 3]);
+        c0[p] = pair16(t[6 * S + 3], t2[6 * S + 3]);
+        c4[p] = pair16(t[3 * S + 6], t2[3 * S + 6]);
+        c8[p] = pair16(t[3], t2[3]);
+        c12[p] = pair16(t[3 * S], t2[3 * S]);
       }
 #pragma unroll
-      for (int u = 0; u < QU; u++) {
-        if (!full && u >= nu) break;
+      for (int p = 0; p < QU / 2; p++) {
+        if (!full && 2 * p >= nu) break;
         // two ADJACENT compass points beyond the threshold <=> (p0 | p8) & (p4 | p12) per
         // polarity, i.e. min(max(p0,p8), max(p4,p12)) > c+t or max(min(p0,p8), min(p4,p12)) < c-t:
-        // min/max on the raw bytes, one difference per polarity
-        const int hi = min(max(c0[u], c8[u]), max(c4[u], c12[u]));
-        const int lo = max(min(c0[u], c8[u]), min(c4[u], c12[u]));
-        const int v = max(hi - cv[u], cv[u] - lo) - (th + 1);  // >= 0 <=> compass hit
-        // lane inside the region: (col - W) and (row - H) both negative, and v >= 0
-        const bool hit = (~v & cw & (y0r + u * RP + ly - H)) < 0;
-        const uint64_t m = __ballot(hit);
-        if (hit) list[n + lane_rank(m)] = (uint16_t)(eb + u * RP * S);
-        n += __popcll(m);
+        // min/max on the raw bytes, one difference per polarity (within -255 .. 255)
+        const u16x2 hi = __builtin_elementwise_min(__builtin_elementwise_max(c0[p], c8[p]),
+                                                   __builtin_elementwise_max(c4[p], c12[p]));
+        const u16x2 lo = __builtin_elementwise_max(__builtin_elementwise_min(c0[p], c8[p]),
+                                                   __builtin_elementwise_min(c4[p], c12[p]));
+        const s16x2 d = __builtin_elementwise_max(__builtin_bit_cast(s16x2, hi - cv[p]),
+                                                  __builtin_bit_cast(s16x2, cv[p] - lo));  // > th <=> compass hit
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+          const int u = 2 * p + h;
+          if (!full && u >= nu) break;
+          // the hit mask is the compare's own scalar pair and-ed with the cell's lane mask, once as the
+          // ballot and once as the branch condition (no vector instruction either way)
+          const bool over = d[h] > th;
+          const uint64_t overm = ballot64(over);  // taken beside the compare: in a later block it is rebuilt
+          auto compact = [&](bool ok, uint64_t okm) {
+            const uint64_t m = overm & okm;
+            if (over && ok) list[n + lane_rank(m)] = (uint16_t)(eb + u * RP * S);
+            n += __popcll(m);
+          };
+          // lane inside the region: every row of a full trip is; the peeled trip's last sub-step
+          // may have only its first row inside (RP = 2, a wave-uniform branch)
+          if (full || RP == 1 || y0r + u * RP + RP <= H) compact(col_ok, colm);
+          else compact(col_ok0, colm0);
+        }
       }
     };
     int y0r = 0;
@@ -970,12 +1012,13 @@ __global__ __launch_bounds__(64) void k_fast(const Geometry* __restrict__ G, con
     for (int i0 = 0; i0 < n; i0 += 64) {
       const int i = i0 + lane;
       int e = 0, sc1 = 0;
-      bool corner = false;
       if (i < n) {
         e = list[i];
         sc1 = ring_score1<S>(tile + e);
-        corner = sc1 > th;
       }
+      // outside the branch, so the ballot is the compare's own mask (a flag set inside comes out
+      // of it as a v_cndmask and goes into the ballot through a v_cmp_ne); an idle lane has sc1 = 0 <= th
+      const bool corner = sc1 > th;
 #ifdef ORBX_FAST_PROBE
       if (th == ini) n_even8 += __popcll(__ballot(i < n && even8_test<S>(tile + e, th)));
 #endif
@@ -991,16 +1034,19 @@ __global__ __launch_bounds__(64) void k_fast(const Geometry* __restrict__ G, con
     return nc;
   };
   // strict NMS inside the region; the map's zero border stands for "outside"
-  auto keep = [&](int e, int thr) -> bool {  // thr = t + 1 in map units (S + 1)
-    const uint8_t* m = smap + e;              // centre at m[S + 1]
-    const int s = m[S + 1];
+  auto ring8_max = [&](int e) -> int {  // the largest of the eight neighbours' map values
+    const uint8_t* m = smap + e;        // centre at m[S + 1]
     const int n0 = m[0], n1 = m[1], n2 = m[2], n3 = m[S], n4 = m[S + 2], n5 = m[2 * S], n6 = m[2 * S + 1],
               n7 = m[2 * S + 2];
-    // a neighbour beats the centre iff nv >= thr and nv >= s: one max over the eight
-    const int mx = max(max(max(n0, n1), max(n2, n3)), max(max(n4, n5), max(n6, n7)));
-    const bool lost = mx >= max(thr, s);
-    return s >= thr && s > 1 && !lost;
+    return max(max(max(n0, n1), max(n2, n3)), max(max(n4, n5), max(n6, n7)));
   };
+  auto kept = [](int s, int mx, int thr) -> bool {  // thr = t + 1 in map units (S + 1)
+    // a neighbour beats the centre iff nv >= thr and nv >= s, so with mx the largest of the eight the
+    // centre stays iff s >= thr && s > 1 && !(mx >= max(thr, s)).  Where s >= thr that maximum is s,
+    // which leaves s >= max(thr, 2) && s >= mx + 1: ONE compare, whose mask the ballots take as it is
+    return s >= max(mx + 1, max(thr, 2));
+  };
+  auto keep = [&](int e, int thr) -> bool { return kept(smap[e + S + 1], ring8_max(e), thr); };
   // FAST at iniThFAST only (src/ORBextractor.cc:892): the map then holds exactly the corners at
   // iniThFAST, which is all NMS at iniThFAST looks at (a weaker neighbour never beats a centre)
   FAST_TS(1);
@@ -1013,13 +1059,17 @@ __global__ __launch_bounds__(64) void k_fast(const Geometry* __restrict__ G, con
   int cnt = 0;
   for (int i0 = 0; i0 < nc; i0 += 64) {
     const int i = i0 + lane;
-    bool k = false;
+    int e = 0, s = 0, mx = 0;
     if (i < nc) {
-      const int e = list[i];
-      k = keep(e, ini + 1);
-      if (k) list[i] = (uint16_t)(e | 0x8000);
+      e = list[i];
+      s = smap[e + S + 1];
+      mx = ring8_max(e);
     }
-    cnt += __popcll(__ballot(k));
+    // the verdict outside the branch, as in detect(): an idle lane has s = 0 and is not kept
+    const bool k = kept(s, mx, ini + 1);
+    const uint64_t km = ballot64(k);
+    if (k) list[i] = (uint16_t)(e | 0x8000);
+    cnt += __popcll(km);
   }
   // an empty cell runs FAST(window, minThFAST) (src/ORBextractor.cc:894-900): a wave-uniform
   // second pass, taken by ~10 % of the cells on the bench images

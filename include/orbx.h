@@ -24,6 +24,12 @@
  *   orbx_stereo_frames_device   extract(L)+extract(R)+ComputeStereoMatches for n stereo frames
  *   orbx_frame_stereo           the ORB part of Frame's stereo constructor: ExtractORB(0/1) on two
  *                               threads + ComputeStereoMatches  src/Frame.cc:62-123 (:80-84, :121)
+ *   orbx_cvt_gray[_device]      cv::cvtColor(.., CV_RGB2GRAY / BGR / RGBA / BGRA) of Tracking::GrabImage*
+ *                                                               src/Tracking.cc:174-199, 215-228, 246-259
+ *   orbx_frame_rgbd             the ORB part of Frame's RGB-D constructor + GrabImageRGBD's preprocessing:
+ *                               cvtColor, convertTo, ExtractORB(0), UndistortKeyPoints, ComputeStereoFromRGBD
+ *                                                               src/Frame.cc:126-183, 791-816, src/Tracking.cc:210-233
+ *   orbx_rgbd_frames_device     the same for n RGB-D frames on the device
  *   orbx_descriptor_distance_device
  *                               ORBmatcher::DescriptorDistance  src/ORBmatcher.cc:1844-1860, include/ORBmatcher.h:50
  *   orbx_search_by_bow_kf_f     ORBmatcher::SearchByBoW(KeyFrame*, Frame&, vector<MapPoint*>&)
@@ -1226,6 +1232,78 @@ orbx_status orbx_undistort_keypoints(const orbx_keypoint* keys, int n, const orb
 orbx_status orbx_undistort_keypoints_device(const orbx_keypoint* keys, const int32_t* frame_off, int n_frames,
                                             int max_keys, const orbx_camera* cams, orbx_keypoint* keys_un,
                                             void* stream);
+
+/* ---------------------------------------------------------------- RGB-D front end
+ * cv::cvtColor(src, dst, CV_RGB2GRAY / CV_BGR2GRAY / CV_RGBA2GRAY / CV_BGRA2GRAY) on 8-bit images, the
+ * first statements of Tracking::GrabImageStereo / GrabImageRGBD / GrabImageMonocular
+ * (src/Tracking.cc:174-199, 215-228, 246-259), as OpenCV 3.2's RGB2Gray<uchar> computes it:
+ * Y = (R*4899 + G*9617 + B*1868 + 8192) >> 14, alpha ignored.  rgb != 0: byte 0 of a pixel is R (mbRGB);
+ * rgb == 0: byte 2 is.  n_images images of width x height pixels with `channels` (3 or 4) bytes each: row y
+ * of image i starts at src + i*src_image_pitch + y*src_pitch and its grey row at dst + i*dst_image_pitch +
+ * y*dst_pitch (bytes; any alignment; bytes of dst outside the rows are not written).  channels == 1 is
+ * ORBX_ERR_ARG (the reference does not call cvtColor then), as are pitches smaller than a row.
+ * Host pointers, synchronous. */
+orbx_status orbx_cvt_gray(const uint8_t* src, size_t src_pitch, size_t src_image_pitch, int n_images, int width,
+                          int height, int channels, int rgb, uint8_t* dst, size_t dst_pitch, size_t dst_image_pitch,
+                          int device);
+/* The same on device pointers, asynchronous on `stream` (NULL = the handle's own; ORBX_STREAM_NULL = the
+ * device's legacy null stream), as orbx_extract_batch_device.  The kernel reads the source with aligned
+ * 4-byte loads: of the 4-byte words at the two ends of a row it may read bytes that are not the row's. */
+orbx_status orbx_cvt_gray_device(orbx_extractor* h, const uint8_t* d_src, size_t src_pitch, size_t src_image_pitch,
+                                 int n_images, int width, int height, int channels, int rgb, uint8_t* d_dst,
+                                 size_t dst_pitch, size_t dst_image_pitch, void* stream);
+
+/* depth image element types (OpenCV's depth codes) */
+#define ORBX_DEPTH_U16 2 /* CV_16U */
+#define ORBX_DEPTH_F32 5 /* CV_32F */
+
+/* The ORB part of Frame's RGB-D constructor (src/Frame.cc:126-183: ExtractORB(0, imGray),
+ * UndistortKeyPoints, ComputeStereoFromRGBD :791-816) with Tracking::GrabImageRGBD's preprocessing
+ * (src/Tracking.cc:210-233: cvtColor, imDepth.convertTo(CV_32F, mDepthMapFactor)) in one call: host images in,
+ * host results out, one upload, one copy back, one synchronisation.
+ *   img          width x height pixels of `channels` (1, 3 or 4) bytes, rows `stride` bytes apart; rgb as above
+ *   depth        depth_width x depth_height elements of depth_type, rows depth_stride bytes apart (a multiple
+ *                of the element size; the pointer aligned to it)
+ *   depth_factor mDepthMapFactor as Tracking holds it, i.e. already inverted (src/Tracking.cc:144-148)
+ *   cam, bf      mK / mDistCoef and mbf
+ * Per keypoint i (of *n): kps[i] / desc are those of orbx_extract on the grey image; kps_un[i] that of
+ * orbx_undistort_keypoints; with d the depth under the DISTORTED keypoint, at row (int)kps[i].y and column
+ * (int)kps[i].x, converted as the reference converts the image -- ORBX_DEPTH_U16: d = (float)raw *
+ * depth_factor, always (the type is not CV_32F); ORBX_DEPTH_F32: d = raw * depth_factor when
+ * fabs(depth_factor - 1.0f) > 1e-5, else raw -- depth[i] = d and uRight[i] = kps_un[i].x - bf / d when d > 0,
+ * else both -1 (zero, negative and NaN depths; +inf gives uRight = kps_un[i].x).  The depth image is only
+ * read under the keypoints; no float image is made.
+ * An empty image (img NULL, width or height <= 0) returns ORBX_OK with *n = 0.  ORBX_ERR_ARG: a depth image
+ * of another size than the image, a depth type other than the two above, channels other than 1, 3, 4.
+ * ORBX_ERR_STATE: a keypoint indexed the depth image out of bounds (cannot happen with this extractor's
+ * keypoints; such a keypoint is never read and gets -1).  Any output pointer but n may be NULL.
+ * Afterwards orbx_pyramid_level(h, 0, l, ...) reads the pyramid of the grey image, and h's last extraction
+ * is no longer an orbx_extract result (orbx_stereo_match on it returns ORBX_ERR_STATE). */
+orbx_status orbx_frame_rgbd(orbx_extractor* h, const uint8_t* img, size_t stride, int width, int height,
+                            int channels, int rgb, const void* depth, size_t depth_stride, int depth_width,
+                            int depth_height, int depth_type, float depth_factor, const orbx_camera* cam, float bf,
+                            orbx_keypoint* kps, uint8_t* desc, int cap, int* n, orbx_keypoint* kps_un,
+                            float* uRight, float* depth_out);
+
+/* Device-resident RGB-D frames, the sibling of orbx_stereo_frames_device: frame f's image (channels 1, 3
+ * or 4) has its row y at d_images + f*image_pitch + y*row_pitch and its depth row y at d_depth +
+ * f*depth_image_pitch + y*depth_row_pitch (bytes).  With channels == 1 the images are the pyramid's level 0
+ * themselves, so row_pitch must equal width, as in orbx_extract_batch_device.  With channels > 1 the grey
+ * images go into a buffer the handle owns, which is then level 0 of the batch's pyramid: it stays valid
+ * (for orbx_pyramid_level, orbx_debug_copy) until the next call on the handle that extracts, and the handle
+ * must outlive the stream's work.  One camera and one bf for the batch (cam is a host pointer, read before
+ * the call returns).  Per frame f: d_counts[f] keypoints at d_kps + f*kp_capacity, descriptors at d_desc +
+ * f*kp_capacity*32, undistorted keypoints at d_kps_un + f*kp_capacity; d_uright / d_depth_out +
+ * f*kp_capacity as above; d_nmatches[f] = the keypoints with d > 0.  Slots beyond d_counts[f] are not
+ * written, as orbx_stereo_frames_device leaves them: what consumes a stereo batch's left side takes this
+ * one (with image step 1 instead of 2).  Asynchronous on `stream`; inputs must stay alive until it
+ * completes. */
+orbx_status orbx_rgbd_frames_device(orbx_extractor* h, int n_frames, const uint8_t* d_images, int width, int height,
+                                    int channels, int rgb, size_t row_pitch, size_t image_pitch, const void* d_depth,
+                                    int depth_type, size_t depth_row_pitch, size_t depth_image_pitch,
+                                    float depth_factor, const orbx_camera* cam, float bf, orbx_keypoint* d_kps,
+                                    uint8_t* d_desc, int32_t* d_counts, int kp_capacity, orbx_keypoint* d_kps_un,
+                                    float* d_uright, float* d_depth_out, int32_t* d_nmatches, void* stream);
 
 /* Per-stage HIP-event timers (the g2o G2OBatchStatistics analogue,
  * Thirdparty/g2o/g2o/core/batch_stats.h:38-79).  When enabled, every kernel

@@ -20,6 +20,8 @@ ORBX_ERR_HIP = -3
 ORBX_ERR_NODEV = -4
 ORBX_ERR_SIZE = -5
 ORBX_ERR_STATE = -6
+ORBX_DEPTH_U16 = 2  # CV_16U
+ORBX_DEPTH_F32 = 5  # CV_32F
 _ERRS = {ORBX_ERR_ARG: "bad argument", ORBX_ERR_CAPACITY: "capacity", ORBX_ERR_HIP: "HIP runtime error",
          ORBX_ERR_NODEV: "no HIP device", ORBX_ERR_SIZE: "unsupported geometry", ORBX_ERR_STATE: "no extraction yet"}
 
@@ -255,6 +257,16 @@ SIGNATURES = {
                            P, P, C.c_int, P, P, P], C.c_int),
     "orbx_stereo_frames_device": ([P, C.c_int, P, C.c_int, C.c_int, C.c_size_t, P, P, P, C.c_int, C.c_float,
                                    C.c_float, P, P, P, P], C.c_int),
+    "orbx_cvt_gray": ([P, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, C.c_size_t,
+                       C.c_size_t, C.c_int], C.c_int),
+    "orbx_cvt_gray_device": ([P, P, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P,
+                              C.c_size_t, C.c_size_t, P], C.c_int),
+    "orbx_frame_rgbd": ([P, P, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, P, C.c_size_t, C.c_int, C.c_int,
+                         C.c_int, C.c_float, C.POINTER(Camera), C.c_float, P, P, C.c_int, C.POINTER(C.c_int), P, P,
+                         P], C.c_int),
+    "orbx_rgbd_frames_device": ([P, C.c_int, P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, P,
+                                 C.c_int, C.c_size_t, C.c_size_t, C.c_float, C.POINTER(Camera), C.c_float, P, P, P,
+                                 C.c_int, P, P, P, P, P], C.c_int),
     "orbx_descriptor_distance_device": ([P, P, C.c_int, P, P], C.c_int),
     "orbx_search_by_bow_kf_f": ([C.POINTER(BowSide), C.POINTER(BowSide), C.c_float, C.c_int, P,
                                  C.POINTER(C.c_int), C.c_int], C.c_int),

@@ -24,6 +24,8 @@
 #include "orbx_stereo.h"
 #include "orbx_prof.h"
 #include "orbx_bow.h"
+#include "orbx_rgbd.h"
+#include "orbx_undistort.h"
 
 namespace orbx {
 hipError_t upload_constants(const int* umax16, const int* gauss7);
@@ -547,6 +549,10 @@ struct orbx_extractor {
   DevBuf<int> oct_start, sad;
   DevBuf<float> sres;  // orbx_stereo_match: uRight | depth, adjacent (one copy back)
   DevBuf<int32_t> nmatch;
+  // RGB-D: orbx_frame_rgbd's upload [image | depth image]; the out-of-image counters of a device batch.
+  // (The grey images of a colour input go into `in`: level 0 of that call's pyramid.)
+  DevBuf<uint8_t> rgbd_in;
+  DevBuf<int32_t> rgbd_oob;
   StageTimer timer;
   // last batch (mvImagePyramid)
   Plan* last_plan = nullptr;
@@ -1106,6 +1112,242 @@ orbx_status orbx_stereo_frames_device(orbx_extractor* h, int n_frames, const uin
   return run_stereo(h, h, n_frames, d_kps, d_desc, d_counts, 2 * kc, 2, d_kps + kc, d_desc + kc * 32, d_counts + 1,
                     2 * kc, 2, 2, 0, 2, 1, h->last_plan->G.max_kps, bf, baseline, d_uright, d_depth, kc,
                     d_nmatches, pick_stream(h, stream));
+}
+
+// ------------------------------------------------------------------ RGB-D front end (kernels: rgbd.hip)
+namespace {
+
+// src/Tracking.cc:230: `fabs(mDepthMapFactor-1.0f)>1e-5`, a float subtraction then a double comparison
+bool depth_factor_applies(float factor) { return (double)std::fabs(factor - 1.0f) > 1e-5; }
+
+size_t depth_elem(int type) { return type == ORBX_DEPTH_U16 ? 2 : type == ORBX_DEPTH_F32 ? 4 : 0; }
+
+// bytes from the first byte of image 0 to the last byte of the last row of image n - 1
+size_t span_bytes(size_t row_bytes, size_t pitch, int h, size_t image_pitch, int n) {
+  return (size_t)(n - 1) * image_pitch + (size_t)(h - 1) * pitch + row_bytes;
+}
+
+orbx_status cvt_gray_check(const void* src, size_t sp, size_t sip, int n, int w, int h, int ch, const void* dst,
+                           size_t dp, size_t dip) {
+  if (ch != 3 && ch != 4) return ORBX_ERR_ARG;  // 1: the reference does not call cvtColor
+  if (n < 0 || w < 0 || h < 0) return ORBX_ERR_ARG;
+  if (n == 0 || w == 0 || h == 0) return ORBX_OK;
+  if (!src || !dst || sp < (size_t)ch * w || dp < (size_t)w) return ORBX_ERR_ARG;
+  if (n > 1 && (sip < span_bytes((size_t)ch * w, sp, h, 0, 1) || dip < span_bytes((size_t)w, dp, h, 0, 1)))
+    return ORBX_ERR_ARG;
+  if (n > 65535 || h > 4 * 65535) return ORBX_ERR_SIZE;  // k_cvt_gray's grid
+  return ORBX_OK;
+}
+
+CvtGrayArgs cvt_gray_args(const uint8_t* src, size_t sp, size_t sip, int n, int w, int h, int rgb, uint8_t* dst,
+                          size_t dp, size_t dip) {
+  CvtGrayArgs A;
+  A.src = src;
+  A.dst = dst;
+  A.src_pitch = (long long)sp;
+  A.src_image_pitch = (long long)sip;
+  A.dst_pitch = (long long)dp;
+  A.dst_image_pitch = (long long)dip;
+  A.w = w;
+  A.h = h;
+  A.n = n;
+  A.c0 = rgb ? kR2Y : kB2Y;
+  A.c2 = rgb ? kB2Y : kR2Y;
+  return A;
+}
+
+// k_rgbd_finish behind an extraction of n_frames images through h (kps at stride kc, counts at stride 1)
+orbx_status run_rgbd_finish(int n_frames, const orbx_keypoint* d_kps, const int32_t* d_counts, long long kc, int max_k,
+                            const orbx_camera& cam, const uint8_t* d_depth, size_t depth_pitch,
+                            size_t depth_image_pitch, int depth_type, float factor, float bf, int w, int h,
+                            orbx_keypoint* d_kps_un, float* d_ur, float* d_dep, int32_t* d_nm, int32_t* d_oob,
+                            hipStream_t st) {
+  RgbdFinishArgs A;
+  std::memset(&A, 0, sizeof(A));
+  A.kps = d_kps;
+  A.counts = d_counts;
+  A.k_stride = kc;
+  A.n_stride = 1;
+  A.max_k = max_k;
+  A.cam = cam;
+  A.depth = d_depth;
+  A.depth_pitch = (long long)depth_pitch;
+  A.depth_image_pitch = (long long)depth_image_pitch;
+  A.depth_type = depth_type;
+  A.scale = depth_factor_applies(factor) ? 1 : 0;
+  A.factor = factor;
+  A.bf = bf;
+  A.w = w;
+  A.h = h;
+  A.kps_un = d_kps_un;
+  A.uR = d_ur;
+  A.dep = d_dep;
+  A.out_stride = kc;
+  A.nmatches = d_nm;
+  A.n_oob = d_oob;
+  return hip_status(launch_rgbd_finish(A, n_frames, st));
+}
+
+}  // namespace
+
+orbx_status orbx_cvt_gray_device(orbx_extractor* h, const uint8_t* d_src, size_t src_pitch, size_t src_image_pitch,
+                                 int n_images, int width, int height, int channels, int rgb, uint8_t* d_dst,
+                                 size_t dst_pitch, size_t dst_image_pitch, void* stream) {
+  if (!h) return ORBX_ERR_ARG;
+  const orbx_status s =
+      cvt_gray_check(d_src, src_pitch, src_image_pitch, n_images, width, height, channels, d_dst, dst_pitch, dst_image_pitch);
+  if (s != ORBX_OK || n_images == 0 || width == 0 || height == 0) return s;
+  if (hipSetDevice(h->device) != hipSuccess) return ORBX_ERR_HIP;
+  return hip_status(launch_cvt_gray(cvt_gray_args(d_src, src_pitch, src_image_pitch, n_images, width, height, rgb,
+                                                  d_dst, dst_pitch, dst_image_pitch),
+                                    channels, pick_stream(h, stream)));
+}
+
+orbx_status orbx_cvt_gray(const uint8_t* src, size_t src_pitch, size_t src_image_pitch, int n_images, int width,
+                          int height, int channels, int rgb, uint8_t* dst, size_t dst_pitch, size_t dst_image_pitch,
+                          int device) {
+  const orbx_status s =
+      cvt_gray_check(src, src_pitch, src_image_pitch, n_images, width, height, channels, dst, dst_pitch, dst_image_pitch);
+  if (s != ORBX_OK || n_images == 0 || width == 0 || height == 0) return s;
+  const orbx_status dv = orbx::select_device(device);
+  if (dv != ORBX_OK) return dv;
+  // rows packed back to back on both sides of PCIe: the caller's padding is neither read nor written
+  using orbx::Staging;
+  const size_t srow = (size_t)channels * width, drow = (size_t)width;
+  Staging S(device);
+  const auto s_src = S.in<uint8_t>(nullptr, srow * height * n_images);
+  const auto s_dst = S.out<uint8_t>(drow * height * n_images);
+  const orbx_status cs = S.commit();
+  if (cs != ORBX_OK) return cs;
+  for (int i = 0; i < n_images; i++)
+    for (int y = 0; y < height; y++)
+      std::memcpy(S.host(s_src) + ((size_t)i * height + y) * srow, src + (size_t)i * src_image_pitch + (size_t)y * src_pitch,
+                  srow);
+  hipError_t e = S.upload(Staging::Outputs::skipped);
+  if (e == hipSuccess)
+    e = launch_cvt_gray(cvt_gray_args(S.dev(s_src), srow, srow * height, n_images, width, height, rgb, S.dev(s_dst), drow,
+                                      drow * height),
+                        channels, S.stream());
+  if (e == hipSuccess) e = S.download();
+  if (e == hipSuccess) e = S.sync();
+  if (e != hipSuccess) return ORBX_ERR_HIP;
+  for (int i = 0; i < n_images; i++)
+    for (int y = 0; y < height; y++)
+      std::memcpy(dst + (size_t)i * dst_image_pitch + (size_t)y * dst_pitch, S.host(s_dst) + ((size_t)i * height + y) * drow,
+                  drow);
+  return ORBX_OK;
+}
+
+orbx_status orbx_frame_rgbd(orbx_extractor* h, const uint8_t* img, size_t stride, int width, int height,
+                            int channels, int rgb, const void* depth, size_t depth_stride, int depth_width,
+                            int depth_height, int depth_type, float depth_factor, const orbx_camera* cam, float bf,
+                            orbx_keypoint* kps, uint8_t* desc, int cap, int* n, orbx_keypoint* kps_un,
+                            float* uRight, float* depth_out) {
+  if (!h || !n) return ORBX_ERR_ARG;
+  *n = 0;
+  if (!img || width <= 0 || height <= 0) return ORBX_OK;  // src/ORBextractor.cc:1141, src/Frame.cc:147-148
+  const size_t es = depth_elem(depth_type);
+  if ((channels != 1 && channels != 3 && channels != 4) || es == 0 || !cam || !camera_ok(*cam)) return ORBX_ERR_ARG;
+  if (!depth || depth_width != width || depth_height != height) return ORBX_ERR_ARG;
+  const size_t irow = (size_t)channels * width, drow = es * width;
+  if (stride < irow || depth_stride < drow || depth_stride % es || (uintptr_t)depth % es) return ORBX_ERR_ARG;
+  if (hipSetDevice(h->device) != hipSuccess) return ORBX_ERR_HIP;
+  Plan* P = nullptr;
+  orbx_status s = get_plan(h, width, height, &P);
+  if (s != ORBX_OK) return s;
+  const int kc = P->G.max_kps;
+  const size_t npx = (size_t)width * height;
+  // upload block: image rows packed | depth rows packed.  Device output block: count, depth count,
+  // out-of-image count | keypoints | undistorted keypoints | descriptors | uRight | depth -- one copy back
+  const size_t i_dep = scratch_align(irow * height), i_end = i_dep + drow * height;
+  const size_t o_kps = 256, o_un = o_kps + scratch_align((size_t)kc * sizeof(orbx_keypoint)),
+               o_desc = o_un + scratch_align((size_t)kc * sizeof(orbx_keypoint)), o_ur = o_desc + (size_t)kc * 32,
+               o_dep = o_ur + (size_t)kc * 4, o_end = o_dep + (size_t)kc * 4;
+  hipError_t e = hipSuccess;
+  auto chk = [&](hipError_t x) { if (x != hipSuccess) e = x; };
+  chk(h->rgbd_in.ensure(i_end + kInSlack));
+  if (channels > 1) chk(h->in.ensure(npx + kInSlack));
+  chk(h->out.ensure(o_end));
+  chk(h->ensure_stage(std::max(i_end, o_end)));
+  if (e != hipSuccess) return ORBX_ERR_HIP;
+  hipStream_t st = h->stream;
+  uint8_t* hs = h->hstage;
+  for (int y = 0; y < height; y++) std::memcpy(hs + (size_t)y * irow, img + (size_t)y * stride, irow);
+  for (int y = 0; y < height; y++)
+    std::memcpy(hs + i_dep + (size_t)y * drow, (const uint8_t*)depth + (size_t)y * depth_stride, drow);
+  if (hipMemcpyAsync(h->rgbd_in.p, hs, i_end, hipMemcpyHostToDevice, st) != hipSuccess) return ORBX_ERR_HIP;
+  const uint8_t* d_gray = h->rgbd_in.p;  // a grey input is level 0 as uploaded
+  if (channels > 1) {
+    if (launch_cvt_gray(cvt_gray_args(h->rgbd_in.p, irow, irow * height, 1, width, height, rgb, h->in.p, width, npx),
+                        channels, st) != hipSuccess)
+      return ORBX_ERR_HIP;
+    d_gray = h->in.p;
+  }
+  int32_t* d_counts = (int32_t*)h->out.p;
+  orbx_keypoint* d_kps = (orbx_keypoint*)(h->out.p + o_kps);
+  orbx_keypoint* d_un = (orbx_keypoint*)(h->out.p + o_un);
+  uint8_t* d_desc = h->out.p + o_desc;
+  s = run_extract(h, P, 1, d_gray, npx, d_kps, d_desc, d_counts, kc, st);
+  if (s != ORBX_OK) return s;
+  s = run_rgbd_finish(1, d_kps, d_counts, kc, kc, *cam, h->rgbd_in.p + i_dep, drow, drow * height, depth_type,
+                      depth_factor, bf, width, height, d_un, (float*)(h->out.p + o_ur), (float*)(h->out.p + o_dep),
+                      d_counts + 1, d_counts + 2, st);
+  if (s != ORBX_OK) return s;
+  chk(hipMemcpyAsync(hs, h->out.p, o_end, hipMemcpyDeviceToHost, st));
+  chk(hipStreamSynchronize(st));
+  if (e != hipSuccess) return ORBX_ERR_HIP;
+  const int32_t cnt = ((const int32_t*)hs)[0], oob = ((const int32_t*)hs)[2];
+  *n = cnt;
+  if (cnt > cap) return ORBX_ERR_CAPACITY;
+  if (cnt > 0) {
+    if (kps) std::memcpy(kps, hs + o_kps, sizeof(orbx_keypoint) * cnt);
+    if (kps_un) std::memcpy(kps_un, hs + o_un, sizeof(orbx_keypoint) * cnt);
+    if (desc) std::memcpy(desc, hs + o_desc, (size_t)32 * cnt);
+    if (uRight) std::memcpy(uRight, hs + o_ur, sizeof(float) * cnt);
+    if (depth_out) std::memcpy(depth_out, hs + o_dep, sizeof(float) * cnt);
+  }
+  return oob != 0 ? ORBX_ERR_STATE : ORBX_OK;
+}
+
+orbx_status orbx_rgbd_frames_device(orbx_extractor* h, int n_frames, const uint8_t* d_images, int width, int height,
+                                    int channels, int rgb, size_t row_pitch, size_t image_pitch, const void* d_depth,
+                                    int depth_type, size_t depth_row_pitch, size_t depth_image_pitch,
+                                    float depth_factor, const orbx_camera* cam, float bf, orbx_keypoint* d_kps,
+                                    uint8_t* d_desc, int32_t* d_counts, int kp_capacity, orbx_keypoint* d_kps_un,
+                                    float* d_uright, float* d_depth_out, int32_t* d_nmatches, void* stream) {
+  if (!h || n_frames < 0 || !d_kps || !d_desc || !d_counts || !d_kps_un || !d_uright || !d_depth_out || !d_nmatches)
+    return ORBX_ERR_ARG;
+  if (n_frames == 0) return ORBX_OK;
+  const size_t es = depth_elem(depth_type);
+  if ((channels != 1 && channels != 3 && channels != 4) || es == 0 || !cam || !camera_ok(*cam)) return ORBX_ERR_ARG;
+  if (!d_images || !d_depth || width <= 0 || height <= 0) return ORBX_ERR_ARG;
+  const size_t irow = (size_t)channels * width, drow = es * width, npx = (size_t)width * height;
+  if (row_pitch < irow || (channels == 1 && row_pitch != irow) || image_pitch < span_bytes(irow, row_pitch, height, 0, 1))
+    return ORBX_ERR_ARG;
+  if (depth_row_pitch < drow || depth_row_pitch % es || depth_image_pitch % es || (uintptr_t)d_depth % es ||
+      depth_image_pitch < span_bytes(drow, depth_row_pitch, height, 0, 1))
+    return ORBX_ERR_ARG;
+  if (hipSetDevice(h->device) != hipSuccess) return ORBX_ERR_HIP;
+  hipStream_t st = pick_stream(h, stream);
+  const uint8_t* d_gray = d_images;
+  size_t gray_pitch = image_pitch;
+  if (channels > 1) {
+    const orbx_status cs = cvt_gray_check(d_images, row_pitch, image_pitch, n_frames, width, height, channels, d_images, width, npx);
+    if (cs != ORBX_OK) return cs;
+    if (h->in.ensure(npx * n_frames + kInSlack) != hipSuccess) return ORBX_ERR_HIP;
+    if (launch_cvt_gray(cvt_gray_args(d_images, row_pitch, image_pitch, n_frames, width, height, rgb, h->in.p, width, npx),
+                        channels, st) != hipSuccess)
+      return ORBX_ERR_HIP;
+    d_gray = h->in.p;
+    gray_pitch = npx;
+  }
+  if (h->rgbd_oob.ensure((size_t)n_frames) != hipSuccess) return ORBX_ERR_HIP;
+  orbx_status s = orbx_extract_batch_device(h, n_frames, d_gray, width, height, gray_pitch, d_kps, d_desc, d_counts,
+                                            kp_capacity, stream);
+  if (s != ORBX_OK) return s;
+  return run_rgbd_finish(n_frames, d_kps, d_counts, kp_capacity, h->last_plan->G.max_kps, *cam, (const uint8_t*)d_depth,
+                         depth_row_pitch, depth_image_pitch, depth_type, depth_factor, bf, width, height, d_kps_un,
+                         d_uright, d_depth_out, d_nmatches, h->rgbd_oob.p, st);
 }
 
 static orbx_status bow_host(const orbx_bow_side* A, const orbx_bow_side* B, float nnratio, int check_ori, int mode,

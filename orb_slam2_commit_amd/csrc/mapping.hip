@@ -16,9 +16,8 @@
 // first row on ties, as the reference's strict `median < BestMedian`.
 // Bytes per point: 32 N read (L1/K$-resident after the first pass), 36 written.
 //
-// k_undistort: one thread per keypoint, all FP64 in cvUndistortPoints'
-// operation order (-ffp-contract=off; AMDGPU f64 division is correctly
-// rounded), so keys_un equals the oracle bit for bit.  28 B read + 28 B
+// k_undistort: one thread per keypoint over undistort_keypoint (orbx_undistort.h: all FP64 in
+// cvUndistortPoints' operation order), so keys_un equals the oracle bit for bit.  28 B read + 28 B
 // written per keypoint: HBM-bound when batched.
 #include <hip/hip_runtime.h>
 
@@ -29,6 +28,7 @@
 #include "orbx_scratch.h"
 #include "orbx_device.h"
 #include "orbx_internal.h"
+#include "orbx_undistort.h"
 
 namespace orbx {
 namespace mapping {
@@ -89,33 +89,7 @@ __global__ __launch_bounds__(UBS) void k_undistort(const orbx_keypoint* __restri
   if (i >= n) return;
   orbx_keypoint kp = keys[a + i];
   const orbx_camera& cam = cams[f];
-  if (cam.dist[0] != 0.0f) {  // mDistCoef.at<float>(0)==0.0: plain copy (src/Frame.cc:474-478)
-    double kc[5] = {0, 0, 0, 0, 0};
-#pragma unroll
-    for (int j = 0; j < 5; j++)
-      if (j < cam.n_dist) kc[j] = cam.dist[j];
-    double A[9];
-#pragma unroll
-    for (int j = 0; j < 9; j++) A[j] = cam.K[j];
-    const double ifx = 1. / A[0], ify = 1. / A[4], cx = A[2], cy = A[5];
-    double x = kp.x, y = kp.y;
-    const double x0 = x = (x - cx) * ifx;
-    const double y0 = y = (y - cy) * ify;
-#pragma unroll
-    for (int it = 0; it < 5; it++) {  // cvUndistortPoints: iters = 5 with distortion
-      const double r2 = x * x + y * y;
-      const double icdist = 1 / (1 + ((kc[4] * r2 + kc[1]) * r2 + kc[0]) * r2);
-      const double deltaX = 2 * kc[2] * x * y + kc[3] * (r2 + 2 * x * x);
-      const double deltaY = kc[2] * (r2 + 2 * y * y) + 2 * kc[3] * x * y;
-      x = (x0 - deltaX) * icdist;
-      y = (y0 - deltaY) * icdist;
-    }
-    const double xx = A[0] * x + A[1] * y + A[2];
-    const double yy = A[3] * x + A[4] * y + A[5];
-    const double ww = 1. / (A[6] * x + A[7] * y + A[8]);
-    kp.x = (float)(xx * ww);
-    kp.y = (float)(yy * ww);
-  }
+  undistort_keypoint(cam, kp);  // a plain copy when mDistCoef.at<float>(0)==0.0 (src/Frame.cc:474-478)
   keys_un[a + i] = kp;
 }
 
@@ -123,11 +97,7 @@ __global__ __launch_bounds__(UBS) void k_undistort(const orbx_keypoint* __restri
 }  // namespace orbx
 
 // ------------------------------------------------------------------ C ABI
-namespace {
-
-bool camera_ok(const orbx_camera& c) { return c.n_dist >= 4 && c.n_dist <= 5 && c.K[0] != 0.0f && c.K[4] != 0.0f; }
-
-}  // namespace
+using orbx::camera_ok;
 
 extern "C" orbx_status orbx_distinctive_descriptors_device(const uint8_t* desc, const int32_t* obs_off, int n_points,
                                                            int32_t* best, uint8_t* out_desc, void* stream) {

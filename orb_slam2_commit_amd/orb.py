@@ -227,6 +227,89 @@ def frame_stereo(extractor, image_left, image_right, bf, baseline):
             uR[:nL].copy(), depth[:nL].copy())
 
 
+def cvt_gray(image, rgb, device=0):
+    """cv::cvtColor(image, gray, CV_RGB2GRAY / CV_BGR2GRAY / CV_RGBA2GRAY / CV_BGRA2GRAY), the first statements
+    of Tracking::GrabImage* (src/Tracking.cc:174-199, 215-228, 246-259).  image: uint8 [H, W, 3 or 4] or a batch
+    [n, H, W, 3 or 4] (row and image strides are the array's own; a pixel's bytes adjacent); rgb: mbRGB.
+    Returns uint8 [H, W] or [n, H, W]."""
+    a = np.asarray(image)
+    assert a.dtype == np.uint8 and a.ndim in (3, 4), "image must be CV_8UC3 / CV_8UC4 (or a batch of them)"
+    b = a if a.ndim == 4 else a[None]
+    n, h, w, c = b.shape
+    if b.size and (b.strides[3] != 1 or b.strides[2] != c or b.strides[1] < w * c or
+                   (n > 1 and b.strides[0] < (h - 1) * b.strides[1] + w * c)):
+        b = np.ascontiguousarray(b)
+    out = np.zeros((n, h, w), np.uint8)
+    check(_lib.lib().orbx_cvt_gray(ptr(b), b.strides[1], b.strides[0], n, w, h, c, int(bool(rgb)), ptr(out), w,
+                                   w * h, int(device)), "orbx_cvt_gray")
+    return out if a.ndim == 4 else out[0]
+
+
+def _depth_type(depth):
+    if depth.dtype == np.uint16:
+        return _lib.ORBX_DEPTH_U16
+    if depth.dtype == np.float32:
+        return _lib.ORBX_DEPTH_F32
+    raise TypeError("depth image must be CV_16U or CV_32F, not %s" % depth.dtype)
+
+
+def frame_rgbd(extractor, image, depth, depth_factor, K, dist_coef, bf, rgb=True):
+    """The ORB part of Frame's RGB-D constructor (src/Frame.cc:126-183: ExtractORB(0), UndistortKeyPoints,
+    ComputeStereoFromRGBD) with Tracking::GrabImageRGBD's preprocessing (src/Tracking.cc:210-233: cvtColor,
+    convertTo(CV_32F, mDepthMapFactor)) in one call through `extractor`.
+
+    image: uint8 [H, W] or [H, W, 3 or 4] (rgb: mbRGB); depth: uint16 or float32 [H, W]; depth_factor:
+    mDepthMapFactor as Tracking holds it (already inverted, src/Tracking.cc:144-148).
+    Returns (kps, desc, kps_un, mvuRight, mvDepth); descriptors None without keypoints."""
+    img = np.asarray(image)
+    dep = np.asarray(depth)
+    assert img.dtype == np.uint8 and img.ndim in (2, 3), "image must be CV_8UC1 / C3 / C4"
+    ch = 1 if img.ndim == 2 else img.shape[2]
+    if img.size and (img.strides[1] != ch or (img.ndim == 3 and img.strides[2] != 1)):
+        img = np.ascontiguousarray(img)
+    assert dep.ndim == 2
+    if dep.size and dep.strides[1] != dep.itemsize:
+        dep = np.ascontiguousarray(dep)
+    h, w = img.shape[:2]
+    cap = max(extractor.max_keypoints(w, h), 1) if w > 0 and h > 0 else 1
+    kps, kun = np.zeros(cap, KEYPOINT_DTYPE), np.zeros(cap, KEYPOINT_DTYPE)
+    desc = np.zeros((cap, 32), np.uint8)
+    uR, d = np.full(cap, -1.0, np.float32), np.full(cap, -1.0, np.float32)
+    n = C.c_int(0)
+    cam = camera(K, dist_coef)
+    check(_lib.lib().orbx_frame_rgbd(extractor._h, ptr(img) if img.size else None, img.strides[0], w, h, ch,
+                                     int(bool(rgb)), ptr(dep), dep.strides[0], dep.shape[1], dep.shape[0],
+                                     _depth_type(dep), C.c_float(depth_factor), C.byref(cam), C.c_float(bf),
+                                     ptr(kps), ptr(desc), cap, C.byref(n), ptr(kun), ptr(uR), ptr(d)),
+          "orbx_frame_rgbd")
+    extractor._last_shape = (w, h)
+    n = n.value
+    return kps[:n].copy(), desc[:n].copy() if n else None, kun[:n].copy(), uR[:n].copy(), d[:n].copy()
+
+
+def rgbd_frames_device(extractor, images, depth, depth_factor, K, dist_coef, bf, kps, desc, counts, kps_un, uright,
+                       depth_out, nmatches, rgb=True, stream=None):
+    """orbx_rgbd_frames_device: n RGB-D frames resident on the device (torch tensors).
+
+    images: uint8 [n, H, W] or [n, H, W, 3 or 4]; depth: int16 / uint16 bits or float32 [n, H, W] (a torch
+    int16 tensor holds CV_16U bits); kps / kps_un: uint8 [n, cap, 28]; desc: uint8 [n, cap, 32]; counts /
+    nmatches: int32 [n]; uright / depth_out: float32 [n, cap].  Row and image strides are the tensors' own."""
+    n, h, w = images.shape[:3]
+    ch = 1 if images.dim() == 3 else images.shape[3]
+    assert images.stride(2) == ch and (ch == 1 or images.stride(3) == 1) and depth.stride(2) == 1
+    es = depth.element_size()
+    dtype = _lib.ORBX_DEPTH_U16 if es == 2 else _lib.ORBX_DEPTH_F32
+    assert es == 2 or depth.is_floating_point(), "depth must be 16-bit integer or float32"
+    cam = camera(K, dist_coef)
+    check(_lib.lib().orbx_rgbd_frames_device(extractor._h, n, ptr(images), w, h, ch, int(bool(rgb)), images.stride(1),
+                                             images.stride(0), ptr(depth), dtype, depth.stride(1) * es,
+                                             depth.stride(0) * es, C.c_float(depth_factor), C.byref(cam),
+                                             C.c_float(bf), ptr(kps), ptr(desc), ptr(counts), kps.shape[1],
+                                             ptr(kps_un), ptr(uright), ptr(depth_out), ptr(nmatches),
+                                             _stream_ptr(stream, True)),
+          "orbx_rgbd_frames_device")
+
+
 def compute_distinctive_descriptors(desc, obs_off, device=0):
     """MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:249-320) for a batch of MapPoints:
     desc[obs_off[p]:obs_off[p+1]] are point p's observed descriptors in mObservations order.

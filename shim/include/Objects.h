@@ -439,7 +439,31 @@ class Frame {
         ORBextractor* extractorRight, ORBVocabulary* voc, cv::Mat& K, cv::Mat& distCoef, const float& bf,
         const float& thDepth);
 
+  // The reference's RGB-D constructor (include/Frame.h:58, src/Frame.cc:126-183): imGray CV_8UC1, imDepth
+  // CV_32F as Tracking::GrabImageRGBD hands it over (already converted, src/Tracking.cc:230-231).
+  // ExtractORB(0), UndistortKeyPoints and ComputeStereoFromRGBD run as ONE orbx_frame_rgbd call; fills
+  // mvKeys, mDescriptors, mvKeysUn, mvuRight, mvDepth, the scale tables and mb, and on the first frame the
+  // image bounds, the grid cell inverses and the static intrinsics.
+  Frame(const cv::Mat& imGray, const cv::Mat& imDepth, const double& timeStamp, ORBextractor* extractor,
+        ORBVocabulary* voc, cv::Mat& K, cv::Mat& distCoef, const float& bf, const float& thDepth);
+  // The same with GrabImageRGBD's preprocessing inside the call (not in the reference): im may be CV_8UC1,
+  // CV_8UC3 or CV_8UC4 (bRGB = Tracking's mbRGB: the byte order of a colour image), imDepth the RAW depth
+  // image, CV_16U or CV_32F, and depthMapFactor Tracking's mDepthMapFactor (already inverted,
+  // src/Tracking.cc:144-148).  The caller skips cvtColor and the host convertTo: the conversion is applied
+  // to the pixels under the keypoints, under the reference's condition (:230).
+  Frame(const cv::Mat& im, const cv::Mat& imDepth, const double& timeStamp, ORBextractor* extractor,
+        ORBVocabulary* voc, cv::Mat& K, cv::Mat& distCoef, const float& bf, const float& thDepth,
+        const float& depthMapFactor, bool bRGB = true);
+  // The reference's monocular constructor (include/Frame.h:61, src/Frame.cc:186-251): extraction and
+  // undistortion, mvuRight and mvDepth all -1.
+  Frame(const cv::Mat& imGray, const double& timeStamp, ORBextractor* extractor, ORBVocabulary* voc, cv::Mat& K,
+        cv::Mat& distCoef, const float& bf, const float& thDepth);
+
   void ExtractORB(int flag, const cv::Mat& im);  // src/Frame.cc:273-279
+  // src/Frame.cc:791-816 on a CV_32F depth image, from mvKeys / mvKeysUn / mbf (the constructors above get
+  // the same values from the GPU inside orbx_frame_rgbd; this member is the reference's own loop, for
+  // callers that invoke it on its own)
+  void ComputeStereoFromRGBD(const cv::Mat& imDepth);
   void UndistortKeyPoints();                     // src/Frame.cc:471-506
   void ComputeImageBounds(const cv::Mat& imLeft);  // src/Frame.cc:508-537 (corners on the MI355X)
   void ComputeStereoMatches();                   // src/Frame.cc:547-788 (on the MI355X)
@@ -480,6 +504,9 @@ class Frame {
   // src/Frame.cc:86-123 after the two ExtractORB calls; uR / dep: stereo results already computed by
   // orbx_frame_stereo (null: ComputeStereoMatches runs)
   void finish_stereo_frame(const std::vector<float>* uR, const std::vector<float>* dep);
+  // the RGB-D (imDepth non-null) and monocular (null) constructors' shared body, src/Frame.cc:130-183, 190-251
+  void init_single_camera(const cv::Mat& im, const cv::Mat* imDepth, float depthMapFactor, bool bRGB,
+                          const double& timeStamp, ORBVocabulary* voc);
 };
 
 // Free-function form of Frame::ComputeStereoMatches for callers without a Frame object:

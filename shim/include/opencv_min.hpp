@@ -4,8 +4,10 @@
 // OpenCV, which this image does not have.  A maintainer building inside ORB-SLAM2 deletes this
 // header and includes <opencv2/core/core.hpp> instead: every use below is source-compatible.
 //
-// Mat is a reference-counted 2-D buffer (CV_8U / CV_32F / CV_64F, one channel): shallow copies
-// share data exactly like cv::Mat, clone()/copyTo() deep-copy, row()/rowRange() are views.
+// Mat is a reference-counted 2-D buffer (CV_8U / CV_16U / CV_32F / CV_64F; one channel, or 3 / 4 for the
+// 8-bit colour images Tracking::GrabImage* receive): shallow copies share data exactly like cv::Mat,
+// clone()/copyTo() deep-copy, row()/rowRange() are views.  A type is OpenCV's own code: depth in the low
+// three bits, channels - 1 above them (CV_MAKETYPE).
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -21,6 +23,21 @@
 #define CV_8UC1 CV_8U
 #define CV_32FC1 CV_32F
 #define CV_64FC1 CV_64F
+#endif
+#ifndef CV_16U
+#define CV_16U 2
+#define CV_16UC1 CV_16U
+#define CV_CN_SHIFT 3
+#define CV_MAT_DEPTH(type) ((type) & ((1 << CV_CN_SHIFT) - 1))
+#define CV_MAT_CN(type) (((type) >> CV_CN_SHIFT) + 1)
+#define CV_MAKETYPE(depth, cn) (CV_MAT_DEPTH(depth) + (((cn) - 1) << CV_CN_SHIFT))
+#define CV_8UC3 CV_MAKETYPE(CV_8U, 3)
+#define CV_8UC4 CV_MAKETYPE(CV_8U, 4)
+// cv::cvtColor codes (imgproc/types_c.h), the four src/Tracking.cc uses
+#define CV_BGR2GRAY 6
+#define CV_RGB2GRAY 7
+#define CV_BGRA2GRAY 10
+#define CV_RGBA2GRAY 11
 #endif
 
 namespace cv {
@@ -61,12 +78,14 @@ class KeyPoint {
       : pt(x, y), size(size_), angle(angle_), response(response_), octave(octave_), class_id(class_id_) {}
 };
 
-inline size_t elem_size(int type) {
-  switch (type) {
-    case CV_8U: return 1;
-    case CV_32F: return 4;
-    case CV_64F: return 8;
-  }
+inline size_t elem_size(int type) {  // bytes of one element, all its channels
+  const size_t cn = (size_t)CV_MAT_CN(type);
+  if (type >= 0 && cn <= 4) switch (CV_MAT_DEPTH(type)) {
+      case CV_8U: return cn;
+      case CV_16U: return 2 * cn;
+      case CV_32F: return 4 * cn;
+      case CV_64F: return 8 * cn;
+    }
   throw std::invalid_argument("opencv_min: unsupported Mat type");
 }
 
@@ -101,6 +120,8 @@ class Mat {
   }
   bool empty() const { return data == nullptr || rows == 0 || cols == 0; }
   int type() const { return type_; }
+  int depth() const { return CV_MAT_DEPTH(type_); }
+  int channels() const { return CV_MAT_CN(type_); }
   size_t elemSize() const { return elem_size(type_); }
   bool isContinuous() const { return step == (size_t)cols * elem_size(type_); }
 
@@ -158,5 +179,9 @@ class _OutputArray {
   Mat* m_;
 };
 typedef const _OutputArray& OutputArray;
+
+// cv::cvtColor for the four codes above on CV_8UC3 / CV_8UC4 (OpenCV 3.2 RGB2Gray<uchar>, on the GPU:
+// orbx_cvt_gray).  dst may be src, as src/Tracking.cc:178 calls it.  Defined in liborbx_shim.so.
+void cvtColor(InputArray src, OutputArray dst, int code, int dstCn = 0);
 
 }  // namespace cv

@@ -1,4 +1,5 @@
-// shim.cc -- the reference's hot-path classes (ORBextractor, Frame's ORB/stereo part and ComputeBoW,
+// shim.cc -- the reference's hot-path classes (ORBextractor, Frame's ORB/stereo part, its RGB-D and
+// monocular constructors, ComputeBoW, cv::cvtColor's four grey codes,
 // ORBmatcher's SearchByBoW x2 / SearchByProjection x3 / SearchForTriangulation / Fuse /
 // DescriptorDistance, PnPsolver, Optimizer::PoseOptimization / LocalBundleAdjustment /
 // GlobalBundleAdjustemnt,
@@ -243,6 +244,154 @@ Frame::Frame(const cv::Mat& imLeft, const cv::Mat& imRight, const double& timeSt
   }
   // AssignFeaturesToGrid (:131): the matchers build the 64x48 grid on the device per call
 }
+
+// ------------------------------------------------------------------ Frame (RGB-D and monocular)
+static orbx_camera frame_camera(const cv::Mat& K, const cv::Mat& distCoef) {
+  orbx_camera cam;
+  for (int r = 0; r < 3; r++)
+    for (int c = 0; c < 3; c++) cam.K[3 * r + c] = K.at<float>(r, c);
+  const int nd = distCoef.empty() ? 0 : distCoef.rows * distCoef.cols;
+  cam.n_dist = nd < 4 ? 4 : nd;
+  for (int i = 0; i < 5; i++) cam.dist[i] = i < nd ? distCoef.ptr<float>(0)[i] : 0.f;
+  return cam;
+}
+
+Frame::Frame(const cv::Mat& imGray, const cv::Mat& imDepth, const double& timeStamp, ORBextractor* extractor,
+             ORBVocabulary* voc, cv::Mat& K, cv::Mat& distCoef, const float& bf, const float& thDepth)
+    : mpORBextractorLeft(extractor), mbf(bf), mThDepth(thDepth) {
+  mK = K.clone();
+  mDistCoef = distCoef.clone();
+  // imDepth.at<float>(v,u), src/Frame.cc:806: the image is CV_32F by now, and a factor of 1 passes its bits on
+  if (!imGray.empty() && (imGray.type() != CV_8UC1 || imDepth.type() != CV_32F))
+    throw std::invalid_argument("Frame: imGray must be CV_8UC1 and imDepth CV_32F");
+  init_single_camera(imGray, &imDepth, 1.0f, true, timeStamp, voc);
+}
+
+Frame::Frame(const cv::Mat& im, const cv::Mat& imDepth, const double& timeStamp, ORBextractor* extractor,
+             ORBVocabulary* voc, cv::Mat& K, cv::Mat& distCoef, const float& bf, const float& thDepth,
+             const float& depthMapFactor, bool bRGB)
+    : mpORBextractorLeft(extractor), mbf(bf), mThDepth(thDepth) {
+  mK = K.clone();
+  mDistCoef = distCoef.clone();
+  init_single_camera(im, &imDepth, depthMapFactor, bRGB, timeStamp, voc);
+}
+
+Frame::Frame(const cv::Mat& imGray, const double& timeStamp, ORBextractor* extractor, ORBVocabulary* voc, cv::Mat& K,
+             cv::Mat& distCoef, const float& bf, const float& thDepth)
+    : mpORBextractorLeft(extractor), mbf(bf), mThDepth(thDepth) {
+  mK = K.clone();
+  mDistCoef = distCoef.clone();
+  init_single_camera(imGray, nullptr, 1.0f, true, timeStamp, voc);
+}
+
+void Frame::init_single_camera(const cv::Mat& im, const cv::Mat* imDepth, float depthMapFactor, bool bRGB,
+                               const double& timeStamp, ORBVocabulary* voc) {
+  mnId = nNextId++;
+  mTimeStamp = timeStamp;
+  mpORBvocabulary = voc;
+  // scale level info (src/Frame.cc:133-140, 193-200)
+  mnScaleLevels = mpORBextractorLeft->GetLevels();
+  mfScaleFactor = mpORBextractorLeft->GetScaleFactor();
+  mfLogScaleFactor = std::log(mfScaleFactor);
+  mvScaleFactors = mpORBextractorLeft->GetScaleFactors();
+  mvInvScaleFactors = mpORBextractorLeft->GetInverseScaleFactors();
+  mvLevelSigma2 = mpORBextractorLeft->GetScaleSigmaSquares();
+  mvInvLevelSigma2 = mpORBextractorLeft->GetInverseScaleSigmaSquares();
+  if (imDepth) {
+    // ExtractORB(0, imGray), UndistortKeyPoints, ComputeStereoFromRGBD (:143-154): one library call
+    if (!im.empty()) {
+      if (im.depth() != CV_8U || im.channels() == 2) throw std::invalid_argument("Frame: image must be CV_8UC1 / C3 / C4");
+      ORBextractor* ex = mpORBextractorLeft;
+      const int cap = orbx_extractor_max_keypoints(ex->gpu(), im.cols, im.rows);
+      if (cap < 0) check(cap, "orbx_extractor_max_keypoints");
+      const int room = cap > 0 ? cap : 1;
+      mvKeys.resize(room);
+      mvKeysUn.resize(room);
+      mvuRight.resize(room);
+      mvDepth.resize(room);
+      cv::Mat desc(room, 32, CV_8U);
+      const orbx_camera cam = frame_camera(mK, mDistCoef);
+      int n = 0;
+      check(orbx_frame_rgbd(ex->gpu(), im.data, im.step, im.cols, im.rows, im.channels(), bRGB ? 1 : 0, imDepth->data,
+                            imDepth->step, imDepth->cols, imDepth->rows, imDepth->type(), depthMapFactor, &cam, mbf,
+                            reinterpret_cast<orbx_keypoint*>(mvKeys.data()), desc.data, cap, &n,
+                            reinterpret_cast<orbx_keypoint*>(mvKeysUn.data()), mvuRight.data(), mvDepth.data()),
+            "orbx_frame_rgbd");
+      mvKeys.resize(n);
+      mvKeysUn.resize(n);
+      mvuRight.resize(n);
+      mvDepth.resize(n);
+      if (n) {  // ExtractForFrame's outputs: exactly n descriptor rows, no pyramid kept
+        mDescriptors.create(n, 32, CV_8U);
+        std::memcpy(mDescriptors.data, desc.data, (size_t)32 * n);
+      }
+      for (int l = 0; l < ex->nlevels; l++) ex->mvImagePyramid[l].release();
+    }
+    N = (int)mvKeys.size();
+    if (mvKeys.empty()) return;  // :147-148
+  } else {
+    ExtractORB(0, im);  // :204
+    N = (int)mvKeys.size();
+    if (mvKeys.empty()) return;  // :208-209
+    UndistortKeyPoints();
+    mvuRight.assign(N, -1.0f);  // no stereo information, :215-216
+    mvDepth.assign(N, -1.0f);
+  }
+  mvpMapPoints.assign(N, nullptr);
+  mvbOutlier.assign(N, false);
+  // only for the first Frame, or after a change in the calibration (:162-177, 223-245)
+  if (mbInitialComputations) {
+    ComputeImageBounds(im);
+    mfGridElementWidthInv = static_cast<float>(ORBX_GRID_COLS) / (mnMaxX - mnMinX);
+    mfGridElementHeightInv = static_cast<float>(ORBX_GRID_ROWS) / (mnMaxY - mnMinY);
+    fx = mK.at<float>(0, 0);
+    fy = mK.at<float>(1, 1);
+    cx = mK.at<float>(0, 2);
+    cy = mK.at<float>(1, 2);
+    invfx = 1.0f / fx;
+    invfy = 1.0f / fy;
+    mbInitialComputations = false;
+  }
+  mb = mbf / fx;  // :179, 247
+  // AssignFeaturesToGrid (:182, 250): the matchers build the 64x48 grid on the device per call
+}
+
+void Frame::ComputeStereoFromRGBD(const cv::Mat& imDepth) {
+  // src/Frame.cc:791-816 as written: a float-indexed at<float> truncates, at the distorted keypoint
+  if (imDepth.type() != CV_32F) throw std::invalid_argument("Frame::ComputeStereoFromRGBD: imDepth must be CV_32F");
+  mvuRight.assign(N, -1.0f);
+  mvDepth.assign(N, -1.0f);
+  for (int i = 0; i < N; i++) {
+    const cv::KeyPoint& kp = mvKeys[i];
+    const cv::KeyPoint& kpU = mvKeysUn[i];
+    const int v = (int)kp.pt.y, u = (int)kp.pt.x;
+    if (v < 0 || v >= imDepth.rows || u < 0 || u >= imDepth.cols)
+      throw std::out_of_range("Frame::ComputeStereoFromRGBD: keypoint outside the depth image");
+    const float d = imDepth.at<float>(v, u);
+    if (d > 0) {
+      mvDepth[i] = d;
+      mvuRight[i] = kpU.pt.x - mbf / d;
+    }
+  }
+}
+
+}  // namespace ORB_SLAM2
+
+// cv::cvtColor for Tracking::GrabImage*'s four codes (src/Tracking.cc:174-199, 215-228, 246-259)
+void cv::cvtColor(cv::InputArray src, cv::OutputArray dst, int code, int) {
+  const cv::Mat s = src.getMat();  // shares the data: dst may be the same Mat
+  const bool four = code == CV_BGRA2GRAY || code == CV_RGBA2GRAY, rgb = code == CV_RGB2GRAY || code == CV_RGBA2GRAY;
+  if (code != CV_BGR2GRAY && code != CV_RGB2GRAY && code != CV_BGRA2GRAY && code != CV_RGBA2GRAY)
+    throw std::invalid_argument("cv::cvtColor: only CV_BGR2GRAY, CV_RGB2GRAY, CV_BGRA2GRAY and CV_RGBA2GRAY");
+  if (s.type() != (four ? CV_8UC4 : CV_8UC3)) throw std::invalid_argument("cv::cvtColor: source channels do not fit the code");
+  cv::Mat g(s.rows, s.cols, CV_8UC1);
+  const orbx_status st = orbx_cvt_gray(s.data, s.step, s.step * (size_t)s.rows, 1, s.cols, s.rows, four ? 4 : 3, rgb ? 1 : 0,
+                                       g.data, g.step, g.step * (size_t)g.rows, ORB_SLAM2::gOrbxDevice);
+  if (st != ORBX_OK) throw std::runtime_error("orbx_cvt_gray failed: orbx_status " + std::to_string(st));
+  dst.getMatRef() = g;
+}
+
+namespace ORB_SLAM2 {
 
 void Frame::ComputeImageBounds(const cv::Mat& imLeft) {
   // src/Frame.cc:508-537: the undistorted image corners (cv::undistortPoints with P = K on the GPU)

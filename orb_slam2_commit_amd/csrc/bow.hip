@@ -10,10 +10,13 @@
 // ties; best2 counts duplicates).
 #include <hip/hip_runtime.h>
 
+#include <cstring>
+
 #include "orbx_device.h"
 #include "orbx_internal.h"
 #include "orbx_bow.h"
 #include "orbx_match.h"
+#include "orbx_scratch.h"
 
 namespace orbx {
 
@@ -163,3 +166,93 @@ hipError_t launch_search_by_bow(const BowProblem* d_probs, int n, hipStream_t st
 }
 
 }  // namespace orbx
+
+// ------------------------------------------------------------------ host entry points
+using namespace orbx;
+
+static orbx_status bow_host(const orbx_bow_side* A, const orbx_bow_side* B, float nnratio, int check_ori, int mode,
+                            int32_t* match, int* nmatches, int device) {
+  if (!A || !B || !match || !nmatches) return ORBX_ERR_ARG;
+  const int nout = mode ? A->n : B->n;
+  *nmatches = 0;
+  if (A->n > kMaxBowFeatures || B->n > kMaxBowFeatures || A->n < 0 || B->n < 0) return ORBX_ERR_CAPACITY;
+  const orbx_status dv = orbx::select_device(device);
+  if (dv != ORBX_OK) return dv;
+  // a pooled lease (orbx_scratch.h): no allocation, no device-wide synchronisation per call
+  using orbx::Staging;
+  Staging S(device);
+  struct Side {
+    Staging::Slot<uint8_t> desc, valid;
+    Staging::Slot<float> angle;
+    Staging::Slot<uint32_t> node_id;
+    Staging::Slot<int32_t> node_off, feat;
+  } L[2];
+  const orbx_bow_side* sides[2] = {A, B};
+  for (int z = 0; z < 2; z++) {
+    const orbx_bow_side* s = sides[z];
+    const size_t n = (size_t)s->n, nn = (size_t)s->n_nodes;
+    L[z].desc = S.in(s->desc, n * 32);
+    L[z].angle = S.in(s->angle, n);
+    L[z].valid = S.in_opt(s->valid, n);
+    L[z].node_id = S.in(s->node_id, nn);
+    L[z].node_off = S.in(s->node_off, nn + 1);
+    L[z].feat = S.in(s->feat, nn ? (size_t)s->node_off[nn] : 0);
+  }
+  const auto s_P = S.record<BowProblem>();
+  const auto s_match = S.out<int32_t>((size_t)nout), s_n = S.out<int32_t>(1);
+  const orbx_status cs = S.commit();
+  if (cs != ORBX_OK) return cs;
+  BowProblem P;
+  std::memset(&P, 0, sizeof(P));  // no device-count overrides on the host path
+  for (int z = 0; z < 2; z++) {
+    orbx_bow_side& d = z ? P.b : P.a;
+    d = *sides[z];
+    d.desc = S.dev(L[z].desc);
+    d.angle = S.dev(L[z].angle);
+    d.valid = S.dev(L[z].valid);
+    d.node_id = S.dev(L[z].node_id);
+    d.node_off = S.dev(L[z].node_off);
+    d.feat = S.dev(L[z].feat);
+  }
+  P.nnratio = nnratio;
+  P.check_ori = check_ori;
+  P.mode = mode;
+  P.match = S.dev(s_match);
+  P.nmatches = S.dev(s_n);
+  S.fill(s_P, P);
+  hipError_t e = S.upload(Staging::Outputs::zeroed);
+  if (e == hipSuccess) e = launch_search_by_bow(S.dev(s_P), 1, S.stream());
+  if (e == hipSuccess) e = S.download();
+  if (e == hipSuccess) e = S.sync();
+  if (e != hipSuccess) return ORBX_ERR_HIP;
+  S.fetch(s_match, match, (size_t)nout);
+  S.fetch(s_n, (int32_t*)nmatches, 1);
+  return ORBX_OK;
+}
+
+extern "C" {
+
+orbx_status orbx_search_by_bow_kf_f(const orbx_bow_side* kf, const orbx_bow_side* f, float nnratio, int check_ori,
+                                    int32_t* match_f, int* nmatches, int device) {
+  return bow_host(kf, f, nnratio, check_ori, 0, match_f, nmatches, device);
+}
+
+orbx_status orbx_search_by_bow_kf_kf(const orbx_bow_side* kf1, const orbx_bow_side* kf2, float nnratio,
+                                     int check_ori, int32_t* match12, int* nmatches, int device) {
+  return bow_host(kf1, kf2, nnratio, check_ori, 1, match12, nmatches, device);
+}
+
+orbx_status orbx_search_by_bow_device(const orbx_bow_problem* problems, int n, void* stream) {
+  if (n < 0 || (n > 0 && !problems)) return ORBX_ERR_ARG;
+  if (n == 0) return ORBX_OK;
+  for (int i = 0; i < n; i++)
+    if (problems[i].a.n > kMaxBowFeatures || problems[i].b.n > kMaxBowFeatures) return ORBX_ERR_CAPACITY;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t bytes = sizeof(BowProblem) * n;
+  return orbx::with_stream_block(bytes, st, [&](uint8_t* d) {
+    const hipError_t e = hipMemcpyAsync(d, problems, bytes, hipMemcpyHostToDevice, st);
+    return e != hipSuccess ? e : launch_search_by_bow((const BowProblem*)d, n, st);
+  });
+}
+
+}  // extern "C"

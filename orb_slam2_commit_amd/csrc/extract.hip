@@ -319,7 +319,7 @@ __device__ __forceinline__ void unrolled_while(std::integer_sequence<int, I...>,
   (void)(f(std::integral_constant<int, I>{}) && ...);
 }
 
-// The fast path of a level (chosen at plan time, strip_resize_ok in capi.hip; every level of a 1.2
+// The fast path of a level (chosen at plan time, strip_resize_ok in plan.hip; every level of a 1.2
 // pyramid takes it).  Same arithmetic, one barrier, no row sums through LDS: a block stages the
 // footprint of a 256 x kRsTH output tile as k_resize does, at the compile-time stride kRsStride, and
 // then each wave owns one strip of kRsR output rows: lane = 4 adjacent output columns.  The wave
@@ -1154,29 +1154,6 @@ struct OctSmem {
   uint16_t* kn;    // [kcap] candidate node | digit << 14
 };
 
-__host__ __device__ inline int next_pow2(int v) {
-  int p = 1;
-  while (p < v) p <<= 1;
-  return p;
-}
-
-__host__ __device__ inline size_t octree_smem_bytes(int NC, int cell_cap, int kcap) {
-  const int NP2 = next_pow2(NC);
-  size_t b = 0;
-  b += 2 * 4 * NC * sizeof(int16_t);
-  b += 2 * 2 * NC * sizeof(int);
-  b += NC * 4 * sizeof(int);
-  b += NC * 4 * sizeof(int16_t);
-  b += NC * sizeof(int16_t);
-  b += 2 * NC * sizeof(int);
-  b = (b + 7) & ~(size_t)7;
-  b += (size_t)NP2 * sizeof(uint64_t);
-  b += (cell_cap + 1) * sizeof(int);
-  b += 8 * sizeof(int);
-  b += (size_t)kcap * (sizeof(uint32_t) + sizeof(uint16_t));
-  return b;
-}
-
 // octree block size NT per launch group (Geometry::og): the split rounds loop over every candidate
 // of the level (thousands at levels 0-2: 512 threads there, 512 beat 256 for a single launch, 0.42
 // -> 0.38 ms per 256 frames, and 1024 halved the resident blocks per CU, 0.71); the upper levels
@@ -1205,7 +1182,7 @@ __device__ __forceinline__ void bitonic_sort_desc(uint64_t* k, int n) {
 }
 
 // Per-candidate state across the split rounds: the packed position (score<<24 |
-// y<<12 | x, level-relative) and node | child digit<<14.  The first G->oct_kcap
+// y<<12 | x, level-relative) and node | child digit<<14.  The first grp.kcap
 // candidates of a level live in LDS for the whole kernel (sized on the host so
 // the block still fits three per CU); only a level with more candidates keeps
 // the rest in the global kpos/knode scratch.  Every round walks all candidates
@@ -2031,8 +2008,6 @@ hipError_t launch_extract_stages(const Geometry& Gh, const Geometry* Gd, const C
   T->end(ST_DESCRIBE, st);
   return hipGetLastError();
 }
-
-size_t octree_smem_host(int NC, int cell_cap, int kcap) { return octree_smem_bytes(NC, cell_cap, kcap); }
 
 hipError_t octree_set_smem_limit(size_t bytes) {
   hipError_t e = hipFuncSetAttribute((const void*)k_octree<512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);

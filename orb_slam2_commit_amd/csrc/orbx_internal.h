@@ -52,15 +52,37 @@ struct OctGroup {
   int kcap;      // candidates of a level kept in LDS (the rest in global scratch)
 };
 
+// k_octree's dynamic LDS for a launch group (OctSmem in extract.hip carves it up in this order); the
+// plan sizes a group's kcap with it, the launch passes it
+__host__ __device__ inline int next_pow2(int v) {
+  int p = 1;
+  while (p < v) p <<= 1;
+  return p;
+}
+
+__host__ __device__ inline size_t octree_smem_bytes(int NC, int cell_cap, int kcap) {
+  const int NP2 = next_pow2(NC);
+  size_t b = 0;
+  b += 2 * 4 * NC * sizeof(int16_t);
+  b += 2 * 2 * NC * sizeof(int);
+  b += NC * 4 * sizeof(int);
+  b += NC * 4 * sizeof(int16_t);
+  b += NC * sizeof(int16_t);
+  b += 2 * NC * sizeof(int);
+  b = (b + 7) & ~(size_t)7;
+  b += (size_t)NP2 * sizeof(uint64_t);
+  b += (cell_cap + 1) * sizeof(int);
+  b += 8 * sizeof(int);
+  b += (size_t)kcap * (sizeof(uint32_t) + sizeof(uint16_t));
+  return b;
+}
+
 struct Geometry {
   int nlevels, width, height;
   int ini_th, min_th;
   LevelGeom lv[kMaxLevelsPlan];
   long long pyr_bytes, blur_bytes;
   int ncells, cand_total, oct_total, max_kps, ntiles;
-  int node_cap;   // octree LDS node capacity (max over levels, multiple of 64)
-  int cell_cap;   // max cells in one level
-  int oct_kcap;   // octree: candidates of a level kept in LDS (the rest in global scratch)
   OctGroup og[2];  // k_octree launch groups (levels 0..split-1 at 512 threads, the rest at 256)
   int n_og;
   OctGroup og_all;  // every level in one launch (batches of <= kOctOneLaunch images)
@@ -80,7 +102,7 @@ struct Geometry {
 constexpr int kRzTW = 128, kRzTH = 32;  // k_resize output tile
 constexpr int kRzMaxRows = 64;
 
-// k_resize_strip (the fast path of a level, chosen at plan time: strip_resize_ok in capi.hip): a wave
+// k_resize_strip (the fast path of a level, chosen at plan time: strip_resize_ok in plan.hip): a wave
 // owns one strip of kRsR output rows across the 256-column tile (lane = 4 adjacent columns), a block
 // four strips.  Footprint rows in LDS at a compile-time stride.
 #ifndef ORBX_RS_R
@@ -172,5 +194,16 @@ struct ResizeDesc {
 struct LaunchPlan {
   ResizeDesc rz[kMaxLevelsPlan];  // [l], l >= 1
 };
+
+// ------------------------------------------------------------ extract.hip's host entry points
+struct StageTimer;
+hipError_t upload_constants(const int* umax16, const int* gauss7);
+hipError_t launch_blur(const Geometry& Gh, const Geometry* Gd, const int* tile_level, const BatchPtrs& B, int n_img,
+                       hipStream_t st);
+hipError_t launch_extract_stages(const Geometry& Gh, const Geometry* Gd, const CellInfo* cells, const int* tile_level,
+                                 const LaunchPlan& LP, const BatchPtrs& B, int n_img, orbx_keypoint* kps, uint8_t* desc,
+                                 int32_t* counts, int kp_cap, hipStream_t st, StageTimer* T);
+hipError_t octree_set_smem_limit(size_t bytes);
+const uint8_t* patch_slot_table();
 
 }  // namespace orbx

@@ -95,7 +95,7 @@ def test_extract_bitexact(gpu, name, seed, w, h, nf):
 @pytest.mark.parametrize("seed,w,h,nf", [(10, 640, 480, 1000), (11, 640, 480, 1000), (12, 1241, 376, 2000)])
 def test_extract_stress_noise(gpu, seed, w, h, nf):
     """i.i.d. uniform noise: dense FAST responses, heavy octree phase 2; levels 0-2 hold more
-    candidates than k_octree keeps in LDS (Geometry::oct_kcap), so the global spill path runs."""
+    candidates than k_octree keeps in LDS (its launch group's OctGroup::kcap), so the global spill path runs."""
     img = _image(seed, w, h, stress=True)
     ex = ORBextractor(nf, 1.2, 8, 20, 7)
     kps, desc = ex(img)

@@ -1,5 +1,5 @@
 """Per-level FAST survivor counts (k_octree's T) on bench-like KITTI frames, beside the LDS slots
-the plan gives k_octree (Geometry::oct_kcap): candidates past kcap live in global scratch and are
+the plan gives k_octree (its launch group's OctGroup::kcap): candidates past kcap live in global scratch and are
 re-read every split round."""
 import json
 import sys

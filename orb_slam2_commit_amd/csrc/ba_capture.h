@@ -5,7 +5,7 @@
 // k_ba_capture_post after k_ba_update (the solve's xp, the pushed state cbak / Xbak and the point
 // step).  optimize_dev launches them only while a capture is selected for the running phase; the
 // device LM state picks the trial, like the other gated kernels.  (Included by ba_host.h after its
-// DBuf and HIP_TRY, which the host half below uses.)
+// HIP_TRY, which the host half below uses.)
 #pragma once
 #include "ba_lm.h"
 
@@ -79,8 +79,8 @@ __global__ __launch_bounds__(LBS) void k_ba_capture_post(BaDev D, BaCapDev C) {
 struct BaCapture {
   int sel_phase = -1, sel_it = -1, sel_q = 0;  // sel_phase < 0: off
   int cur_phase = 0;                           // the phase optimize_dev is running (run_local_ba sets it)
-  DBuf<double> dd;
-  DBuf<int> di;
+  DevBuf<double> dd;
+  DevBuf<int> di;
   std::vector<double> hd;
   std::vector<int> hi;
   int dims[7] = {0, 0, 0, 0, 0, 0, 0};  // phase, nc, np, ne, na, npa, nposes of the host copy
@@ -124,8 +124,8 @@ struct BaCapture {
     std::memcpy(dims, d, sizeof d);
     size_t nd, ni;
     totals(dims, &nd, &ni);
-    HIP_TRY(dd.alloc(nd));
-    HIP_TRY(di.alloc(ni));
+    HIP_TRY(dd.ensure(nd));
+    HIP_TRY(di.ensure(ni));
     HIP_TRY(hipMemsetAsync(dd.p, 0, nd * sizeof(double), st));
     HIP_TRY(hipMemsetAsync(di.p, 0, ni * sizeof(int), st));
     auto pd = [&](int what) {

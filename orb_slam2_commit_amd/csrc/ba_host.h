@@ -21,36 +21,13 @@ namespace orbx {
 
 // ------------------------------------------------------------------ host
 
-template <class T>
-struct DBuf {
-  T* p = nullptr;
-  size_t n = 0;
-  ~DBuf() {
-    if (p) (void)hipFree(p);
-  }
-  hipError_t alloc(size_t count) {
-    if (count <= n && p) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-    hipError_t e = hipMalloc((void**)&p, std::max<size_t>(count, 1) * sizeof(T));
-    if (e == hipSuccess) n = std::max<size_t>(count, 1);
-    return e;
-  }
-  hipError_t put(const std::vector<T>& v) {
-    hipError_t e = alloc(v.size());
-    if (e != hipSuccess || v.empty()) return e;
-    return hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-  }
-};
-
 struct Ctx {
-  DBuf<double> cbak, Xbak, eerr, Hpl, ptc, cmc, BD, cf, Hll, bl, Dinv, dmax_p, Hpp, bp, xp, bs, S, Sw, scal, gpart, gpose;
+  DevBuf<double> cbak, Xbak, eerr, Hpl, ptc, cmc, BD, cf, Hll, bl, Dinv, dmax_p, Hpp, bp, xp, bs, S, Sw, scal, gpart, gpose;
 
-  DBuf<int> ptab;
-  DBuf<uint8_t> flag;
-  DBuf<LmState> lm;
-  DBuf<uint8_t> prob;  // k_ba_prep outputs: FP64 points and edge arrays
+  DevBuf<int> ptab;
+  DevBuf<uint8_t> flag;
+  DevBuf<LmState> lm;
+  DevBuf<uint8_t> prob;  // k_ba_prep outputs: FP64 points and edge arrays
 };
 
 #define HIP_TRY(x)                      \
@@ -65,44 +42,42 @@ struct Ctx {
 
 // A pinned host block and its device twin, carved by take() in the same offsets: arrays are laid
 // out with take(), filled through host(), and sent with one async copy (upload).  mapped: no
-// twin -- dbuf is the device's view of the pinned block itself, so kernels write results straight
+// twin -- dbuf() is the device's view of the pinned block itself, so kernels write results straight
 // into host memory (no copy, no copy engine hand-off after the last kernel)
+// (grows to arena_capacity(bytes), orbx_scratch.h)
 struct Arena {
-  uint8_t* hbuf = nullptr;
-  uint8_t* dbuf = nullptr;
-  size_t cap = 0, off = 0;
-  bool mapped = false;
-  explicit Arena(bool m = false) : mapped(m) {}
-  ~Arena() { release(); }
-  void release() {
-    if (hbuf) (void)hipHostFree(hbuf);
-    if (dbuf && !mapped) (void)hipFree(dbuf);
-    hbuf = dbuf = nullptr;
-  }
+  PinnedBuf hmem;
+  DevBuf<uint8_t> dmem;  // the twin (empty when mapped)
+  size_t off = 0;
+  const bool mapped;
+  explicit Arena(bool m = false) : hmem(m), mapped(m) {}
+  uint8_t* hbuf() const { return hmem.p; }
+  uint8_t* dbuf() const { return mapped ? hmem.dev() : dmem.p; }  // the device's side of the block
+  // what take() may hand out: the smaller side (the pinned owner rounds up to pages, the twin does not)
+  size_t capacity() const { return pair_capacity(hmem.cap, dmem.n, mapped); }
+  // both sides hold at least `bytes`, or neither holds anything
   hipError_t reserve(size_t bytes) {
     off = 0;
-    if (bytes <= cap && hbuf) return hipSuccess;
-    release();
-    cap = bytes + bytes / 4 + 4096;
-    hipError_t e = hipHostMalloc((void**)&hbuf, cap, mapped ? hipHostMallocMapped : hipHostMallocDefault);
-    if (e == hipSuccess)
-      e = mapped ? hipHostGetDevicePointer((void**)&dbuf, hbuf, 0) : hipMalloc((void**)&dbuf, cap);
+    if (bytes <= capacity() && hbuf() && dbuf()) return hipSuccess;
+    const size_t cap = arena_capacity(bytes);
+    hipError_t e = hmem.ensure(cap);
+    if (e == hipSuccess && !mapped) e = dmem.ensure(cap);
     if (e != hipSuccess) {
-      release();
-      cap = 0;
+      hmem.release();
+      dmem.release();
     }
     return e;
   }
   template <class T>
   T* take(size_t n) {
     off = scratch_align(off);
-    T* d = reinterpret_cast<T*>(dbuf + off);
+    T* d = reinterpret_cast<T*>(dbuf() + off);
     off += std::max<size_t>(n, 1) * sizeof(T);
     return d;
   }
   template <class T>
   T* host(T* d) {
-    return reinterpret_cast<T*>(hbuf + (reinterpret_cast<uint8_t*>(d) - dbuf));
+    return reinterpret_cast<T*>(hbuf() + (reinterpret_cast<uint8_t*>(d) - dbuf()));
   }
   template <class T>
   T* put(const std::vector<T>& v) {
@@ -111,7 +86,7 @@ struct Arena {
     return d;
   }
   hipError_t upload(hipStream_t st) {
-    return off && !mapped ? hipMemcpyAsync(dbuf, hbuf, off, hipMemcpyHostToDevice, st) : hipSuccess;
+    return off && !mapped ? hipMemcpyAsync(dbuf(), hbuf(), off, hipMemcpyHostToDevice, st) : hipSuccess;
   }
 };
 
@@ -122,7 +97,7 @@ inline size_t arena_bytes(std::initializer_list<size_t> sizes) {
 }
 
 }  // namespace orbx
-#include "ba_capture.h"  // (uses DBuf and HIP_TRY above)
+#include "ba_capture.h"  // (uses HIP_TRY above)
 namespace orbx {
 
 struct LocalBA {
@@ -145,10 +120,8 @@ struct LocalBA {
   std::vector<uint8_t> level;  // 0/1 per edge
   int trials = 0;
   int nbu = 1, n_rb = 8;           // k_ba_update blocks; doubles in the readback block
-  double* rb_host = nullptr;       // pinned readback block (mapped: rb_map is the device's view)
-  double* rb_map = nullptr;
-  int rb_cap = 0;
-  hipEvent_t rb_ev = nullptr;      // recorded after the readback copy (the wait skips later work)
+  PinnedBuf rb{true};              // pinned readback block, n_rb doubles (mapped: kernels write it in place)
+  Event rb_ev;                     // recorded after the readback copy (the wait skips later work)
   // the linearisation outputs the LM trials read
   struct LinSet {
     double *Hpl, *Hll, *bl, *dmax_p, *Hpp, *bp;
@@ -157,15 +130,7 @@ struct LocalBA {
   LocalBA() = default;
   LocalBA(const LocalBA&) = delete;
   LocalBA& operator=(const LocalBA&) = delete;
-  ~LocalBA() {
-    if (rb_host) (void)hipHostFree(rb_host);
-    if (rb_ev) (void)hipEventDestroy(rb_ev);
-    if (sint_host) (void)hipHostFree(sint_host);
-    if (lm_host) (void)hipHostFree(lm_host);
-    if (own_stop) (void)hipHostFree(own_stop);
-    if (mirror) (void)hipHostFree(mirror);
-  }
-  int* own_stop = nullptr;  // orbx_ba_stop_flag: pinned, device-readable
+  PinnedBuf own_stop{true};  // orbx_ba_stop_flag: one int, pinned, device-readable
   bool hook_stopped = false;  // ORBX_BA_RAISE_STOP_AFTER fired (the host then stops as for a raised flag)
   static void use_lin(BaDev& D, const LinSet& L) {
     D.Hpl = L.Hpl;
@@ -185,7 +150,7 @@ struct LocalBA {
   }
   // fused point side (k_ba_lin_schur): edges grouped by point with at most kFuseMaxDeg per point
   bool fuse_ok = false;
-  DBuf<int> pblk;
+  DevBuf<int> pblk;
   // host scratch, reused across calls
   std::vector<int> act, pos_pt, chidx, pose_cam, pt_off, pt_id, cam_off, cam_pos, cnt, pcam, ccnt, ccnt4, boff;
 
@@ -198,9 +163,8 @@ struct LocalBA {
   double t_struct[4] = {0, 0, 0, 0};  // host ms: index/CSR, pose groups, device build, upload+alloc
   bool dev_struct = false;  // k_ba_struct_* build the arrays (edges grouped by point, nc <= kStructMaxNc)
   const uint8_t* dfix = nullptr;  // device copy of the fixed flags
-  DBuf<int> sbuf;                 // k_ba_struct_* tiles and outputs, sized for the whole edge list
-  int* sint_host = nullptr;       // pinned, mapped: k_ba_struct_scan's five sizes (written there directly)
-  int* sint_map = nullptr;
+  DevBuf<int> sbuf;               // k_ba_struct_* tiles and outputs, sized for the whole edge list
+  PinnedBuf sint{true};           // pinned, mapped: k_ba_struct_scan's five sizes (written there directly)
   int sizes1[5] = {0, 0, 0, 0, 0};  // phase-1 sizes (all edges active), counted on the host
   orbx_status build_structure(int lvl, hipStream_t st) {
     if (dev_struct) return build_structure_dev(lvl, st, lvl < 0 ? sizes1 : nullptr);
@@ -327,24 +291,21 @@ struct LocalBA {
     const int* sz = known;
     if (!sz) {
       BA_CHECK(hipStreamSynchronize(st));
-      sz = sint_host;
+      sz = sint.as<int>();
     }
     const orbx_status fs = finish_structure(sz[0], sz[1], sz[2], sz[3], sz[4], st);
     t_struct[2] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - T0).count();
     return fs;
   }
-  // The structure kernels alone (sizes to the mapped sint_host unless known); gate: the device LM
+  // The structure kernels alone (sizes to the mapped sint block unless known); gate: the device LM
   // state that gates them (spec_skip), or null.  The host reads the sizes after the stream's next
   // synchronisation point and calls finish_structure.
   hipError_t launch_structure_dev(int lvl, hipStream_t st, const int* known, const LmState* gate) {
     const int nc = D.nc, ne = D.ne;
     const int ntiles = (ne + kTileE - 1) / kTileE;
     const size_t nb = (size_t)nc * (nc + 1) / 2 + 1;
-    HIP_TRY(sbuf.alloc(8 * (size_t)ntiles + (size_t)ntiles * nc + 6 * (size_t)ne + 1 + 3 * (size_t)nc + 1 + nb + 8));
-    if (!sint_host) {
-      HIP_TRY(hipHostMalloc((void**)&sint_host, 8 * sizeof(int), hipHostMallocMapped));
-      HIP_TRY(hipHostGetDevicePointer((void**)&sint_map, sint_host, 0));
-    }
+    HIP_TRY(sbuf.ensure(8 * (size_t)ntiles + (size_t)ntiles * nc + 6 * (size_t)ne + 1 + 3 * (size_t)nc + 1 + nb + 8));
+    HIP_TRY(sint.ensure(8 * sizeof(int)));
     int* p = sbuf.p;
     int4* ttot = reinterpret_cast<int4*>(p);  // first: 16-byte aligned
     p += 4 * (size_t)ntiles;
@@ -369,7 +330,7 @@ struct LocalBA {
       hipLaunchKernelGGL(k_ba_struct_count, dim3(ntiles), dim3(kTileT), sizeof(int) * (nc + kTileT / 64), st, Ds, fl,
                          lvl, tcnt, ttot);
     hipLaunchKernelGGL(k_ba_struct_scan, dim3(1), dim3(kStructNT), sizeof(int) * (nc + 1 + kStructNT / 64), st, Ds,
-                       dfix, ntiles, tcnt, ttot, tcar, known ? p : sint_map);
+                       dfix, ntiles, tcnt, ttot, tcar, known ? p : sint.dev<int>());
     if (ntiles > 0)
       hipLaunchKernelGGL(k_ba_struct_fill, dim3(ntiles), dim3(kTileT),
                          sizeof(int) * ((1 + kTileT / 64) * (size_t)nc + kTileE + kTileT / 64), st, Ds, fl, lvl, tcnt,
@@ -384,21 +345,21 @@ struct LocalBA {
     if (nposes > kTiledMaxPoses || nslots < 0) return ORBX_ERR_SIZE;
     const int gsplit = std::min(std::max((maxc + kGPpt * kGB - 1) / (kGPpt * kGB), 1), 64);
     const size_t N = 6 * (size_t)nposes;
-    BA_CHECK(c.Hpl.alloc(18 * (size_t)na));
-    BA_CHECK(c.ptc.alloc(12 * (size_t)na));
-    BA_CHECK(c.cmc.alloc(kCmc * (size_t)na));
-    BA_CHECK(c.BD.alloc(18 * (size_t)na));
-    BA_CHECK(c.cf.alloc(6 * (size_t)na));
-    BA_CHECK(c.Hll.alloc(9 * (size_t)npa));
-    BA_CHECK(c.bl.alloc(3 * (size_t)npa));
-    BA_CHECK(c.Dinv.alloc(9 * (size_t)npa));
-    BA_CHECK(c.dmax_p.alloc(npa + nposes));
-    BA_CHECK(c.Hpp.alloc(36 * (size_t)nposes));
-    BA_CHECK(c.bp.alloc(N));
-    if (!rb_ev) BA_CHECK(hipEventCreateWithFlags(&rb_ev, hipEventDisableTiming));
-    BA_CHECK(c.xp.alloc(N));
-    BA_CHECK(c.bs.alloc(N));
-    BA_CHECK(c.S.alloc(N * N));
+    BA_CHECK(c.Hpl.ensure(18 * (size_t)na));
+    BA_CHECK(c.ptc.ensure(12 * (size_t)na));
+    BA_CHECK(c.cmc.ensure(kCmc * (size_t)na));
+    BA_CHECK(c.BD.ensure(18 * (size_t)na));
+    BA_CHECK(c.cf.ensure(6 * (size_t)na));
+    BA_CHECK(c.Hll.ensure(9 * (size_t)npa));
+    BA_CHECK(c.bl.ensure(3 * (size_t)npa));
+    BA_CHECK(c.Dinv.ensure(9 * (size_t)npa));
+    BA_CHECK(c.dmax_p.ensure(npa + nposes));
+    BA_CHECK(c.Hpp.ensure(36 * (size_t)nposes));
+    BA_CHECK(c.bp.ensure(N));
+    BA_CHECK(rb_ev.ensure());
+    BA_CHECK(c.xp.ensure(N));
+    BA_CHECK(c.bs.ensure(N));
+    BA_CHECK(c.S.ensure(N * N));
     D.na = na;
     D.npa = npa;
     D.nposes = nposes;
@@ -406,24 +367,17 @@ struct LocalBA {
     D.gsplit = gsplit;
     // pairs | rhs | camfold pose terms (64-bit: nblk grows with the square of the poses)
     const size_t ngpart = ((size_t)D.nblk * 36 + (size_t)nposes * 6 + (size_t)nposes * 27) * (size_t)gsplit;
-    BA_CHECK(c.gpart.alloc(ngpart));
+    BA_CHECK(c.gpart.ensure(ngpart));
     D.gpart = c.gpart.p;
     // readback block: scal[0..7], then errors partials (2 slots of nbe), then update partials
     D.nbe = std::max((na + LBS - 1) / LBS, 1);
     nbu = std::max((nposes + LBS - 1) / LBS + (npa + kUpPts - 1) / kUpPts, 1);  // k_ba_update: pose blocks, then point blocks
     D.nbu = nbu;
     n_rb = 8 + 2 * D.nbe + nbu;
-    BA_CHECK(c.scal.alloc(n_rb));
+    BA_CHECK(c.scal.ensure(n_rb));
     D.scal = c.scal.p;
-    if (rb_cap < n_rb) {
-      if (rb_host) (void)hipHostFree(rb_host);
-      rb_host = nullptr;
-      rb_cap = 0;
-      BA_CHECK(hipHostMalloc((void**)&rb_host, n_rb * sizeof(double), hipHostMallocMapped));
-      BA_CHECK(hipHostGetDevicePointer((void**)&rb_map, rb_host, 0));
-      rb_cap = n_rb;
-    }
-    BA_CHECK(c.ptab.alloc(nslots));
+    BA_CHECK(rb.ensure(n_rb * sizeof(double)));
+    BA_CHECK(c.ptab.ensure(nslots));
     D.ptab = c.ptab.p;
     D.nbf = 0;
     D.pblk = nullptr;
@@ -434,12 +388,12 @@ struct LocalBA {
     int npb = 0;  // the pblk blocks, run inside the pair-table launch
     if (fuse_ok && na > 0) {
       D.nbf = (na - 1) / kFuseStride + 1;
-      BA_CHECK(pblk.alloc((size_t)D.nbf + 1));
+      BA_CHECK(pblk.ensure((size_t)D.nbf + 1));
       D.pblk = pblk.p;
       npb = npa / LBS + 1;
       const size_t ng = (size_t)D.nbf * nposes * kCmc;
       if (nposes > 0 && nposes <= kPosePartMaxPoses && ng <= kPosePartMaxDoubles) {
-        BA_CHECK(c.gpose.alloc(ng));
+        BA_CHECK(c.gpose.ensure(ng));
         D.gpose = c.gpose.p;
       }
     }
@@ -472,16 +426,17 @@ struct LocalBA {
     return e == hipSuccess ? finish_read(out) : e;
   }
   hipError_t start_read(hipStream_t st) {
-    hipError_t e = hipMemcpyAsync(rb_host, D.scal, n_rb * sizeof(double), hipMemcpyDeviceToHost, st);
+    hipError_t e = hipMemcpyAsync(rb.p, D.scal, n_rb * sizeof(double), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipEventRecord(rb_ev, st);
     return e;
   }
   hipError_t finish_read(double out[5]) {
     hipError_t e = wait_event(rb_ev);
     if (e != hipSuccess) return e;
-    out[2] = rb_host[2];
-    out[3] = rb_host[3];
-    const double* p = rb_host + 8;
+    const double* r = rb.as<double>();
+    out[2] = r[2];
+    out[3] = r[3];
+    const double* p = r + 8;
     double a = 0, b = 0, u = 0;
     for (int i = 0; i < D.nbe; i++) a += p[i];
     for (int i = 0; i < D.nbe; i++) b += p[D.nbe + i];
@@ -500,8 +455,8 @@ struct LocalBA {
   // queues as many trials as iterations remain (every trial ends at most one
   // iteration), reads the state back once, and queues more only after
   // rejections; a finished phase turns the queued rest into empty launches.
-  LmState* lm_host = nullptr;  // pinned, mapped (lm_map: the device's view)
-  LmState* lm_map = nullptr;
+  PinnedBuf lm_pin{true};      // one LmState, pinned, mapped: the last launch of a batch of trials writes it
+  LmState* lm_host() const { return lm_pin.as<LmState>(); }
   // spec (optional): launches queued behind every readback of the phase (before its event), gated on
   // the device LM state (spec_skip) -- phase 1 queues phase 2's outlier marking and structure there
   orbx_status optimize_dev(int iterations, const StopFlag& stop, const DevStop& dstop, hipStream_t st, int* iters,
@@ -513,14 +468,11 @@ struct LocalBA {
     BA_CHECK(ldlt.prepare((int)N));
     D.ldlt_pan = ldlt.pan ? 1 : 0;
     if (ldlt.sw_doubles() > 0) {
-      BA_CHECK(c.Sw.alloc(ldlt.sw_doubles()));
+      BA_CHECK(c.Sw.ensure(ldlt.sw_doubles()));
       D.Sw = c.Sw.p;
     }
-    BA_CHECK(c.lm.alloc(1));
-    if (!lm_host) {
-      BA_CHECK(hipHostMalloc((void**)&lm_host, sizeof(LmState), hipHostMallocMapped));
-      BA_CHECK(hipHostGetDevicePointer((void**)&lm_map, lm_host, 0));
-    }
+    BA_CHECK(c.lm.ensure(1));
+    BA_CHECK(lm_pin.ensure(sizeof(LmState)));
     const int gp = std::max((D.npa + D.nposes + LBS - 1) / LBS, 1);
     const int ga = std::max((D.na + LBS - 1) / LBS, 1);
     const int ge = std::max((D.na + LBS - 1) / LBS, 1);
@@ -590,29 +542,29 @@ struct LocalBA {
         // (slot 0 is not read by the trials; a batch that did not finish recomputes it later); the
         // launch writes the readback block and the LM state into mapped memory itself
         BaDev Dr = D0;
-        Dr.rb_out = rb_map;
-        Dr.lm_out = lm_map;
+        Dr.rb_out = rb.dev<double>();
+        Dr.lm_out = lm_pin.dev<LmState>();
         Dr.lm_copy = c.lm.p;
         hipLaunchKernelGGL(k_ba_errors, dim3(ge), dim3(LBS), 0, st, Dr, 0, 0);
         BA_CHECK(hipGetLastError());
         if (spec) BA_CHECK(spec());
         BA_CHECK(hipEventRecord(rb_ev, st));
         BA_CHECK(finish_read(sc));
-        if (lm_host->refresh) {  // paused on a NaN-rho rejection: pop, errors at the restored state, resume
+        if (lm_host()->refresh) {  // paused on a NaN-rho rejection: pop, errors at the restored state, resume
           hipLaunchKernelGGL(k_ba_restore, dim3(gp), dim3(LBS), 0, st, Dg);
           hipLaunchKernelGGL(k_ba_errors, dim3(ge), dim3(LBS), 0, st, Dg, 2, 0);
           hipLaunchKernelGGL(k_ba_lm_resume, dim3(1), dim3(64), 0, st, Dg);
           BA_CHECK(hipGetLastError());
-        } else if (lm_host->done) {
+        } else if (lm_host()->done) {
           break;
         }
-        budget = std::max(1, iterations - lm_host->it);
+        budget = std::max(1, iterations - lm_host()->it);
       }
       if (capt) BA_CHECK(cap.end());  // (the readback's event has passed: the stream is idle)
-      it = lm_host->it;
-      trials += lm_host->trials;
-      hook_stopped |= lm_host->stopped && D.raise_after >= 0;
-      if (lm_host->rejected) {  // ended on a rejected trial: its pop (chi above reads errors only)
+      it = lm_host()->it;
+      trials += lm_host()->trials;
+      hook_stopped |= lm_host()->stopped && D.raise_after >= 0;
+      if (lm_host()->rejected) {  // ended on a rejected trial: its pop (chi above reads errors only)
         hipLaunchKernelGGL(k_ba_restore, dim3(gp), dim3(LBS), 0, st, Dg);
         BA_CHECK(hipGetLastError());
       }
@@ -632,36 +584,24 @@ struct LocalBA {
   // in the call anyway -- copies the caller's flag into it while it waits for the device
   // (wait_event).  So the device never holds an address whose page the caller may free or
   // remap, and no registration outlives the call (or is shared between handles).
-  int* mirror = nullptr;  // pinned, mapped
+  PinnedBuf mirror{true};  // one int, pinned, mapped
   StopFlag mirror_src;    // the caller flag the mirror follows during a call (empty: none)
   bool map_stop(const StopFlag& s, DevStop* ds) {
     ds->i = nullptr;
     ds->b = nullptr;
     mirror_src = StopFlag{};
     if (!s.i && !s.b) return true;
-    void* dp = nullptr;
-    if (s.i && own_stop && (const void*)s.i == (const void*)own_stop) {
-      if (hipHostGetDevicePointer(&dp, own_stop, 0) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-      }
-      ds->i = (const int*)dp;
+    if (s.i && own_stop.p && (const void*)s.i == (const void*)own_stop.p) {
+      ds->i = own_stop.dev<const int>();
       return true;
     }
-    if (!mirror) {
-      if (hipHostMalloc((void**)&mirror, sizeof(int), hipHostMallocMapped) != hipSuccess) {
-        (void)hipGetLastError();
-        mirror = nullptr;
-        return false;
-      }
-    }
-    if (hipHostGetDevicePointer(&dp, mirror, 0) != hipSuccess) {
+    if (mirror.ensure(sizeof(int)) != hipSuccess) {
       (void)hipGetLastError();
       return false;
     }
     mirror_src = s;
-    *(volatile int*)mirror = s() ? 1 : 0;
-    ds->i = (const int*)dp;
+    *mirror.as<volatile int>() = s() ? 1 : 0;
+    ds->i = mirror.dev<const int>();
     return true;
   }
   void unmap_stop() { mirror_src = StopFlag{}; }
@@ -670,7 +610,7 @@ struct LocalBA {
     if (!mirror_src.i && !mirror_src.b) return hipEventSynchronize(ev);
     for (;;) {
       const int v = mirror_src() ? 1 : 0;
-      if (*(volatile int*)mirror != v) *(volatile int*)mirror = v;
+      if (*mirror.as<volatile int>() != v) *mirror.as<volatile int>() = v;
       const hipError_t q = hipEventQuery(ev);
       if (q != hipErrorNotReady) return q;
       std::this_thread::yield();

@@ -656,7 +656,7 @@ namespace {
 using orbx::InitJob;
 using orbx::InitRec;
 
-orbx::RansacDevice g_init_dev[64];
+orbx::RansacDevice* const g_init_dev = new orbx::RansacDevice[64];  // never deleted (orbx_mem.h)
 
 // Normalize (:1076-1131) over every keypoint of a frame: float accumulators in index order
 void init_normalize(const float* keys, int n, float* pn, float T[9]) {
@@ -692,7 +692,7 @@ struct orbx_initializer {
   int n1 = 0, iterations = 0;
   float K[9], sigma = 1.f, T1[9];
   std::vector<float> k1, pn1;
-  float* d_mem = nullptr;  // k1 | pn1
+  orbx::DevBuf<float> d_mem;  // k1 | pn1
 };
 
 namespace {
@@ -818,8 +818,8 @@ orbx_status init_run_device(orbx_initializer* h, const float* keys2_xy, InitCall
   std::memcpy(hp + o_m2, c.m2.data(), 4 * N);
   std::memcpy(hp + o_sets, c.sets.data(), 32 * its);
   InitJob& J = c.J;
-  J.k1 = h->d_mem;
-  J.pn1 = h->d_mem + 2 * n1;
+  J.k1 = h->d_mem.p;
+  J.pn1 = h->d_mem.p + 2 * n1;
   J.k2 = (const float*)(dp + o_k2);
   J.pn2 = (const float*)(dp + o_pn2);
   J.m1 = (const int*)(dp + o_m1);
@@ -969,14 +969,10 @@ orbx_status orbx_initializer_create(const float* keys1_xy, int n1, const float K
   init_fill(h, keys1_xy, n1, K, sigma, iterations);
   h->device = device;
   const size_t half = 8 * (size_t)n1;
-  if (hipMalloc((void**)&h->d_mem, 2 * half) != hipSuccess) {
-    delete h;
-    return ORBX_ERR_HIP;
-  }
-  if (hipMemcpyAsync(h->d_mem, h->k1.data(), half, hipMemcpyHostToDevice, dev.st) != hipSuccess ||
-      hipMemcpyAsync(h->d_mem + 2 * (size_t)n1, h->pn1.data(), half, hipMemcpyHostToDevice, dev.st) != hipSuccess ||
+  if (h->d_mem.ensure(4 * (size_t)n1) != hipSuccess ||
+      hipMemcpyAsync(h->d_mem.p, h->k1.data(), half, hipMemcpyHostToDevice, dev.st) != hipSuccess ||
+      hipMemcpyAsync(h->d_mem.p + 2 * (size_t)n1, h->pn1.data(), half, hipMemcpyHostToDevice, dev.st) != hipSuccess ||
       hipStreamSynchronize(dev.st) != hipSuccess) {
-    (void)hipFree(h->d_mem);
     delete h;
     return ORBX_ERR_HIP;
   }
@@ -986,10 +982,7 @@ orbx_status orbx_initializer_create(const float* keys1_xy, int n1, const float K
 
 orbx_status orbx_initializer_destroy(orbx_initializer* h) {
   if (!h) return ORBX_ERR_ARG;
-  if (h->device >= 0) {
-    (void)hipSetDevice(h->device);
-    if (h->d_mem) (void)hipFree(h->d_mem);
-  }
+  if (h->device >= 0) (void)hipSetDevice(h->device);
   delete h;
   return ORBX_OK;
 }

@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "../../include/orbx.h"
+#include "orbx_mem.h"
 
 namespace orbx {
 
@@ -338,8 +339,8 @@ using orbx::KfMeta;
 
 struct orbx_kfdb {
   int device = 0;
-  hipStream_t st = nullptr;
-  hipEvent_t ev = nullptr;  // end of the last queued query
+  orbx::Stream st;  // (declared first: destroyed after everything below)
+  orbx::Event ev;   // end of the last queued query
   bool ev_set = false;
   unsigned n_words = 0;
   // host mirrors (by slot; a slot is kept for every id ever seen, so its state survives erase + add)
@@ -351,32 +352,34 @@ struct orbx_kfdb {
   uint32_t next_seq = 0;
   int meta_lo = 0, meta_hi = 0, neigh_lo = 0, neigh_hi = 0;  // dirty slot ranges [lo, hi)
   bool live_dirty = false;
-  // device
-  uint32_t* d_words = nullptr;
-  double* d_vals = nullptr;
+  // device: the pool (repool replaces both)
+  orbx::DevBuf<uint32_t> d_words;
+  orbx::DevBuf<double> d_vals;
+  // the per-slot tables (slot_for grows them together)
   int slot_cap = 0;
-  KfMeta* d_meta = nullptr;
-  int32_t* d_neigh = nullptr;
-  unsigned long long *d_rq = nullptr, *d_lq = nullptr, *d_minkey = nullptr;
-  int32_t *d_rw = nullptr, *d_lw = nullptr;
-  float *d_rs = nullptr, *d_ls = nullptr;
-  uint8_t* d_conn = nullptr;
+  orbx::DevBuf<KfMeta> d_meta;
+  orbx::DevBuf<int32_t> d_neigh;
+  orbx::DevBuf<unsigned long long> d_rq, d_lq, d_minkey;
+  orbx::DevBuf<int32_t> d_rw, d_lw;
+  orbx::DevBuf<float> d_rs, d_ls;
+  orbx::DevBuf<uint8_t> d_conn;
+  // the per-live query scratch (flush grows it)
   int live_cap = 0;
-  int32_t* d_live = nullptr;
-  unsigned long long *d_key = nullptr, *d_wkey = nullptr;
-  float *d_si = nullptr, *d_acc = nullptr;
-  int32_t *d_flag = nullptr, *d_best = nullptr;
-  long long *d_wid = nullptr, *d_cand = nullptr;
-  uint32_t* d_bitmap = nullptr;
-  orbx::KfCtl* d_ctl = nullptr;
-  uint32_t* d_qw = nullptr;  // the host forms' query
-  double* d_qv = nullptr;
-  int32_t *d_qn = nullptr, *d_ncand = nullptr;
+  orbx::DevBuf<int32_t> d_live;
+  orbx::DevBuf<unsigned long long> d_key, d_wkey;
+  orbx::DevBuf<float> d_si, d_acc;
+  orbx::DevBuf<int32_t> d_flag, d_best;
+  orbx::DevBuf<long long> d_wid, d_cand;
+  // the fixed blocks (orbx_kfdb_create)
+  orbx::DevBuf<uint32_t> d_bitmap;
+  orbx::DevBuf<orbx::KfCtl> d_ctl;
+  orbx::DevBuf<uint32_t> d_qw;  // the host forms' query
+  orbx::DevBuf<double> d_qv;
+  orbx::DevBuf<int32_t> d_qn, d_ncand;
   int32_t h_qn = 0, h_ncand = 0;  // host ends of the two small copies: they outlive every early return
   // connected sets of the loop queries: pinned, read by the kernels in place
-  int32_t* h_conn[orbx::kKfdbConnRing] = {};
-  int conn_cap[orbx::kKfdbConnRing] = {};
-  hipEvent_t conn_ev[orbx::kKfdbConnRing] = {};
+  orbx::PinnedBuf h_conn[orbx::kKfdbConnRing];
+  orbx::Event conn_ev[orbx::kKfdbConnRing];
   bool conn_used[orbx::kKfdbConnRing] = {};
   int conn_next = 0;
 };
@@ -388,24 +391,27 @@ namespace {
     if ((x) != hipSuccess) return ORBX_ERR_HIP; \
   } while (0)
 
+// growth: the per-slot and per-live tables double from 1,024 entries, the pool holds twice what is asked
+// for and at least 65,536 entries, a connected-set ring block twice the set and at least 256 slots
+constexpr int table_slots(int n) { return 2 * n > 1024 ? 2 * n : 1024; }
+constexpr long long pool_entries(long long n) { return 2 * n > (1 << 16) ? 2 * n : 1 << 16; }
+constexpr size_t conn_slots(int n) { return 2 * n > 256 ? 2 * (size_t)n : 256; }
+
 // a fresh array of new_n entries in place of *p, zeroed and/or holding the first old_n of the old one.  The
 // fill and the copy go to st (the handle's own stream) and are waited for here, so whichever stream
-// touches the array next finds them done; the caller has made sure nothing queued still reads *p.
+// touches the array next finds them done, and only then is the new array swapped in; the caller has made
+// sure nothing queued still reads *p (wait_queued).  On failure *p is untouched.
 template <class T>
-hipError_t grow(T** p, size_t old_n, size_t new_n, bool keep, bool zero, hipStream_t st) {
-  T* q = nullptr;
-  hipError_t e = hipMalloc((void**)&q, std::max<size_t>(new_n, 1) * sizeof(T));
+hipError_t grow(orbx::DevBuf<T>* p, size_t old_n, size_t new_n, bool keep, bool zero, hipStream_t st) {
+  orbx::DevBuf<T> q;
+  hipError_t e = q.ensure(new_n);
   if (e != hipSuccess) return e;
-  const bool copy = keep && *p && old_n;
-  if (zero) e = hipMemsetAsync(q, 0, std::max<size_t>(new_n, 1) * sizeof(T), st);
-  if (e == hipSuccess && copy) e = hipMemcpyAsync(q, *p, old_n * sizeof(T), hipMemcpyDeviceToDevice, st);
+  const bool copy = keep && p->p && old_n;
+  if (zero) e = hipMemsetAsync(q.p, 0, q.n * sizeof(T), st);
+  if (e == hipSuccess && copy) e = hipMemcpyAsync(q.p, p->p, old_n * sizeof(T), hipMemcpyDeviceToDevice, st);
   if (e == hipSuccess && (zero || copy)) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) {
-    (void)hipFree(q);
-    return e;
-  }
-  if (*p) (void)hipFree(*p);
-  *p = q;
+  if (e != hipSuccess) return e;  // (*p is still in place; q goes)
+  p->swap(q);                     // the old array goes with q
   return hipSuccess;
 }
 
@@ -424,7 +430,7 @@ orbx_status slot_for(orbx_kfdb* db, long long id, int* out) {
   }
   const int s = (int)db->meta.size();
   if (s >= db->slot_cap) {
-    const int oc = db->slot_cap, nc = std::max(1024, 2 * oc);
+    const int oc = db->slot_cap, nc = table_slots(oc);
     KF_CHECK(grow(&db->d_meta, oc, nc, false, true, db->st));
     KF_CHECK(grow(&db->d_neigh, (size_t)oc * 10, (size_t)nc * 10, false, false, db->st));
     KF_CHECK(grow(&db->d_rq, oc, nc, true, true, db->st));
@@ -461,18 +467,18 @@ void touch_meta(orbx_kfdb* db, int s) {
 // uploads what changed in the mirrors and sizes the per-query scratch, on stream s
 orbx_status flush(orbx_kfdb* db, hipStream_t s) {
   if (db->meta_hi > db->meta_lo) {
-    KF_CHECK(hipMemcpyAsync(db->d_meta + db->meta_lo, db->meta.data() + db->meta_lo,
+    KF_CHECK(hipMemcpyAsync(db->d_meta.p + db->meta_lo, db->meta.data() + db->meta_lo,
                             sizeof(KfMeta) * (size_t)(db->meta_hi - db->meta_lo), hipMemcpyHostToDevice, s));
     db->meta_lo = db->meta_hi = 0;
   }
   if (db->neigh_hi > db->neigh_lo) {
-    KF_CHECK(hipMemcpyAsync(db->d_neigh + (size_t)db->neigh_lo * 10, db->neigh.data() + (size_t)db->neigh_lo * 10,
+    KF_CHECK(hipMemcpyAsync(db->d_neigh.p + (size_t)db->neigh_lo * 10, db->neigh.data() + (size_t)db->neigh_lo * 10,
                             40 * (size_t)(db->neigh_hi - db->neigh_lo), hipMemcpyHostToDevice, s));
     db->neigh_lo = db->neigh_hi = 0;
   }
   const int nl = (int)db->live.size();
   if (nl > db->live_cap) {  // only after an add, which waited for every queued query
-    const int nc = std::max(1024, 2 * nl);
+    const int nc = table_slots(nl);
     KF_CHECK(grow(&db->d_live, 0, nc, false, false, db->st));
     KF_CHECK(grow(&db->d_key, 0, nc, false, false, db->st));
     KF_CHECK(grow(&db->d_wkey, 0, nc, false, false, db->st));
@@ -486,37 +492,37 @@ orbx_status flush(orbx_kfdb* db, hipStream_t s) {
     db->live_dirty = true;
   }
   if (db->live_dirty && nl > 0)
-    KF_CHECK(hipMemcpyAsync(db->d_live, db->live.data(), 4 * (size_t)nl, hipMemcpyHostToDevice, s));
+    KF_CHECK(hipMemcpyAsync(db->d_live.p, db->live.data(), 4 * (size_t)nl, hipMemcpyHostToDevice, s));
   db->live_dirty = false;
   return ORBX_OK;
 }
 
 orbx::KfDev dev_view(const orbx_kfdb* db) {
   orbx::KfDev D{};
-  D.words = db->d_words;
-  D.vals = db->d_vals;
-  D.meta = db->d_meta;
-  D.live = db->d_live;
+  D.words = db->d_words.p;
+  D.vals = db->d_vals.p;
+  D.meta = db->d_meta.p;
+  D.live = db->d_live.p;
   D.n_live = (int)db->live.size();
-  D.neigh = db->d_neigh;
-  D.rq = db->d_rq;
-  D.rw = db->d_rw;
-  D.rs = db->d_rs;
-  D.lq = db->d_lq;
-  D.lw = db->d_lw;
-  D.ls = db->d_ls;
-  D.bitmap = db->d_bitmap;
+  D.neigh = db->d_neigh.p;
+  D.rq = db->d_rq.p;
+  D.rw = db->d_rw.p;
+  D.rs = db->d_rs.p;
+  D.lq = db->d_lq.p;
+  D.lw = db->d_lw.p;
+  D.ls = db->d_ls.p;
+  D.bitmap = db->d_bitmap.p;
   D.n_words = db->n_words;
-  D.conn = db->d_conn;
-  D.minkey = db->d_minkey;
-  D.key = db->d_key;
-  D.si = db->d_si;
-  D.flag = db->d_flag;
-  D.acc = db->d_acc;
-  D.best = db->d_best;
-  D.wkey = db->d_wkey;
-  D.wid = db->d_wid;
-  D.ctl = db->d_ctl;
+  D.conn = db->d_conn.p;
+  D.minkey = db->d_minkey.p;
+  D.key = db->d_key.p;
+  D.si = db->d_si.p;
+  D.flag = db->d_flag.p;
+  D.acc = db->d_acc.p;
+  D.best = db->d_best.p;
+  D.wkey = db->d_wkey.p;
+  D.wid = db->d_wid.p;
+  D.ctl = db->d_ctl.p;
   return D;
 }
 
@@ -532,39 +538,31 @@ orbx_status repool(orbx_kfdb* db, long long extra) {
     new_off[i] = used;
     used += db->meta[order[i]].len;
   }
-  const long long cap = std::max<long long>(2 * (used + extra), 1 << 16);
-  uint32_t* w1 = nullptr;
-  double* v1 = nullptr;
-  long long* d_off = nullptr;
-  int32_t* d_order = nullptr;
-  hipError_t e = hipMalloc((void**)&w1, 4 * (size_t)cap);
-  if (e == hipSuccess) e = hipMalloc((void**)&v1, 8 * (size_t)cap);
+  const long long cap = pool_entries(used + extra);
+  orbx::DevBuf<uint32_t> w1;
+  orbx::DevBuf<double> v1;
+  orbx::DevBuf<long long> d_off;
+  orbx::DevBuf<int32_t> d_order;
+  hipError_t e = w1.ensure((size_t)cap);
+  if (e == hipSuccess) e = v1.ensure((size_t)cap);
   if (e == hipSuccess && nl > 0 && used > 0) {
     // the device still holds the old offsets: push pending mirror changes first
     orbx_status st = flush(db, db->st);
     if (st != ORBX_OK) e = hipErrorUnknown;
-    if (e == hipSuccess) e = hipMalloc((void**)&d_off, 8 * (size_t)nl);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_order, 4 * (size_t)nl);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_off, new_off.data(), 8 * (size_t)nl, hipMemcpyHostToDevice, db->st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_order, order.data(), 4 * (size_t)nl, hipMemcpyHostToDevice, db->st);
+    if (e == hipSuccess) e = d_off.ensure((size_t)nl);
+    if (e == hipSuccess) e = d_order.ensure((size_t)nl);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_off.p, new_off.data(), 8 * (size_t)nl, hipMemcpyHostToDevice, db->st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_order.p, order.data(), 4 * (size_t)nl, hipMemcpyHostToDevice, db->st);
     if (e == hipSuccess) {
-      hipLaunchKernelGGL(orbx::k_kfdb_compact, dim3(nl), dim3(256), 0, db->st, db->d_meta, d_order, d_off,
-                         db->d_words, db->d_vals, w1, v1);
+      hipLaunchKernelGGL(orbx::k_kfdb_compact, dim3(nl), dim3(256), 0, db->st, db->d_meta.p, d_order.p, d_off.p,
+                         db->d_words.p, db->d_vals.p, w1.p, v1.p);
       e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(db->st);
-    if (d_off) (void)hipFree(d_off);
-    if (d_order) (void)hipFree(d_order);
   }
-  if (e != hipSuccess) {
-    if (w1) (void)hipFree(w1);
-    if (v1) (void)hipFree(v1);
-    return ORBX_ERR_HIP;
-  }
-  if (db->d_words) (void)hipFree(db->d_words);
-  if (db->d_vals) (void)hipFree(db->d_vals);
-  db->d_words = w1;
-  db->d_vals = v1;
+  if (e != hipSuccess) return ORBX_ERR_HIP;
+  db->d_words.swap(w1);  // (the old pool goes with w1, v1)
+  db->d_vals.swap(v1);
   db->pool_cap = cap;
   db->pool_used = used;
   db->pool_dead = 0;
@@ -585,7 +583,7 @@ bool query_ok(const uint32_t* words, const double* values, int n, unsigned n_wor
 }
 
 hipStream_t pick_stream(orbx_kfdb* db, void* stream) {
-  return stream == ORBX_STREAM_NULL ? (hipStream_t)0 : stream ? (hipStream_t)stream : db->st;
+  return stream == ORBX_STREAM_NULL ? (hipStream_t)0 : stream ? (hipStream_t)stream : db->st.st;
 }
 
 // queues one query on s: no host synchronisation (but see the connected-set ring)
@@ -597,7 +595,7 @@ orbx_status enqueue_query(orbx_kfdb* db, hipStream_t s, int loop, unsigned long 
   if (fs != ORBX_OK) return fs;
   const int nl = (int)db->live.size();
   if (cap < 0) {  // the host forms: the handle's own list, one entry per live keyframe, the most there can be
-    d_cand = db->d_cand;
+    d_cand = db->d_cand.p;
     cap = db->live_cap;
   }
   if (nl == 0) {
@@ -618,20 +616,15 @@ orbx_status enqueue_query(orbx_kfdb* db, hipStream_t s, int loop, unsigned long 
       ring = db->conn_next;
       db->conn_next = (ring + 1) % orbx::kKfdbConnRing;
       if (db->conn_used[ring]) KF_CHECK(hipEventSynchronize(db->conn_ev[ring]));  // its last reader is done
-      if (n_connected > db->conn_cap[ring]) {
-        if (db->h_conn[ring]) (void)hipHostFree(db->h_conn[ring]);
-        db->h_conn[ring] = nullptr;
-        db->conn_cap[ring] = 0;
-        const int nc = std::max(256, 2 * n_connected);
-        KF_CHECK(hipHostMalloc((void**)&db->h_conn[ring], 4 * (size_t)nc, hipHostMallocDefault));
-        db->conn_cap[ring] = nc;
-      }
+      orbx::PinnedBuf& block = db->h_conn[ring];
+      if (4 * (size_t)n_connected > block.cap) KF_CHECK(block.ensure(4 * conn_slots(n_connected)));
+      int32_t* const conn = block.as<int32_t>();
       int k = 0;
       for (int i = 0; i < n_connected; i++) {
         auto it = db->slot_of.find(connected[i]);
-        if (it != db->slot_of.end()) db->h_conn[ring][k++] = it->second;
+        if (it != db->slot_of.end()) conn[k++] = it->second;
       }
-      Q.conn_list = db->h_conn[ring];
+      Q.conn_list = conn;
       Q.n_conn = k;
     }
     const orbx::KfDev D = dev_view(db);
@@ -664,14 +657,14 @@ orbx_status host_query(orbx_kfdb* db, int loop, unsigned long long qid, const ui
   KF_CHECK(hipSetDevice(db->device));
   db->h_qn = n;
   if (n > 0) {
-    KF_CHECK(hipMemcpyAsync(db->d_qw, words, 4 * (size_t)n, hipMemcpyHostToDevice, db->st));
-    KF_CHECK(hipMemcpyAsync(db->d_qv, values, 8 * (size_t)n, hipMemcpyHostToDevice, db->st));
+    KF_CHECK(hipMemcpyAsync(db->d_qw.p, words, 4 * (size_t)n, hipMemcpyHostToDevice, db->st));
+    KF_CHECK(hipMemcpyAsync(db->d_qv.p, values, 8 * (size_t)n, hipMemcpyHostToDevice, db->st));
   }
-  hipError_t e = hipMemcpyAsync(db->d_qn, &db->h_qn, 4, hipMemcpyHostToDevice, db->st);
-  orbx_status qs = e == hipSuccess ? enqueue_query(db, db->st, loop, qid, db->d_qw, db->d_qv, db->d_qn, connected,
-                                                   n_connected, min_score, nullptr, -1, db->d_ncand)
+  hipError_t e = hipMemcpyAsync(db->d_qn.p, &db->h_qn, 4, hipMemcpyHostToDevice, db->st);
+  orbx_status qs = e == hipSuccess ? enqueue_query(db, db->st, loop, qid, db->d_qw.p, db->d_qv.p, db->d_qn.p,
+                                                   connected, n_connected, min_score, nullptr, -1, db->d_ncand.p)
                                    : ORBX_ERR_HIP;
-  if (qs == ORBX_OK && hipMemcpyAsync(&db->h_ncand, db->d_ncand, 4, hipMemcpyDeviceToHost, db->st) != hipSuccess)
+  if (qs == ORBX_OK && hipMemcpyAsync(&db->h_ncand, db->d_ncand.p, 4, hipMemcpyDeviceToHost, db->st) != hipSuccess)
     qs = ORBX_ERR_HIP;
   // one synchronisation on every path: the caller's words / values are free again on return
   if (hipStreamSynchronize(db->st) != hipSuccess) qs = ORBX_ERR_HIP;
@@ -679,7 +672,7 @@ orbx_status host_query(orbx_kfdb* db, int loop, unsigned long long qid, const ui
   const int32_t m = db->h_ncand;
   *n_cand = m;
   if (m > cap) return ORBX_ERR_CAPACITY;
-  if (m > 0) KF_CHECK(hipMemcpy(cand, db->d_cand, 8 * (size_t)m, hipMemcpyDeviceToHost));
+  if (m > 0) KF_CHECK(hipMemcpy(cand, db->d_cand.p, 8 * (size_t)m, hipMemcpyDeviceToHost));
   return ORBX_OK;
 }
 
@@ -707,10 +700,9 @@ orbx_status orbx_kfdb_create(const orbx_voc* voc, int device, orbx_kfdb** out) {
   db->device = device;
   db->n_words = (unsigned)info[5];
   const size_t bm = ((size_t)db->n_words + 31) / 32 + 1;
-  hipError_t e = hipStreamCreateWithFlags(&db->st, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&db->ev, hipEventDisableTiming);
-  for (int i = 0; i < orbx::kKfdbConnRing && e == hipSuccess; i++)
-    e = hipEventCreateWithFlags(&db->conn_ev[i], hipEventDisableTiming);
+  hipError_t e = db->st.ensure();
+  if (e == hipSuccess) e = db->ev.ensure();
+  for (int i = 0; i < orbx::kKfdbConnRing && e == hipSuccess; i++) e = db->conn_ev[i].ensure();
   if (e == hipSuccess) e = grow(&db->d_bitmap, 0, bm, false, true, db->st);
   if (e == hipSuccess) e = grow(&db->d_ctl, 0, 1, false, true, db->st);
   if (e == hipSuccess) e = grow(&db->d_qw, 0, orbx::kKfdbMaxQuery, false, true, db->st);
@@ -730,18 +722,6 @@ orbx_status orbx_kfdb_destroy(orbx_kfdb* db) {
   (void)hipSetDevice(db->device);
   if (db->ev_set) (void)hipEventSynchronize(db->ev);
   if (db->st) (void)hipStreamSynchronize(db->st);
-  void* frees[] = {db->d_words, db->d_vals, db->d_meta, db->d_neigh, db->d_rq,   db->d_lq,     db->d_minkey,
-                   db->d_rw,    db->d_lw,   db->d_rs,   db->d_ls,    db->d_conn, db->d_live,   db->d_key,
-                   db->d_wkey,  db->d_si,   db->d_acc,  db->d_flag,  db->d_best, db->d_wid,    db->d_cand,
-                   db->d_bitmap, db->d_ctl, db->d_qw,   db->d_qv,    db->d_qn,   db->d_ncand};
-  for (void* p : frees)
-    if (p) (void)hipFree(p);
-  for (int i = 0; i < orbx::kKfdbConnRing; i++) {
-    if (db->h_conn[i]) (void)hipHostFree(db->h_conn[i]);
-    if (db->conn_ev[i]) (void)hipEventDestroy(db->conn_ev[i]);
-  }
-  if (db->ev) (void)hipEventDestroy(db->ev);
-  if (db->st) (void)hipStreamDestroy(db->st);
   delete db;
   return ORBX_OK;
 }
@@ -764,8 +744,8 @@ orbx_status orbx_kfdb_add(orbx_kfdb* db, int64_t kf_id, const uint32_t* words, c
     if (s != ORBX_OK) return s;
   }
   if (n > 0) {
-    KF_CHECK(hipMemcpyAsync(db->d_words + db->pool_used, words, 4 * (size_t)n, hipMemcpyHostToDevice, db->st));
-    KF_CHECK(hipMemcpyAsync(db->d_vals + db->pool_used, values, 8 * (size_t)n, hipMemcpyHostToDevice, db->st));
+    KF_CHECK(hipMemcpyAsync(db->d_words.p + db->pool_used, words, 4 * (size_t)n, hipMemcpyHostToDevice, db->st));
+    KF_CHECK(hipMemcpyAsync(db->d_vals.p + db->pool_used, values, 8 * (size_t)n, hipMemcpyHostToDevice, db->st));
     KF_CHECK(hipStreamSynchronize(db->st));  // the caller's arrays are free again on return
   }
   KfMeta& m = db->meta[slot];
@@ -816,12 +796,12 @@ orbx_status orbx_kfdb_clear(orbx_kfdb* db) {
   if (s != ORBX_OK) return s;
   const size_t nc = (size_t)db->slot_cap;
   if (nc) {
-    KF_CHECK(hipMemsetAsync(db->d_rq, 0, 8 * nc, db->st));
-    KF_CHECK(hipMemsetAsync(db->d_lq, 0, 8 * nc, db->st));
-    KF_CHECK(hipMemsetAsync(db->d_rw, 0, 4 * nc, db->st));
-    KF_CHECK(hipMemsetAsync(db->d_lw, 0, 4 * nc, db->st));
-    KF_CHECK(hipMemsetAsync(db->d_rs, 0, 4 * nc, db->st));
-    KF_CHECK(hipMemsetAsync(db->d_ls, 0, 4 * nc, db->st));
+    KF_CHECK(hipMemsetAsync(db->d_rq.p, 0, 8 * nc, db->st));
+    KF_CHECK(hipMemsetAsync(db->d_lq.p, 0, 8 * nc, db->st));
+    KF_CHECK(hipMemsetAsync(db->d_rw.p, 0, 4 * nc, db->st));
+    KF_CHECK(hipMemsetAsync(db->d_lw.p, 0, 4 * nc, db->st));
+    KF_CHECK(hipMemsetAsync(db->d_rs.p, 0, 4 * nc, db->st));
+    KF_CHECK(hipMemsetAsync(db->d_ls.p, 0, 4 * nc, db->st));
     KF_CHECK(hipStreamSynchronize(db->st));  // done before a query on any other stream can start
   }
   db->slot_of.clear();
@@ -915,30 +895,26 @@ orbx_status orbx_kfdb_score(orbx_kfdb* db, const uint32_t* words, const double* 
   if (db->ev_set) KF_CHECK(hipStreamWaitEvent(s, db->ev, 0));
   orbx_status fs = flush(db, s);
   if (fs != ORBX_OK) return fs;
-  int32_t* d_slots = nullptr;
-  double* d_out = nullptr;
-  hipError_t e = hipMalloc((void**)&d_slots, 4 * (size_t)n_kfs);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_out, 8 * (size_t)n_kfs);
+  orbx::DevBuf<int32_t> d_slots;
+  orbx::DevBuf<double> d_out;
+  hipError_t e = d_slots.ensure((size_t)n_kfs);
+  if (e == hipSuccess) e = d_out.ensure((size_t)n_kfs);
   db->h_qn = n;
-  if (e == hipSuccess && n > 0) e = hipMemcpyAsync(db->d_qw, words, 4 * (size_t)n, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess && n > 0) e = hipMemcpyAsync(db->d_qv, values, 8 * (size_t)n, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(db->d_qn, &db->h_qn, 4, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_slots, slots.data(), 4 * (size_t)n_kfs, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && n > 0) e = hipMemcpyAsync(db->d_qw.p, words, 4 * (size_t)n, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && n > 0) e = hipMemcpyAsync(db->d_qv.p, values, 8 * (size_t)n, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(db->d_qn.p, &db->h_qn, 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_slots.p, slots.data(), 4 * (size_t)n_kfs, hipMemcpyHostToDevice, s);
   if (e == hipSuccess) {
     const orbx::KfDev D = dev_view(db);
     const int qb = orbx::kKfdbMaxQuery / 256;
-    hipLaunchKernelGGL(orbx::k_kfdb_bitmap, dim3(qb), dim3(256), 0, s, db->d_bitmap, db->n_words, db->d_qw, db->d_qn,
-                       0);
-    hipLaunchKernelGGL(orbx::k_kfdb_score, dim3((n_kfs + 3) / 4), dim3(256), 0, s, D, db->d_qw, db->d_qv, db->d_qn,
-                       d_slots, n_kfs, d_out);
-    hipLaunchKernelGGL(orbx::k_kfdb_bitmap, dim3(qb), dim3(256), 0, s, db->d_bitmap, db->n_words, db->d_qw, db->d_qn,
-                       1);
+    hipLaunchKernelGGL(orbx::k_kfdb_bitmap, dim3(qb), dim3(256), 0, s, D.bitmap, D.n_words, db->d_qw.p, db->d_qn.p, 0);
+    hipLaunchKernelGGL(orbx::k_kfdb_score, dim3((n_kfs + 3) / 4), dim3(256), 0, s, D, db->d_qw.p, db->d_qv.p,
+                       db->d_qn.p, d_slots.p, n_kfs, d_out.p);
+    hipLaunchKernelGGL(orbx::k_kfdb_bitmap, dim3(qb), dim3(256), 0, s, D.bitmap, D.n_words, db->d_qw.p, db->d_qn.p, 1);
     e = hipGetLastError();
   }
-  if (e == hipSuccess) e = hipMemcpyAsync(scores, d_out, 8 * (size_t)n_kfs, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(scores, d_out.p, 8 * (size_t)n_kfs, hipMemcpyDeviceToHost, s);
   const hipError_t e2 = hipStreamSynchronize(s);
-  if (d_slots) (void)hipFree(d_slots);
-  if (d_out) (void)hipFree(d_out);
   return (e == hipSuccess && e2 == hipSuccess) ? ORBX_OK : ORBX_ERR_HIP;
 }
 
@@ -961,27 +937,27 @@ orbx_status orbx_kfdb_read_state(orbx_kfdb* db, const int64_t* kf_ids, int n, ui
   std::vector<int32_t> w(ns);
   std::vector<float> f(ns);
   if (reloc_query) {
-    KF_CHECK(hipMemcpy(q.data(), db->d_rq, 8 * ns, hipMemcpyDeviceToHost));
+    KF_CHECK(hipMemcpy(q.data(), db->d_rq.p, 8 * ns, hipMemcpyDeviceToHost));
     for (int i = 0; i < n; i++) reloc_query[i] = q[slots[i]];
   }
   if (loop_query) {
-    KF_CHECK(hipMemcpy(q.data(), db->d_lq, 8 * ns, hipMemcpyDeviceToHost));
+    KF_CHECK(hipMemcpy(q.data(), db->d_lq.p, 8 * ns, hipMemcpyDeviceToHost));
     for (int i = 0; i < n; i++) loop_query[i] = q[slots[i]];
   }
   if (reloc_words) {
-    KF_CHECK(hipMemcpy(w.data(), db->d_rw, 4 * ns, hipMemcpyDeviceToHost));
+    KF_CHECK(hipMemcpy(w.data(), db->d_rw.p, 4 * ns, hipMemcpyDeviceToHost));
     for (int i = 0; i < n; i++) reloc_words[i] = w[slots[i]];
   }
   if (loop_words) {
-    KF_CHECK(hipMemcpy(w.data(), db->d_lw, 4 * ns, hipMemcpyDeviceToHost));
+    KF_CHECK(hipMemcpy(w.data(), db->d_lw.p, 4 * ns, hipMemcpyDeviceToHost));
     for (int i = 0; i < n; i++) loop_words[i] = w[slots[i]];
   }
   if (reloc_score) {
-    KF_CHECK(hipMemcpy(f.data(), db->d_rs, 4 * ns, hipMemcpyDeviceToHost));
+    KF_CHECK(hipMemcpy(f.data(), db->d_rs.p, 4 * ns, hipMemcpyDeviceToHost));
     for (int i = 0; i < n; i++) reloc_score[i] = f[slots[i]];
   }
   if (loop_score) {
-    KF_CHECK(hipMemcpy(f.data(), db->d_ls, 4 * ns, hipMemcpyDeviceToHost));
+    KF_CHECK(hipMemcpy(f.data(), db->d_ls.p, 4 * ns, hipMemcpyDeviceToHost));
     for (int i = 0; i < n; i++) loop_score[i] = f[slots[i]];
   }
   return ORBX_OK;

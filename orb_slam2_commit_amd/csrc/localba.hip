@@ -163,7 +163,7 @@ orbx_status ba_intake(LocalBA& L, const orbx_ba_problem* pb, hipStream_t st, con
   const size_t o_X = 0, o_eobs = o_X + rnd(24 * (size_t)np), o_einfo = o_eobs + rnd(24 * (size_t)ne),
                o_edelta = o_einfo + rnd(8 * (size_t)ne), o_edsqr = o_edelta + rnd(8 * (size_t)ne),
                o_est = o_edsqr + rnd(4 * (size_t)ne), o_erob = o_est + rnd(ne), o_end = o_erob + rnd(ne);
-  BA_CHECK(c.prob.alloc(o_end));
+  BA_CHECK(c.prob.ensure(o_end));
   double* X = reinterpret_cast<double*>(c.prob.p + o_X);
   double* eobs = reinterpret_cast<double*>(c.prob.p + o_eobs);
   double* einfo = reinterpret_cast<double*>(c.prob.p + o_einfo);
@@ -201,9 +201,9 @@ orbx_status ba_intake(LocalBA& L, const orbx_ba_problem* pb, hipStream_t st, con
     }
   }
   BA_CHECK(A.upload(st));
-  BA_CHECK(c.cbak.alloc(7 * (size_t)nc));
-  BA_CHECK(c.Xbak.alloc(3 * (size_t)np));
-  BA_CHECK(c.eerr.alloc(3 * (size_t)ne));
+  BA_CHECK(c.cbak.ensure(7 * (size_t)nc));
+  BA_CHECK(c.Xbak.ensure(3 * (size_t)np));
+  BA_CHECK(c.eerr.ensure(3 * (size_t)ne));
   {
     const float thMono = kn.th_mono, thStereo = kn.th_stereo;
     const int gpre = (std::max(ne, 3 * np) + LBS - 1) / LBS;
@@ -213,8 +213,8 @@ orbx_status ba_intake(LocalBA& L, const orbx_ba_problem* pb, hipStream_t st, con
     BA_CHECK(hipGetLastError());
     if (!kn.robust && ne > 0) BA_CHECK(hipMemsetAsync(erob, 0, ne, st));  // no edge carries a kernel
   }
-  BA_CHECK(c.flag.alloc(ne));
-  BA_CHECK(c.scal.alloc(8));
+  BA_CHECK(c.flag.ensure(ne));
+  BA_CHECK(c.scal.ensure(8));
   D.cq = cq;
   D.ct = ct;
   D.cbak = c.cbak.p;
@@ -341,7 +341,7 @@ orbx_status run_local_ba(LocalBA& L, const orbx_ba_problem* pb, orbx_ba_result* 
     // did the speculative phase-2 launches run (spec_skip's condition: phase 1 ended done, nothing to
     // pop or refresh, and not on the stop flag)?
     const bool spec_ran =
-        spec2 && L.lm_host->done && !L.lm_host->refresh && !L.lm_host->rejected && !L.lm_host->stopped;
+        spec2 && L.lm_host()->done && !L.lm_host()->refresh && !L.lm_host()->rejected && !L.lm_host()->stopped;
     tm[2] = tm[3] = tm[4] = std::chrono::steady_clock::now();
     if (!(stop()) && !L.hook_stopped) {
       // :764-802 level-1 outliers, drop robust kernels (already done on the device when spec_ran)
@@ -353,7 +353,7 @@ orbx_status run_local_ba(LocalBA& L, const orbx_ba_problem* pb, orbx_ba_result* 
       }
       const auto tb2 = std::chrono::steady_clock::now();
       if (spec_ran) {
-        const int* sz = L.sint_host;  // written by the speculative k_ba_struct_scan before the readback's event
+        const int* sz = L.sint.as<int>();  // written by the speculative k_ba_struct_scan before the readback's event
         s = L.finish_structure(sz[0], sz[1], sz[2], sz[3], sz[4], st);
       } else {
         s = L.build_structure(0, st);
@@ -399,14 +399,11 @@ namespace orbx {
 // partitions and reduction orders are those of the single-problem device LM
 // loop, so every problem's result is bit-identical to running it alone.
 struct BaBatch {
-  DBuf<BaDev> dev;       // [Dg_0..Dg_K-1, D0_0..D0_K-1]
-  DBuf<LmState> lm;      // K
-  LmState* lm_host = nullptr;
-  int cap = 0;
+  DevBuf<BaDev> dev;       // [Dg_0..Dg_K-1, D0_0..D0_K-1]
+  DevBuf<LmState> lm;      // K
+  PinnedBuf lm_pin;
+  LmState* lm_host() const { return lm_pin.as<LmState>(); }  // K states
   std::vector<BaDev> hostD;
-  ~BaBatch() {
-    if (lm_host) (void)hipHostFree(lm_host);
-  }
 };
 
 orbx_status optimize_many(LocalBA* const* Ls, int K, BaBatch& B, int iterations, const StopFlag& stop,
@@ -445,15 +442,9 @@ orbx_status optimize_many(LocalBA* const* Ls, int K, BaBatch& B, int iterations,
   }
   const bool camfold = true;
   int n_ps = 0, n_psfold = 0;  // problems that launch k_ba_point_schur / whose k_ba_lin_schur takes it
-  if (B.cap < K) {
-    if (B.lm_host) (void)hipHostFree(B.lm_host);
-    B.lm_host = nullptr;
-    B.cap = 0;
-    BA_CHECK(hipHostMalloc((void**)&B.lm_host, sizeof(LmState) * K, hipHostMallocDefault));
-    B.cap = K;
-  }
-  BA_CHECK(B.lm.alloc(K));
-  BA_CHECK(B.dev.alloc(2 * (size_t)K));
+  BA_CHECK(B.lm_pin.ensure(sizeof(LmState) * K));
+  BA_CHECK(B.lm.ensure(K));
+  BA_CHECK(B.dev.ensure(2 * (size_t)K));
   B.hostD.resize(2 * (size_t)K);
   for (int i = 0; i < K; i++) {
     B.hostD[i] = Ls[i]->D;
@@ -513,14 +504,14 @@ orbx_status optimize_many(LocalBA* const* Ls, int K, BaBatch& B, int iterations,
       hipLaunchKernelGGL(k_ba_errors_many, dim3(geM, 1, K), dim3(LBS), 0, st, D0, 0, 0);
       hipLaunchKernelGGL(k_ba_lm_final_many, dim3(1, 1, K), dim3(64), 0, st, Dg);
       BA_CHECK(hipGetLastError());
-      BA_CHECK(hipMemcpyAsync(B.lm_host, B.lm.p, sizeof(LmState) * K, hipMemcpyDeviceToHost, st));
+      BA_CHECK(hipMemcpyAsync(B.lm_host(), B.lm.p, sizeof(LmState) * K, hipMemcpyDeviceToHost, st));
       BA_CHECK(hipEventRecord(Ls[0]->rb_ev, st));
       BA_CHECK(Ls[0]->wait_event(Ls[0]->rb_ev));  // keeps the device's stop mirror current
       int left = 0;
       bool refresh = false;
       for (int i = 0; i < K; i++) {
-        if (!B.lm_host[i].done || B.lm_host[i].refresh) left = std::max(left, iterations - B.lm_host[i].it);
-        refresh |= B.lm_host[i].refresh != 0;
+        if (!B.lm_host()[i].done || B.lm_host()[i].refresh) left = std::max(left, iterations - B.lm_host()[i].it);
+        refresh |= B.lm_host()[i].refresh != 0;
       }
       if (left == 0) break;
       if (refresh) {  // problems paused on a NaN-rho rejection (all three launches gated per problem)
@@ -533,10 +524,10 @@ orbx_status optimize_many(LocalBA* const* Ls, int K, BaBatch& B, int iterations,
     }
     bool rej = false;
     for (int i = 0; i < K; i++) {
-      iters[i] = B.lm_host[i].it;
-      Ls[i]->trials += B.lm_host[i].trials;
-      chis[i] = B.lm_host[i].final_chi;
-      rej |= B.lm_host[i].rejected != 0;
+      iters[i] = B.lm_host()[i].it;
+      Ls[i]->trials += B.lm_host()[i].trials;
+      chis[i] = B.lm_host()[i].final_chi;
+      rej |= B.lm_host()[i].rejected != 0;
     }
     if (rej) {  // the pops of problems that ended on a rejected trial (gated per problem)
       hipLaunchKernelGGL(k_ba_restore_many, dim3(gpM, 1, K), dim3(LBS), 0, st, Dg);
@@ -546,9 +537,9 @@ orbx_status optimize_many(LocalBA* const* Ls, int K, BaBatch& B, int iterations,
     hipLaunchKernelGGL(k_ba_errors_many, dim3(geM, 1, K), dim3(LBS), 0, st, D0, 0, 0);
     hipLaunchKernelGGL(k_ba_lm_final_many, dim3(1, 1, K), dim3(64), 0, st, Dg);
     BA_CHECK(hipGetLastError());
-    BA_CHECK(hipMemcpyAsync(B.lm_host, B.lm.p, sizeof(LmState) * K, hipMemcpyDeviceToHost, st));
+    BA_CHECK(hipMemcpyAsync(B.lm_host(), B.lm.p, sizeof(LmState) * K, hipMemcpyDeviceToHost, st));
     BA_CHECK(hipStreamSynchronize(st));
-    for (int i = 0; i < K; i++) chis[i] = B.lm_host[i].final_chi;
+    for (int i = 0; i < K; i++) chis[i] = B.lm_host()[i].final_chi;
   }
   return ORBX_OK;
 }
@@ -599,7 +590,7 @@ orbx_status run_local_ba_many(LocalBA* const* Ls, int K, BaBatch& B, const orbx_
     for (int i = 0; i < K; i++) {
       ress[i].iterations[0] = it[i];
       ress[i].chi2[0] = chi[i];
-      hook |= B.lm_host[i].stopped && Ls[i]->D.raise_after >= 0;
+      hook |= B.lm_host()[i].stopped && Ls[i]->D.raise_after >= 0;
     }
     if (!(stop()) && !hook) {
       for (int i = 0; i < K; i++) {  // :764-802 level-1 outliers, drop robust kernels
@@ -787,15 +778,12 @@ int orbx_debug_ba_options(orbx_ba* h, const orbx_ba_debug_options* o) {
 
 orbx_status orbx_ba_stop_flag(orbx_ba* h, volatile int** flag) {
   if (!h || !flag) return ORBX_ERR_ARG;
-  if (!h->L.own_stop) {
+  if (!h->L.own_stop.p) {
     (void)hipSetDevice(h->device);
-    if (hipHostMalloc((void**)&h->L.own_stop, sizeof(int), hipHostMallocMapped) != hipSuccess) {
-      h->L.own_stop = nullptr;
-      return ORBX_ERR_HIP;
-    }
-    *h->L.own_stop = 0;
+    if (h->L.own_stop.ensure(sizeof(int)) != hipSuccess) return ORBX_ERR_HIP;
+    *h->L.own_stop.as<int>() = 0;
   }
-  *flag = h->L.own_stop;
+  *flag = h->L.own_stop.as<int>();
   return ORBX_OK;
 }
 
@@ -894,68 +882,52 @@ extern "C" int orbx_debug_ldlt_ex(const double* S, const double* b, int N, doubl
   const int stage_limit = 99;
   orbx::BaDev D{};
   D.nposes = N / 6;
-  double *dS = nullptr, *dS0 = nullptr, *db = nullptr, *dx = nullptr, *dscal = nullptr;
-  const size_t nn = (size_t)N * N * sizeof(double);
-  hipEvent_t e0, e1;
-  hipError_t e = hipMalloc((void**)&dS, nn);
-  if (e == hipSuccess) e = hipMalloc((void**)&dS0, nn);
-  if (e == hipSuccess) e = hipMalloc((void**)&db, N * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc((void**)&dx, N * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc((void**)&dscal, 8 * sizeof(double));
-  if (e == hipSuccess) e = hipMemcpy(dS0, S, nn, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(db, b, N * sizeof(double), hipMemcpyHostToDevice);
-  D.S = dS;
-  D.bs = db;
-  D.xp = dx;
-  D.scal = dscal;
-  unsigned long long* ddbg = nullptr;
+  const size_t nn = (size_t)N * N;
+  orbx::DevBuf<double> dS, dS0, db, dx, dscal, dSw;
+  orbx::DevBuf<unsigned long long> ddbg;
+  orbx::Event e0, e1;
+  hipError_t e = dS.ensure(nn);
+  if (e == hipSuccess) e = dS0.upload(S, nn);
+  if (e == hipSuccess) e = db.upload(b, N);
+  if (e == hipSuccess) e = dx.ensure(N);
+  if (e == hipSuccess) e = dscal.ensure(8);
+  D.S = dS.p;
+  D.bs = db.p;
+  D.xp = dx.p;
+  D.scal = dscal.p;
   const bool want_ts = stamps != nullptr;
   if (e == hipSuccess && want_ts) {
-    e = hipMalloc((void**)&ddbg, 64 * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemset(ddbg, 0, 64 * sizeof(unsigned long long));
+    e = ddbg.ensure(64);
+    if (e == hipSuccess) e = hipMemset(ddbg.p, 0, 64 * sizeof(unsigned long long));
   }
-  D.dbg = ddbg;
+  D.dbg = ddbg.p;
   // (the single-workgroup kernels stop at a padded size of kLdltMaxNp, the tiled ones at kTiledMaxN)
   if (orbx::LdltPlan::use_tiled(N) ? N > orbx::kTiledMaxN : orbx::ldlt_np(N) > orbx::kLdltMaxNp) e = hipErrorInvalidValue;
   orbx::LdltPlan plan;
   if (e == hipSuccess) e = plan.prepare(N);
   D.ldlt_pan = plan.pan ? 1 : 0;
-  double* dSw = nullptr;
-  if (e == hipSuccess && plan.sw_doubles() > 0) e = hipMalloc((void**)&dSw, plan.sw_doubles() * sizeof(double));
-  D.Sw = dSw;
+  if (e == hipSuccess && plan.sw_doubles() > 0) e = dSw.ensure(plan.sw_doubles());
+  D.Sw = dSw.p;
   float total = 0;
-  if (e == hipSuccess) {
-    (void)hipEventCreate(&e0);
-    (void)hipEventCreate(&e1);
-    for (int r = 0; r < reps && e == hipSuccess; r++) {
-      e = hipMemcpy(dS, dS0, nn, hipMemcpyDeviceToDevice);
-      (void)hipEventRecord(e0, nullptr);
-      plan.launch(D, nullptr, stage_limit);
-      (void)hipEventRecord(e1, nullptr);
-      if (e == hipSuccess) e = hipEventSynchronize(e1);
-      float t = 0;
-      (void)hipEventElapsedTime(&t, e0, e1);
-      total += t;
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
+  if (e == hipSuccess) e = e0.ensure(hipEventDefault);
+  if (e == hipSuccess) e = e1.ensure(hipEventDefault);
+  for (int r = 0; r < reps && e == hipSuccess; r++) {
+    e = hipMemcpy(dS.p, dS0.p, nn * sizeof(double), hipMemcpyDeviceToDevice);
+    (void)hipEventRecord(e0, nullptr);
+    plan.launch(D, nullptr, stage_limit);
+    (void)hipEventRecord(e1, nullptr);
+    if (e == hipSuccess) e = hipEventSynchronize(e1);
+    float t = 0;
+    (void)hipEventElapsedTime(&t, e0, e1);
+    total += t;
   }
   double ok = 0;
-  if (e == hipSuccess) e = hipMemcpy(x, dx, N * sizeof(double), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(&ok, dscal + 2, sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(x, dx.p, N * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(&ok, dscal.p + 2, sizeof(double), hipMemcpyDeviceToHost);
   if (ms) *ms = total / reps;
-  (void)hipFree(dS);
-  (void)hipFree(dS0);
-  (void)hipFree(db);
-  (void)hipFree(dx);
-  (void)hipFree(dscal);
-  if (dSw) (void)hipFree(dSw);
-  if (ddbg) {
-    // the kernel's s_memtime stamps (LDLT_TS points; 0 = not reached) of the last launch
-    if (hipMemcpy(stamps, ddbg, 64 * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess)
-      e = hipErrorUnknown;
-    (void)hipFree(ddbg);
-  }
+  // the kernel's s_memtime stamps (LDLT_TS points; 0 = not reached) of the last launch
+  if (ddbg.p && hipMemcpy(stamps, ddbg.p, 64 * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess)
+    e = hipErrorUnknown;
   if (e != hipSuccess) return ORBX_ERR_HIP;
   return ok != 0.0 ? ORBX_OK : ORBX_ERR_STATE;
 }

@@ -455,8 +455,7 @@ __global__ __launch_bounds__(kThreads) void k_cnmp_points(const Job* jp, int nbi
 // ------------------------------------------------------------------ C ABI
 struct orbx_new_points {
   int device = 0;
-  int* flags = nullptr;  // pinned, mapped: [0] the handle's flag, [1] the mirror of a caller's bool
-  const int* flags_dev = nullptr;
+  orbx::PinnedBuf flags{true};  // mapped, two ints: [0] the handle's flag, [1] the mirror of a caller's bool
   orbx_new_points_debug_options opt{-1, 0};
   // probes of the last host call
   bool have_probes = false;
@@ -624,7 +623,7 @@ orbx_status np_run_host(orbx_new_points* h, const orbx_new_points_problem* p, co
   J.raise_after = h->opt.raise_after_neighbour;
   J.zstride = (int)zstride;
   J.ratio_factor = 1.5f * p->scale_factor;
-  J.flag = h->flags_dev;
+  J.flag = h->flags.dev<const int>();
   J.tri = S.dev(s_tri);
   J.pose = S.dev(d_pose);
   J.zbuf = S.dev(d_z);
@@ -651,7 +650,8 @@ orbx_status np_run_host(orbx_new_points* h, const orbx_new_points_problem* p, co
     T.kf2 = v.kf;
     S.fill(s_tri, T, (size_t)i);
   }
-  h->flags[1] = stop && *stop ? 1 : 0;
+  int* const mirror = h->flags.as<int>() + 1;
+  *mirror = stop && *stop ? 1 : 0;
   hipError_t e = S.upload(Staging::Outputs::zeroed);
   if (e == hipSuccess) e = np_enqueue(J, S.dev(s_job), S.stream());
   if (e == hipSuccess) e = S.download();
@@ -661,7 +661,7 @@ orbx_status np_run_host(orbx_new_points* h, const orbx_new_points_problem* p, co
     } else {  // the device's view of the caller's bool follows it while this thread waits
       for (;;) {
         const int v = *stop ? 1 : 0;
-        if (*(volatile int*)(h->flags + 1) != v) *(volatile int*)(h->flags + 1) = v;
+        if (*(volatile int*)mirror != v) *(volatile int*)mirror = v;
         e = hipStreamQuery(S.stream());
         if (e != hipErrorNotReady) break;
         std::this_thread::yield();
@@ -669,7 +669,7 @@ orbx_status np_run_host(orbx_new_points* h, const orbx_new_points_problem* p, co
       if (e == hipSuccess) e = S.sync();
     }
   }
-  h->flags[1] = 0;
+  *mirror = 0;
   if (e != hipSuccess) {
     (void)hipGetLastError();
     return ORBX_ERR_HIP;
@@ -707,16 +707,12 @@ orbx_status orbx_new_points_create(int device, orbx_new_points** out) {
   orbx_new_points* h = new (std::nothrow) orbx_new_points;
   if (!h) return ORBX_ERR_HIP;
   h->device = device;
-  void* dp = nullptr;
-  if (hipHostMalloc((void**)&h->flags, 2 * sizeof(int), hipHostMallocMapped) != hipSuccess ||
-      hipHostGetDevicePointer(&dp, h->flags, 0) != hipSuccess) {
+  if (h->flags.ensure(2 * sizeof(int)) != hipSuccess) {
     (void)hipGetLastError();
-    if (h->flags) (void)hipHostFree(h->flags);
     delete h;
     return ORBX_ERR_HIP;
   }
-  h->flags[0] = h->flags[1] = 0;
-  h->flags_dev = (const int*)dp;
+  h->flags.as<int>()[0] = h->flags.as<int>()[1] = 0;
   *out = h;
   return ORBX_OK;
 }
@@ -724,14 +720,13 @@ orbx_status orbx_new_points_create(int device, orbx_new_points** out) {
 orbx_status orbx_new_points_destroy(orbx_new_points* h) {
   if (!h) return ORBX_ERR_ARG;
   (void)hipSetDevice(h->device);
-  if (h->flags) (void)hipHostFree(h->flags);
   delete h;
   return ORBX_OK;
 }
 
 orbx_status orbx_new_points_stop_flag(orbx_new_points* h, volatile int** flag) {
   if (!h || !flag) return ORBX_ERR_ARG;
-  *flag = h->flags;
+  *flag = h->flags.as<int>();
   return ORBX_OK;
 }
 
@@ -783,7 +778,7 @@ orbx_status orbx_create_new_map_points_device(orbx_new_points* h, const orbx_new
     J.raise_after = h->opt.raise_after_neighbour;
     J.zstride = (int)zstride;
     J.ratio_factor = 1.5f * p->scale_factor;
-    J.flag = h->flags_dev;
+    J.flag = h->flags.dev<const int>();
     J.tri = (orbx_tri_problem*)(d + f_tri);
     J.pose = (Pose*)(d + f_pose);
     J.zbuf = (float*)(d + f_z);

@@ -9,55 +9,13 @@
 #include <memory>
 #include <utility>
 
+#include "orbx_mem.h"
 #include "orbx_plan.h"
 #include "orbx_prof.h"
 #include "orbx_scratch.h"
 #include "orbx_stereo.h"
 
 namespace orbx {
-
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  size_t n = 0;
-  ~DevBuf() { release(); }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-  }
-  hipError_t ensure(size_t count) {
-    if (count <= n && p) return hipSuccess;
-    release();
-    size_t c = std::max<size_t>(count, 1);
-    hipError_t e = hipMalloc((void**)&p, c * sizeof(T));
-    if (e == hipSuccess) n = c;
-    return e;
-  }
-  hipError_t upload(const T* src, size_t count) {  // a blocking copy of a host table
-    const hipError_t e = ensure(count);
-    return e != hipSuccess || !count ? e : hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice);
-  }
-};
-
-// pinned host bytes, grown in whole pages
-struct PinnedBuf {
-  uint8_t* p = nullptr;
-  size_t cap = 0;
-  ~PinnedBuf() {
-    if (p) (void)hipHostFree(p);
-  }
-  hipError_t ensure(size_t bytes) {
-    if (bytes <= cap && p) return hipSuccess;
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-    const size_t c = (bytes + 4095) & ~(size_t)4095;
-    hipError_t e = hipHostMalloc((void**)&p, c, hipHostMallocDefault);
-    if (e == hipSuccess) cap = c;
-    return e;
-  }
-};
 
 // A plan as a handle holds it: the host part (orbx_plan.h) and its device copies
 struct DevPlan : Plan {

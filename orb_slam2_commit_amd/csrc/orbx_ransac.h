@@ -22,32 +22,27 @@ namespace orbx {
 
 // One stream, one pinned block and one device staging block per device and solver family, shared
 // by every solver of the family (the reference creates a solver per candidate, so creation must
-// be cheap).  Both blocks only grow.
+// be cheap).  Both blocks only grow.  The contexts live for the process: a family keeps its array
+// behind a pointer it never deletes (orbx_mem.h), so nothing here is freed at exit.
 struct RansacDevice {
   std::once_flag once;
   hipError_t init_err = hipSuccess;
   hipStream_t st = nullptr;
   std::mutex mu;  // serialises the calls that share the stream and the two blocks
-  void* pinned = nullptr;
-  size_t pinned_cap = 0;
-  void* dstage = nullptr;  // device side of the batched calls: job records, minimal sets, results
-  size_t dstage_cap = 0;
+  void* pinned = nullptr;  // pinned_mem's block
+  void* dstage = nullptr;  // dstage_mem's block, the device side of the batched calls: job records, sets, results
+  PinnedBuf pinned_mem;
+  DevBuf<uint8_t> dstage_mem;
   hipError_t dstage_reserve(size_t bytes) {
-    if (bytes <= dstage_cap) return hipSuccess;
-    if (dstage) (void)hipFree(dstage);
-    dstage = nullptr;
-    dstage_cap = 0;
-    hipError_t e = hipMalloc(&dstage, bytes);
-    if (e == hipSuccess) dstage_cap = bytes;
+    if (bytes <= dstage_mem.n) return hipSuccess;  // (also zero bytes of a fresh context: nothing is allocated)
+    const hipError_t e = dstage_mem.ensure(bytes);
+    dstage = dstage_mem.p;
     return e;
   }
   hipError_t pinned_reserve(size_t bytes) {
-    if (bytes <= pinned_cap) return hipSuccess;
-    if (pinned) (void)hipHostFree(pinned);
-    pinned = nullptr;
-    pinned_cap = 0;
-    hipError_t e = hipHostMalloc(&pinned, bytes, hipHostMallocDefault);
-    if (e == hipSuccess) pinned_cap = bytes;
+    if (bytes <= pinned_mem.cap) return hipSuccess;
+    const hipError_t e = pinned_mem.ensure(bytes);
+    pinned = pinned_mem.p;
     return e;
   }
 };

@@ -31,16 +31,30 @@
 #include <vector>
 
 #include "../../include/orbx.h"
+#include "orbx_mem.h"
 
 namespace orbx {
 
+constexpr size_t scratch_align(size_t x) { return (x + 255) & ~(size_t)255; }
+// What a block allocates when a call asks for more bytes than it holds, a quarter of slack each: a lease's
+// two blocks, and the LocalBA arenas (ba_host.h Arena; stated here, where a host-only test can reach it).
+constexpr size_t lease_capacity(size_t bytes) { return scratch_align(bytes + bytes / 4); }
+constexpr size_t arena_capacity(size_t bytes) { return bytes + bytes / 4 + 4096; }
+// What a pinned block and its device twin hold together: the smaller of the two capacities (the pinned
+// owner rounds up to whole pages, the device owner does not), so growth is decided against this one.
+// mapped: there is no twin.
+constexpr size_t pair_capacity(size_t pinned_cap, size_t device_cap, bool mapped) {
+  return mapped || pinned_cap < device_cap ? pinned_cap : device_cap;
+}
+
+// (A lease is a heap object that is never deleted -- see orbx_mem.h on process-lifetime owners.)
 struct ScratchLease {
   int device = 0;
   hipStream_t st = nullptr;
-  uint8_t* d = nullptr;  // device arena
-  size_t dcap = 0;
-  uint8_t* h = nullptr;  // pinned host staging
-  size_t hcap = 0;
+  uint8_t* d = nullptr;  // device arena (dmem's block)
+  uint8_t* h = nullptr;  // pinned host staging (hmem's block)
+  DevBuf<uint8_t> dmem;
+  PinnedBuf hmem;
   // grow-only: on growth the old blocks are released first (the lease is idle between calls)
   hipError_t reserve(size_t dbytes, size_t hbytes);
   // wait for the lease's stream (the calls are synchronous, as the reference's are)
@@ -60,8 +74,6 @@ struct ScratchGuard {
   ScratchGuard(const ScratchGuard&) = delete;
   ScratchGuard& operator=(const ScratchGuard&) = delete;
 };
-
-inline size_t scratch_align(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // The device check of every host form: ORBX_ERR_NODEV without a device, ORBX_ERR_ARG for an index
 // out of range (or one hipSetDevice refuses).

@@ -746,7 +746,7 @@ namespace {
 using orbx::scratch_align;
 using orbx::RansacDevice;
 
-RansacDevice g_pnp_dev[64];
+RansacDevice* const g_pnp_dev = new RansacDevice[64];  // never deleted (orbx_mem.h)
 
 hipError_t pnp_kernel_setup() {
   return hipFuncSetAttribute((const void*)orbx::k_pnp_refine_many<true>, hipFuncAttributeMaxDynamicSharedMemorySize,

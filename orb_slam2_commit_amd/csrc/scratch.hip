@@ -18,29 +18,19 @@ Pool g_pool[kMaxDevices];
 hipError_t ScratchLease::reserve(size_t dbytes, size_t hbytes) {
   dbytes = dbytes ? dbytes : 256;
   hbytes = hbytes ? hbytes : 256;
-  if (dbytes > dcap) {
+  if (dbytes > dmem.n) {
     if (d) {
       hipError_t e = hipStreamSynchronize(st);  // the previous call's work is done (defensive)
       if (e != hipSuccess) return e;
-      (void)hipFree(d);
-      d = nullptr;
-      dcap = 0;
     }
-    const size_t cap = scratch_align(dbytes + dbytes / 4);
-    hipError_t e = hipMalloc((void**)&d, cap);
+    const hipError_t e = dmem.ensure(lease_capacity(dbytes));
+    d = dmem.p;
     if (e != hipSuccess) return e;
-    dcap = cap;
   }
-  if (hbytes > hcap) {
-    if (h) {
-      (void)hipHostFree(h);
-      h = nullptr;
-      hcap = 0;
-    }
-    const size_t cap = scratch_align(hbytes + hbytes / 4);
-    hipError_t e = hipHostMalloc((void**)&h, cap, hipHostMallocDefault);
+  if (hbytes > hmem.cap) {
+    const hipError_t e = hmem.ensure(lease_capacity(hbytes));
+    h = hmem.p;
     if (e != hipSuccess) return e;
-    hcap = cap;
   }
   return hipSuccess;
 }

@@ -523,7 +523,7 @@ using orbx::Sim3State;
 // One context per device (orbx_ransac.h), shared by every solver (LoopClosing creates a Sim3Solver
 // per loop candidate): a solver owns only its correspondences, its best mask and its state; the
 // per-hypothesis arrays of a call live in the context's device staging block.
-orbx::RansacDevice g_sim3_dev[64];
+orbx::RansacDevice* const g_sim3_dev = new orbx::RansacDevice[64];  // never deleted (orbx_mem.h)
 
 }  // namespace
 

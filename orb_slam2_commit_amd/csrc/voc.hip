@@ -270,10 +270,10 @@ __global__ __launch_bounds__(kVocBuildThreads) void k_voc_build(VocDev V, const 
 // ------------------------------------------------------------------ host / C ABI
 struct orbx_voc {
   int device = 0;
-  hipStream_t st = nullptr;
+  orbx::Stream st;
   int k = 0, L = 0, scoring = 0, weighting = 0, n_nodes = 0, n_words = 0;
   bool empty = true;
-  void* d_mem = nullptr;
+  orbx::DevBuf<uint8_t> d_mem;  // every table of `dev`, one block
   orbx::VocDev dev{};
   // No per-handle scratch: ORB-SLAM2 shares one vocabulary between the Tracking and LocalMapping
   // threads (Frame::ComputeBoW / KeyFrame::ComputeBoW), so every call brings its own -- a scratch
@@ -386,16 +386,11 @@ orbx_status orbx_voc_load_text(const char* text, size_t len, int device, orbx_vo
   std::memcpy(stage.data() + b_desc + b_w, word.data(), 4 * (size_t)n);
   std::memcpy(stage.data() + b_desc + b_w + b_word, child_off.data(), 4 * (size_t)(n + 1));
   std::memcpy(stage.data() + b_desc + b_w + b_word + b_off, child.data(), 4 * child.size());
-  hipError_t he = hipStreamCreateWithFlags(&v->st, hipStreamNonBlocking);
-  if (he == hipSuccess) he = hipMalloc(&v->d_mem, stage.size());
-  if (he == hipSuccess) he = hipMemcpy(v->d_mem, stage.data(), stage.size(), hipMemcpyHostToDevice);
-  if (he != hipSuccess) {
-    if (v->d_mem) (void)hipFree(v->d_mem);
-    if (v->st) (void)hipStreamDestroy(v->st);
+  if (v->st.ensure() != hipSuccess || v->d_mem.upload(stage) != hipSuccess) {
     delete v;
     return ORBX_ERR_HIP;
   }
-  uint8_t* base = (uint8_t*)v->d_mem;
+  uint8_t* base = v->d_mem.p;
   v->dev.desc = (const uint64_t*)base;
   v->dev.weight = (const double*)(base + b_desc);
   v->dev.word_id = (const int*)(base + b_desc + b_w);
@@ -411,8 +406,6 @@ orbx_status orbx_voc_load_text(const char* text, size_t len, int device, orbx_vo
 orbx_status orbx_voc_destroy(orbx_voc* v) {
   if (!v) return ORBX_ERR_ARG;
   (void)hipSetDevice(v->device);
-  if (v->d_mem) (void)hipFree(v->d_mem);
-  if (v->st) (void)hipStreamDestroy(v->st);
   delete v;
   return ORBX_OK;
 }
@@ -525,7 +518,7 @@ orbx_status orbx_voc_transform_device(orbx_voc* v, const uint8_t* d_desc, int ca
   if (cap > orbx::kVocMaxSet) return ORBX_ERR_SIZE;
   if (v->empty) return ORBX_ERR_STATE;
   if (hipSetDevice(v->device) != hipSuccess) return ORBX_ERR_HIP;
-  hipStream_t st = stream == ORBX_STREAM_NULL ? (hipStream_t)0 : stream ? (hipStream_t)stream : v->st;
+  hipStream_t st = stream == ORBX_STREAM_NULL ? (hipStream_t)0 : stream ? (hipStream_t)stream : v->st.st;
   const size_t nt = (size_t)n_sets * cap;
   if (nt > (size_t)0x7FFFFFFF) return ORBX_ERR_SIZE;
   const size_t need = scratch_align(4 * nt) + scratch_align(8 * nt) + scratch_align(4 * nt);  // word | weight | nid

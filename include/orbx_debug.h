@@ -47,9 +47,20 @@ enum {
   ORBX_LP_PATH = 8,       /* x8 per level >= 1, the resize kernel chosen for it: path (1: k_resize_strip, 0: k_resize),
                              tile columns, tile rows (its grid), tile width, tile height, LDS row stride,
                              footprint rows staged, strip rows per thread (0 for k_resize) */
-  ORBX_LP_FAST = 9        /* x8 per k_fast launch group: first cell, end cell, then the kernel instance k_fast<S, RP, NK>
+  ORBX_LP_FAST = 9,       /* x8 per k_fast launch group: first cell, end cell, then the kernel instance k_fast<S, RP, NK>
                              (LDS row stride, region rows per compass instruction, window loads per lane) and
                              its LDS: window tile bytes, score map bytes, bytes per block */
+  ORBX_LP_OCTREE = 10,    /* x8 per k_octree launch group, the groups of a batch of three or more images first, then
+                             the one launch of smaller batches: first level, end level, threads per block, LDS node
+                             capacity, largest cell count of a level, kcap (a level's candidates kept in LDS; the
+                             rest go through global scratch), dynamic LDS bytes, the largest batch that takes this
+                             row (-1 for the groups: every larger batch) */
+  ORBX_LP_CELLS = 11,     /* x8 per FAST cell: level, x0, y0, x1, y1 (the detection region, inclusive), the cell's
+                             offset in ORBX_DBG_CANDIDATES' logical view (as ORBX_DBG_CELL_TABLE), cap (its
+                             candidate slots), kin (those of them that are inline) */
+  ORBX_LP_OCT_LEVELS = 12 /* x8 per level, DistributeOctTree's inputs and outputs: minBorderX, minBorderY, maxBorderX,
+                             maxBorderY, N (the level's quota), nIni (clamped to 1), the level's offset in
+                             ORBX_DBG_OCT_OUT, its output slots */
 };
 long long orbx_debug_launch_plan(const orbx_extractor_params* params, int width, int height, int what, int a0,
                                  int a1, int a2, long long* dst, size_t cap);
@@ -74,6 +85,29 @@ orbx_status orbx_debug_stereo_keypoints(orbx_extractor* left, orbx_extractor* ri
  * otherwise.  The matcher indexes its level and row tables with these unguarded.  No device is
  * needed or touched. */
 int orbx_debug_stereo_keypoints_check(const orbx_keypoint* kps, int n, int nlevels, int width, int height);
+
+/* The shipped k_octree (orbx_extract's launch path for a batch of n_img images, unchanged: one launch
+ * over every level for one or two images, the launch groups beyond) on FAST candidates the caller
+ * supplies instead of k_fast's own (tests only: scenes that drive DistributeOctTree down every path).
+ * Precondition: the handle's last call was an extraction (ORBX_ERR_STATE otherwise); its geometry and
+ * device are used.  Per image: cell_counts, one int32 per FAST cell (ORBX_DBG_CELL_COUNTS' layout), and
+ * candidates in ORBX_DBG_CANDIDATES' logical view (score << 24 | y << 12 | x in level coordinates,
+ * every cell's cap slots from its ORBX_LP_CELLS offset on, its first count slots read).  They go to a
+ * scratch block of this call in the kernel's inline / overflow slot layout, so the handle's
+ * extraction state is untouched.  Outputs per image: oct_count (nlevels values, ORBX_DBG_OCT_COUNTS)
+ * and oct_out (ORBX_DBG_OCT_OUT's slots, filled with 0xFFFFFFFF before the launch, so a slot the
+ * kernel did not write shows).  Checked on the host before any device call: ORBX_ERR_ARG unless the
+ * input passes orbx_debug_octree_candidates_check on the handle's geometry. */
+orbx_status orbx_debug_octree_candidates(orbx_extractor* h, int n_img, const int32_t* cell_counts,
+                                         const uint32_t* candidates, int32_t* oct_count, uint32_t* oct_out);
+/* ORBX_OK when n_img is in [1, 64], every cell's count is in [0, cap], every candidate read has x in
+ * [minBorderX, maxBorderX) and y in [minBorderY, maxBorderY) of its cell's level, and no two
+ * candidates of one level of one image share a pixel; ORBX_ERR_ARG otherwise (also for a geometry
+ * without a FAST cell), or the plan's ORBX_ERR_SIZE.  The kernel subtracts the minimum border and packs
+ * 12-bit fields unguarded, and its best-response pass relies on FAST's one candidate per pixel.  The
+ * plan is built on the host as orbx_debug_launch_plan builds it: no device is needed or touched. */
+int orbx_debug_octree_candidates_check(const orbx_extractor_params* params, int width, int height, int n_img,
+                                       const int32_t* cell_counts, const uint32_t* candidates);
 
 /* The library's deterministic double atan2 (Sim3Solver's half-angle, src/Sim3Solver.cc:325) evaluated
  * on the host: the same operation sequence as the kernels run (no device is needed or touched). */

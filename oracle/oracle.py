@@ -106,6 +106,8 @@ def lib():
         L.oracle_gaussian_blur7.argtypes = [P, C.c_int, C.c_int, P]
         L.oracle_fast_window.argtypes = [P, C.c_int, C.c_int, C.c_size_t, C.c_int, P, C.c_int]
         L.oracle_fast_score.argtypes = [P, C.c_size_t, C.c_int, C.c_int]
+        L.oracle_distribute_octree.argtypes = [P, P, P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P,
+                                               C.c_int]
         L.oracle_fast_atan2.argtypes = [C.c_float, C.c_float]
         L.oracle_fast_atan2.restype = C.c_float
         L.oracle_cosf.argtypes = [C.c_float]
@@ -282,6 +284,17 @@ def fast_window(img, threshold):
     n = lib().oracle_fast_window(_p(img), w, h, w, threshold, _p(out), cap)
     out = out[:n]
     return np.stack([out & 0xFFF, (out >> 12) & 0xFFF, out >> 24], axis=1).astype(np.int32)
+
+
+def distribute_octree(x, y, response, min_x, max_x, min_y, max_y, N):
+    """DistributeOctTree on candidates whose x, y are relative to (min_x, min_y), in candidate order:
+    the selected candidates' indices in list order."""
+    x, y, r = (np.ascontiguousarray(v, np.float32) for v in (x, y, response))
+    n = len(x)
+    out = np.zeros(max(n, 1), np.int32)
+    k = lib().oracle_distribute_octree(_p(x), _p(y), _p(r), n, int(min_x), int(max_x), int(min_y), int(max_y),
+                                       int(N), _p(out), len(out))
+    return out[:k].copy()
 
 
 def fast_score(img, x, y):

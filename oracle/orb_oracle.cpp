@@ -379,7 +379,8 @@ void divide(const Node& n, const std::vector<Kp>& kp, Node c[4]) {
   }
 }
 
-std::vector<Kp> distribute_octree(const std::vector<Kp>& kp, int minX, int maxX, int minY, int maxY, int N) {
+std::vector<Kp> distribute_octree(const std::vector<Kp>& kp, int minX, int maxX, int minY, int maxY, int N,
+                                  std::vector<int>* index = nullptr) {  // index: the selection as indices into kp
   std::vector<Kp> result;
   if (kp.empty()) return result;
   int nIni = (int)std::round((float)(maxX - minX) / (maxY - minY));
@@ -459,6 +460,7 @@ std::vector<Kp> distribute_octree(const std::vector<Kp>& kp, int minX, int maxX,
     for (size_t k = 1; k < n.keys.size(); k++)
       if (kp[n.keys[k]].response > kp[best].response) best = n.keys[k];
     result.push_back(kp[best]);
+    if (index) index->push_back(best);
   }
   return result;
 }
@@ -698,6 +700,18 @@ int oracle_fast_window(const uint8_t* img, int w, int h, size_t stride, int thre
   for (int i = 0; i < n; i++)
     out[i] = ((uint32_t)kp[i].response << 24) | ((uint32_t)kp[i].y << 12) | (uint32_t)kp[i].x;
   return (int)kp.size();
+}
+
+// distribute_octree on n candidates (coordinates relative to the border box, as extract() hands them
+// over): the selected candidates' indices in list order; returns their number (copies min(cap, number)).
+int oracle_distribute_octree(const float* x, const float* y, const float* response, int n, int minX, int maxX,
+                             int minY, int maxY, int N, int32_t* out_index, int cap) {
+  std::vector<Kp> kp((size_t)std::max(n, 0));
+  for (int i = 0; i < n; i++) kp[i] = {x[i], y[i], 7.f, -1.f, response[i], 0};
+  std::vector<int> index;
+  distribute_octree(kp, minX, maxX, minY, maxY, N, &index);
+  for (int i = 0; i < std::min((int)index.size(), cap); i++) out_index[i] = index[i];
+  return (int)index.size();
 }
 
 int oracle_fast_score(const uint8_t* img, size_t stride, int x, int y) {

@@ -58,6 +58,10 @@ int oracle_gaussian_blur7(const uint8_t* src, int w, int h, uint8_t* dst);
 int oracle_fast_window(const uint8_t* img, int w, int h, size_t stride, int threshold,
                        uint32_t* out, int cap);
 int oracle_fast_score(const uint8_t* img, size_t stride, int x, int y);
+/* DistributeOctTree on n candidates (x, y relative to the border box minX / minY, in candidate
+ * order): indices of the selected candidates in list order; returns their number. */
+int oracle_distribute_octree(const float* x, const float* y, const float* response, int n, int minX, int maxX,
+                             int minY, int maxY, int N, int32_t* out_index, int cap);
 float oracle_fast_atan2(float y, float x);
 float oracle_cosf(float x);
 float oracle_sinf(float x);

@@ -382,6 +382,8 @@ SIGNATURES = {
                                 C.c_size_t], C.c_longlong),
     "orbx_debug_stereo_keypoints": ([P, P, P, P, C.c_int, P, P, C.c_int, C.c_float, C.c_float, P, P, P, P], C.c_int),
     "orbx_debug_stereo_keypoints_check": ([P, C.c_int, C.c_int, C.c_int, C.c_int], C.c_int),
+    "orbx_debug_octree_candidates": ([P, C.c_int, P, P, P, P], C.c_int),
+    "orbx_debug_octree_candidates_check": ([C.POINTER(ExtractorParams), C.c_int, C.c_int, C.c_int, P, P], C.c_int),
     "orbx_debug_atan2_det": ([C.c_double, C.c_double], C.c_double),
     "orbx_debug_exp": ([P, C.c_int, P, C.c_int], C.c_int),
     "orbx_debug_initializer_host": ([P, C.c_int, P, C.c_float, C.c_int, P, C.c_int, P, P, C.c_int,

@@ -1,6 +1,7 @@
 // debug.hip -- the extractor's part of include/orbx_debug.h (tests and tools only): stage buffers of a
 // handle's last extraction, the plan's launch descriptors built on the host, the stereo matcher on
-// supplied keypoints, and the HBM copy reference of the roofline (this unit's one kernel).
+// supplied keypoints, k_octree on supplied candidates, and the HBM copy reference of the roofline (this
+// unit's one kernel).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -187,6 +188,110 @@ extern "C" orbx_status orbx_debug_stereo_keypoints(orbx_extractor* left, orbx_ex
   return hip_status(e);
 }
 
+// ------------------------------------------------------------ k_octree on supplied candidates
+// What k_octree reads of a candidate unguarded: put_cand subtracts the level's minBX / minBY and packs
+// 12-bit fields, a cell's count indexes its slots up to cap, and the best-response pass assumes one
+// candidate per pixel (FAST's non-maximum suppression never emits two).  counts: n_img x ncells;
+// cand: n_img x (sum of the cells' caps), a cell's survivors from its logical offset on.  Host only.
+constexpr int kOctInjectMaxImages = 64;
+static bool octree_candidates_ok(const Plan& P, int n_img, const int32_t* counts, const uint32_t* cand) {
+  const Geometry& G = P.G;
+  if (n_img < 1 || n_img > kOctInjectMaxImages || !counts || !cand || G.ncells < 1) return false;
+  long long total = 0;
+  for (const CellInfo& c : P.cells) total += c.cap;
+  std::vector<uint8_t> seen;
+  for (int img = 0; img < n_img; img++) {
+    const int32_t* cnt = counts + (size_t)img * G.ncells;
+    const uint32_t* cd = cand + (size_t)img * total;
+    for (int l = 0; l < G.nlevels; l++) {
+      const LevelGeom& L = G.lv[l];
+      seen.assign((size_t)L.w * L.h, 0);
+      for (int ci = L.cell_begin; ci < L.cell_end; ci++) {
+        if (cnt[ci] < 0 || cnt[ci] > P.cells[ci].cap) return false;
+        for (int q = 0; q < cnt[ci]; q++) {
+          const uint32_t v = cd[q];
+          const int x = (int)(v & 0xFFF), y = (int)((v >> 12) & 0xFFF);
+          if (x < L.minBX || x >= L.maxBX || y < L.minBY || y >= L.maxBY) return false;
+          uint8_t& s = seen[(size_t)y * L.w + x];
+          if (s) return false;
+          s = 1;
+        }
+        cd += P.cells[ci].cap;
+      }
+    }
+  }
+  return true;
+}
+
+extern "C" int orbx_debug_octree_candidates_check(const orbx_extractor_params* params, int width, int height,
+                                                  int n_img, const int32_t* cell_counts, const uint32_t* candidates) {
+  if (!params_ok(params) || width <= 0 || height <= 0) return ORBX_ERR_ARG;
+  Plan P;
+  const orbx_status s = build_plan(*params, make_tables(*params), width, height, P);
+  if (s != ORBX_OK) return s;
+  return octree_candidates_ok(P, n_img, cell_counts, candidates) ? ORBX_OK : ORBX_ERR_ARG;
+}
+
+extern "C" orbx_status orbx_debug_octree_candidates(orbx_extractor* h, int n_img, const int32_t* cell_counts,
+                                                    const uint32_t* candidates, int32_t* oct_count,
+                                                    uint32_t* oct_out) {
+  if (!h || !oct_count || !oct_out) return ORBX_ERR_ARG;
+  if (!h->last_plan) return ORBX_ERR_STATE;
+  const DevPlan& P = *h->last_plan;
+  const Geometry& G = P.G;
+  if (!octree_candidates_ok(P, n_img, cell_counts, candidates)) return ORBX_ERR_ARG;
+  if (hipSetDevice(h->device) != hipSuccess) return ORBX_ERR_HIP;
+  // scratch block of this call alone (the handle's batch buffers keep their extraction):
+  // candidates in cell_slot's layout | cell counts | k_octree's spill scratch (positions, nodes) |
+  // output slots | output counts
+  const size_t n = (size_t)n_img;
+  BlockCursor cur;
+  const size_t o_cand = cur.take<uint32_t>(n * G.cand_total), o_cnt = cur.take<int>(n * G.ncells),
+               o_kpos = cur.take<uint32_t>(n * G.cand_total), o_knode = cur.take<int>(n * G.cand_total),
+               o_oct = cur.take<uint32_t>(n * G.oct_total), o_octn = cur.take<int>(n * G.nlevels);
+  DevBuf<uint8_t> blk;
+  if (blk.ensure(cur.end()) != hipSuccess) return ORBX_ERR_HIP;
+  std::vector<uint32_t> raw(n * G.cand_total, 0);
+  {
+    const uint32_t* cd = candidates;
+    for (int img = 0; img < n_img; img++)
+      for (int ci = 0; ci < G.ncells; ci++) {
+        const CellInfo& c = P.cells[ci];
+        for (int q = 0; q < cell_counts[(size_t)img * G.ncells + ci]; q++)
+          raw[(size_t)img * G.cand_total + cell_slot(c, q)] = cd[q];
+        cd += c.cap;
+      }
+  }
+  hipError_t e = hipSuccess;
+  auto chk = [&](hipError_t x) { if (x != hipSuccess) e = x; };
+  hipStream_t st = h->stream;
+  chk(hipMemcpyAsync(blk.p + o_cand, raw.data(), raw.size() * 4, hipMemcpyHostToDevice, st));
+  chk(hipMemcpyAsync(blk.p + o_cnt, cell_counts, n * G.ncells * sizeof(int), hipMemcpyHostToDevice, st));
+  chk(hipMemsetAsync(blk.p + o_oct, 0xFF, n * G.oct_total * 4, st));
+  chk(hipMemsetAsync(blk.p + o_octn, 0xFF, n * G.nlevels * sizeof(int), st));
+  if (e == hipSuccess) {
+    BatchPtrs B{};
+    B.cand = (uint32_t*)(blk.p + o_cand);
+    B.cell_count = (int*)(blk.p + o_cnt);
+    B.kpos = (uint32_t*)(blk.p + o_kpos);
+    B.knode = (int*)(blk.p + o_knode);
+    B.oct = (uint32_t*)(blk.p + o_oct);
+    B.oct_count = (int*)(blk.p + o_octn);
+    // the dynamic LDS limit is per kernel, not per plan: another geometry's plan may have set it since
+    size_t mx = octree_smem_bytes(G.og_all.node_cap, G.og_all.cell_cap, G.og_all.kcap);
+    for (int g = 0; g < G.n_og; g++) mx = std::max(mx, octree_smem_bytes(G.og[g].node_cap, G.og[g].cell_cap, G.og[g].kcap));
+    chk(octree_set_smem_limit(mx));
+    // the shipped launch path, as launch_extract_stages takes it
+    if (e == hipSuccess) chk(launch_octree(G, P.dG.p, P.dcells.p, B, n_img, st));
+  }
+  if (e == hipSuccess) {
+    chk(hipMemcpyAsync(oct_count, blk.p + o_octn, n * G.nlevels * sizeof(int), hipMemcpyDeviceToHost, st));
+    chk(hipMemcpyAsync(oct_out, blk.p + o_oct, n * G.oct_total * 4, hipMemcpyDeviceToHost, st));
+  }
+  chk(hipStreamSynchronize(st));  // before blk is freed
+  return hip_status(e);
+}
+
 extern "C" long long orbx_debug_launch_plan(const orbx_extractor_params* params, int width, int height, int what,
                                             int a0, int a1, int a2, long long* dst, size_t cap) {
   std::vector<long long> out;
@@ -238,6 +343,29 @@ extern "C" long long orbx_debug_launch_plan(const orbx_extractor_params* params,
       for (int g = 0; g < G.n_fg; g++) {
         const Geometry::FastGroup& F = G.fg[g];
         out.insert(out.end(), {F.c0, F.c1, F.s, F.rp, F.nk, F.tile_bytes, F.map_bytes, F.smem});
+      }
+      break;
+    case ORBX_LP_OCTREE: {
+      auto row = [&](const OctGroup& g, long long max_batch) {
+        out.insert(out.end(), {g.l0, g.l1, g.nt, g.node_cap, g.cell_cap, g.kcap,
+                               (long long)octree_smem_bytes(g.node_cap, g.cell_cap, g.kcap), max_batch});
+      };
+      for (int g = 0; g < G.n_og; g++) row(G.og[g], -1);
+      row(G.og_all, kOctOneLaunch);
+      break;
+    }
+    case ORBX_LP_CELLS: {
+      long long loff = 0;
+      for (const CellInfo& c : P.cells) {
+        out.insert(out.end(), {c.level, c.x0, c.y0, c.x1, c.y1, loff, c.cap, c.kin});
+        loff += c.cap;
+      }
+      break;
+    }
+    case ORBX_LP_OCT_LEVELS:
+      for (int l = 0; l < G.nlevels; l++) {
+        const LevelGeom& L = G.lv[l];
+        out.insert(out.end(), {L.minBX, L.minBY, L.maxBX, L.maxBY, L.nfeat, L.nIni, L.oct_off, L.oct_cap});
       }
       break;
     case ORBX_LP_GRIDS: {

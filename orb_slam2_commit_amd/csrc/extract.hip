@@ -1931,6 +1931,23 @@ hipError_t launch_blur(const Geometry& Gh, const Geometry* Gd, const int* tile_l
   return hipGetLastError();
 }
 
+// k_octree over n_img images' candidates (also orbx_debug_octree_candidates, on supplied candidates).
+// (Launch order of the groups measured flat.)  One or two images: all levels in one launch (the groups'
+// launches would run one after the other with a few blocks each)
+hipError_t launch_octree(const Geometry& Gh, const Geometry* Gd, const CellInfo* cells, const BatchPtrs& B, int n_img,
+                         hipStream_t st) {
+  const bool one = n_img <= kOctOneLaunch;
+  for (int gi = 0; gi < (one ? 1 : Gh.n_og); gi++) {
+    const OctGroup& og = one ? Gh.og_all : Gh.og[gi];
+    const size_t smem = octree_smem_bytes(og.node_cap, og.cell_cap, og.kcap);
+    if (og.nt == 512)
+      hipLaunchKernelGGL(k_octree<512>, dim3(n_img, og.l1 - og.l0), dim3(512), smem, st, Gd, cells, B, og);
+    else
+      hipLaunchKernelGGL(k_octree<256>, dim3(n_img, og.l1 - og.l0), dim3(256), smem, st, Gd, cells, B, og);
+  }
+  return hipPeekAtLastError();
+}
+
 hipError_t launch_extract_stages(const Geometry& Gh, const Geometry* Gd, const CellInfo* cells, const int* tile_level,
                                  const LaunchPlan& LP, const BatchPtrs& B, int n_img, orbx_keypoint* kps, uint8_t* desc,
                                  int32_t* counts, int kp_cap, hipStream_t st, StageTimer* T) {
@@ -1990,17 +2007,7 @@ hipError_t launch_extract_stages(const Geometry& Gh, const Geometry* Gd, const C
   }
   if (Gh.ncells > 0) {
     T->begin(st);
-    // (launch order of the groups measured flat).  One or two images: all levels in one launch
-    // (the groups' launches would run one after the other with a few blocks each)
-    const bool one = n_img <= kOctOneLaunch;
-    for (int gi = 0; gi < (one ? 1 : Gh.n_og); gi++) {
-      const OctGroup& og = one ? Gh.og_all : Gh.og[gi];
-      const size_t smem = octree_smem_bytes(og.node_cap, og.cell_cap, og.kcap);
-      if (og.nt == 512)
-        hipLaunchKernelGGL(k_octree<512>, dim3(n_img, og.l1 - og.l0), dim3(512), smem, st, Gd, cells, B, og);
-      else
-        hipLaunchKernelGGL(k_octree<256>, dim3(n_img, og.l1 - og.l0), dim3(256), smem, st, Gd, cells, B, og);
-    }
+    (void)launch_octree(Gh, Gd, cells, B, n_img, st);  // its error, if any, is the hipGetLastError below
     T->end(ST_OCTREE, st);
   }
   T->begin(st);

@@ -200,6 +200,8 @@ struct StageTimer;
 hipError_t upload_constants(const int* umax16, const int* gauss7);
 hipError_t launch_blur(const Geometry& Gh, const Geometry* Gd, const int* tile_level, const BatchPtrs& B, int n_img,
                        hipStream_t st);
+hipError_t launch_octree(const Geometry& Gh, const Geometry* Gd, const CellInfo* cells, const BatchPtrs& B, int n_img,
+                         hipStream_t st);
 hipError_t launch_extract_stages(const Geometry& Gh, const Geometry* Gd, const CellInfo* cells, const int* tile_level,
                                  const LaunchPlan& LP, const BatchPtrs& B, int n_img, orbx_keypoint* kps, uint8_t* desc,
                                  int32_t* counts, int kp_cap, hipStream_t st, StageTimer* T);

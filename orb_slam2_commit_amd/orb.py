@@ -198,6 +198,37 @@ def debug_stereo_keypoints(extractor_left, extractor_right, kps_left, desc_left,
     return uR, depth, sad, int(nm[0])
 
 
+def debug_launch_plan(params, width, height, what, a0=0, a1=0, a2=0):
+    """Item `what` (ORBX_LP_*) of the plan of one image geometry, built on the host: int64 words."""
+    L = _lib.lib()
+    n = L.orbx_debug_launch_plan(C.byref(params), int(width), int(height), int(what), a0, a1, a2, None, 0)
+    if n < 0:
+        check(n, "orbx_debug_launch_plan")
+    out = np.zeros(n, np.int64)
+    L.orbx_debug_launch_plan(C.byref(params), int(width), int(height), int(what), a0, a1, a2, ptr(out), n)
+    return out
+
+
+def debug_octree_candidates(extractor, cell_counts, candidates):
+    """The shipped k_octree on SUPPLIED FAST candidates (orbx_debug_octree_candidates, tests only), on
+    the geometry of the extractor's last call.  cell_counts int32[n_img, ncells], candidates
+    uint32[n_img, cand_total] in ORBX_DBG_CANDIDATES' logical view.
+
+    Returns (oct_count int32[n_img, nlevels], oct_out uint32[n_img, oct_total])."""
+    counts = np.ascontiguousarray(cell_counts, np.int32)
+    cand = np.ascontiguousarray(candidates, np.uint32)
+    w, h = extractor._last_shape
+    cells = debug_launch_plan(extractor.params, w, h, 11).reshape(-1, 8)  # ORBX_LP_CELLS
+    levels = debug_launch_plan(extractor.params, w, h, 12).reshape(-1, 8)  # ORBX_LP_OCT_LEVELS
+    n_img = len(counts)
+    assert counts.shape == (n_img, len(cells)) and cand.shape == (n_img, int(cells[:, 6].sum()))
+    oct_count = np.zeros((n_img, extractor.nlevels), np.int32)
+    oct_out = np.zeros((n_img, int(levels[:, 7].sum())), np.uint32)
+    check(_lib.lib().orbx_debug_octree_candidates(extractor._h, n_img, ptr(counts), ptr(cand), ptr(oct_count),
+                                                  ptr(oct_out)), "orbx_debug_octree_candidates")
+    return oct_count, oct_out
+
+
 def frame_stereo(extractor, image_left, image_right, bf, baseline):
     """The ORB part of Frame's stereo constructor (src/Frame.cc:62-123: ExtractORB(0/1) + ComputeStereoMatches)
     in one call through `extractor` (both images as one batch of two, one copy back).

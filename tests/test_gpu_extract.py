@@ -94,14 +94,24 @@ def test_extract_bitexact(gpu, name, seed, w, h, nf):
 
 @pytest.mark.parametrize("seed,w,h,nf", [(10, 640, 480, 1000), (11, 640, 480, 1000), (12, 1241, 376, 2000)])
 def test_extract_stress_noise(gpu, seed, w, h, nf):
-    """i.i.d. uniform noise: dense FAST responses, heavy octree phase 2; levels 0-2 hold more
-    candidates than k_octree keeps in LDS (its launch group's OctGroup::kcap), so the global spill path runs."""
+    """i.i.d. uniform noise: dense FAST responses, heavy octree phase 2.  A single image runs k_octree as
+    one launch over every level (the last ORBX_LP_OCTREE row), whose kcap only the first levels exceed
+    (level 0 at 640x480, levels 0 and 1 at 1241x376): their candidates beyond kcap go through the global
+    spill path, the other levels stay in LDS.  (The launch groups' spill path, with their smaller kcap,
+    is tests/test_gpu_octree.py's.)"""
     img = _image(seed, w, h, stress=True)
     ex = ORBextractor(nf, 1.2, 8, 20, 7)
     kps, desc = ex(img)
     ref = oracle.extract(oracle.params(nf, 1.2, 8, 20, 7), img)
     assert np.array_equal(kps.view(np.uint8), ref.keypoints.view(np.uint8))
     assert np.array_equal(desc, ref.descriptors)
+    from orb_slam2_commit_amd.orb import debug_launch_plan
+    one = debug_launch_plan(ex.params, w, h, 10).reshape(-1, 8)[-1]  # ORBX_LP_OCTREE: the one-launch row
+    assert (one[0], one[1]) == (0, 8) and one[7] >= 1
+    cells = dbg(ex, DBG_CELL_TABLE).reshape(-1, 8)
+    counts = dbg(ex, DBG_CELL_COUNTS)
+    T = np.bincount(cells[:, 0], weights=counts, minlength=8)
+    assert list(np.flatnonzero(T > one[5])) == ([0] if w == 640 else [0, 1]) and (T > 0).all(), (T, one[5])
 
 
 @pytest.mark.parametrize("params", [(1000, 1.2, 8, 20, 7), (500, 1.5, 4, 30, 10), (300, 1.1, 12, 12, 5),

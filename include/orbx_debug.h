@@ -58,9 +58,15 @@ enum {
   ORBX_LP_CELLS = 11,     /* x8 per FAST cell: level, x0, y0, x1, y1 (the detection region, inclusive), the cell's
                              offset in ORBX_DBG_CANDIDATES' logical view (as ORBX_DBG_CELL_TABLE), cap (its
                              candidate slots), kin (those of them that are inline) */
-  ORBX_LP_OCT_LEVELS = 12 /* x8 per level, DistributeOctTree's inputs and outputs: minBorderX, minBorderY, maxBorderX,
+  ORBX_LP_OCT_LEVELS = 12,/* x8 per level, DistributeOctTree's inputs and outputs: minBorderX, minBorderY, maxBorderX,
                              maxBorderY, N (the level's quota), nIni (clamped to 1), the level's offset in
                              ORBX_DBG_OCT_OUT, its output slots */
+  ORBX_LP_OCT_PYRAMID = 13/* x8 per k_octree launch group, ORBX_LP_OCTREE's rows in its order: the count pyramid's
+                             depth D (0: the group's blocks run the generic path only), the root count it is
+                             sized for (the largest nIni of the group's levels), its 16-bit counters (depths
+                             0..D, depth 0 padded to an even count) and their bytes, the pyramid path's LDS
+                             bytes, the generic path's, the dynamic LDS of the launch (the larger of the
+                             two), the largest depth the plan considers */
 };
 long long orbx_debug_launch_plan(const orbx_extractor_params* params, int width, int height, int what, int a0,
                                  int a1, int a2, long long* dst, size_t cap);
@@ -100,6 +106,15 @@ int orbx_debug_stereo_keypoints_check(const orbx_keypoint* kps, int n, int nleve
  * input passes orbx_debug_octree_candidates_check on the handle's geometry. */
 orbx_status orbx_debug_octree_candidates(orbx_extractor* h, int n_img, const int32_t* cell_counts,
                                          const uint32_t* candidates, int32_t* oct_count, uint32_t* oct_out);
+/* The same launch, which also reports per (image, level), n_img x nlevels values, the path the level's
+ * block took: 0 an empty level, 1 the count-pyramid path, 2 the generic path (ORBX_LP_OCT_PYRAMID; a
+ * block leaves the pyramid path when a round selects a node of depth D that holds several candidates,
+ * or when the level holds more than 65535).  The kernel writes the path through a pointer that is null
+ * in every other launch.  depth_cap >= 0 runs the launch groups at min(D, depth_cap) with the plan's
+ * LDS (0: the generic path alone, as a plan whose D is 0 runs); -1 leaves the plan's D. */
+orbx_status orbx_debug_octree_paths(orbx_extractor* h, int n_img, const int32_t* cell_counts,
+                                    const uint32_t* candidates, int depth_cap, int32_t* oct_count,
+                                    uint32_t* oct_out, int32_t* paths);
 /* ORBX_OK when n_img is in [1, 64], every cell's count is in [0, cap], every candidate read has x in
  * [minBorderX, maxBorderX) and y in [minBorderY, maxBorderY) of its cell's level, and no two
  * candidates of one level of one image share a pixel; ORBX_ERR_ARG otherwise (also for a geometry

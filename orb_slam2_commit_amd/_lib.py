@@ -383,7 +383,7 @@ SIGNATURES = {
     "orbx_debug_stereo_keypoints": ([P, P, P, P, C.c_int, P, P, C.c_int, C.c_float, C.c_float, P, P, P, P], C.c_int),
     "orbx_debug_stereo_keypoints_check": ([P, C.c_int, C.c_int, C.c_int, C.c_int], C.c_int),
     "orbx_debug_octree_candidates": ([P, C.c_int, P, P, P, P], C.c_int),
-    "orbx_debug_octree_candidates_check": ([C.POINTER(ExtractorParams), C.c_int, C.c_int, C.c_int, P, P], C.c_int),
+    "orbx_debug_octree_paths": ([P, C.c_int, P, P, C.c_int, P, P, P], C.c_int),    "orbx_debug_octree_candidates_check": ([C.POINTER(ExtractorParams), C.c_int, C.c_int, C.c_int, P, P], C.c_int),
     "orbx_debug_atan2_det": ([C.c_double, C.c_double], C.c_double),
     "orbx_debug_exp": ([P, C.c_int, P, C.c_int], C.c_int),
     "orbx_debug_initializer_host": ([P, C.c_int, P, C.c_float, C.c_int, P, C.c_int, P, P, C.c_int,
@@ -419,6 +419,9 @@ BA_CAPTURE_ITEMS = {
 BA_CAPTURE_HEADER = ("fired", "phase", "it", "q", "ok", "trial", "nc", "np", "ne", "na", "npa", "nposes")
 
 _lib = None
+# debug entries an ORBX_LIB_OVERRIDE library built from the parent commit may lack; the shipped
+# library must have every entry of SIGNATURES
+_NEWER_ENTRIES = {"orbx_debug_octree_paths"}
 
 
 def lib():
@@ -430,6 +433,8 @@ def lib():
                                % LIB_PATH)
         L = C.CDLL(LIB_PATH)
         for name, (args, res) in SIGNATURES.items():
+            if name in _NEWER_ENTRIES and os.environ.get("ORBX_LIB_OVERRIDE") and not hasattr(L, name):
+                continue  # a side-by-side library of an earlier commit (A/B runs); calling the entry still raises
             fn = getattr(L, name)
             fn.argtypes = args
             fn.restype = res

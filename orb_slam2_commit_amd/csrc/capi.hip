@@ -39,9 +39,8 @@ orbx_status get_plan(orbx_extractor* h, int W, int H, DevPlan** out) {
   if (e == hipSuccess) e = P->dyt.upload(P->yt.data(), P->yt.size());
   if (e != hipSuccess) return ORBX_ERR_HIP;
   build_launch_plan(*P, P->dxt.p, P->dyt.p, P->drzb.p, P->LP);
-  size_t mx = octree_smem_bytes(P->G.og_all.node_cap, P->G.og_all.cell_cap, P->G.og_all.kcap);
-  for (int g = 0; g < P->G.n_og; g++)
-    mx = std::max(mx, octree_smem_bytes(P->G.og[g].node_cap, P->G.og[g].cell_cap, P->G.og[g].kcap));
+  size_t mx = octree_group_smem(P->G.og_all);
+  for (int g = 0; g < P->G.n_og; g++) mx = std::max(mx, octree_group_smem(P->G.og[g]));
   if (octree_set_smem_limit(mx) != hipSuccess) return ORBX_ERR_HIP;
   *out = P.get();
   h->plans[key] = std::move(P);

@@ -232,9 +232,10 @@ extern "C" int orbx_debug_octree_candidates_check(const orbx_extractor_params* p
   return octree_candidates_ok(P, n_img, cell_counts, candidates) ? ORBX_OK : ORBX_ERR_ARG;
 }
 
-extern "C" orbx_status orbx_debug_octree_candidates(orbx_extractor* h, int n_img, const int32_t* cell_counts,
-                                                    const uint32_t* candidates, int32_t* oct_count,
-                                                    uint32_t* oct_out) {
+// paths (n_img x nlevels, or null) and depth_cap: launch_octree's
+static orbx_status octree_candidates_run(orbx_extractor* h, int n_img, const int32_t* cell_counts,
+                                         const uint32_t* candidates, int32_t* oct_count, uint32_t* oct_out,
+                                         int32_t* paths, int depth_cap) {
   if (!h || !oct_count || !oct_out) return ORBX_ERR_ARG;
   if (!h->last_plan) return ORBX_ERR_STATE;
   const DevPlan& P = *h->last_plan;
@@ -248,7 +249,8 @@ extern "C" orbx_status orbx_debug_octree_candidates(orbx_extractor* h, int n_img
   BlockCursor cur;
   const size_t o_cand = cur.take<uint32_t>(n * G.cand_total), o_cnt = cur.take<int>(n * G.ncells),
                o_kpos = cur.take<uint32_t>(n * G.cand_total), o_knode = cur.take<int>(n * G.cand_total),
-               o_oct = cur.take<uint32_t>(n * G.oct_total), o_octn = cur.take<int>(n * G.nlevels);
+               o_oct = cur.take<uint32_t>(n * G.oct_total), o_octn = cur.take<int>(n * G.nlevels),
+               o_path = cur.take<int>(n * G.nlevels);
   DevBuf<uint8_t> blk;
   if (blk.ensure(cur.end()) != hipSuccess) return ORBX_ERR_HIP;
   std::vector<uint32_t> raw(n * G.cand_total, 0);
@@ -269,6 +271,7 @@ extern "C" orbx_status orbx_debug_octree_candidates(orbx_extractor* h, int n_img
   chk(hipMemcpyAsync(blk.p + o_cnt, cell_counts, n * G.ncells * sizeof(int), hipMemcpyHostToDevice, st));
   chk(hipMemsetAsync(blk.p + o_oct, 0xFF, n * G.oct_total * 4, st));
   chk(hipMemsetAsync(blk.p + o_octn, 0xFF, n * G.nlevels * sizeof(int), st));
+  chk(hipMemsetAsync(blk.p + o_path, 0xFF, n * G.nlevels * sizeof(int), st));
   if (e == hipSuccess) {
     BatchPtrs B{};
     B.cand = (uint32_t*)(blk.p + o_cand);
@@ -278,18 +281,34 @@ extern "C" orbx_status orbx_debug_octree_candidates(orbx_extractor* h, int n_img
     B.oct = (uint32_t*)(blk.p + o_oct);
     B.oct_count = (int*)(blk.p + o_octn);
     // the dynamic LDS limit is per kernel, not per plan: another geometry's plan may have set it since
-    size_t mx = octree_smem_bytes(G.og_all.node_cap, G.og_all.cell_cap, G.og_all.kcap);
-    for (int g = 0; g < G.n_og; g++) mx = std::max(mx, octree_smem_bytes(G.og[g].node_cap, G.og[g].cell_cap, G.og[g].kcap));
+    size_t mx = octree_group_smem(G.og_all);
+    for (int g = 0; g < G.n_og; g++) mx = std::max(mx, octree_group_smem(G.og[g]));
     chk(octree_set_smem_limit(mx));
-    // the shipped launch path, as launch_extract_stages takes it
-    if (e == hipSuccess) chk(launch_octree(G, P.dG.p, P.dcells.p, B, n_img, st));
+    // the shipped launch path, as launch_extract_stages takes it (which passes no path pointer and no cap)
+    if (e == hipSuccess)
+      chk(launch_octree(G, P.dG.p, P.dcells.p, B, n_img, st, paths ? (int*)(blk.p + o_path) : nullptr, depth_cap));
   }
+  if (e == hipSuccess && paths)
+    chk(hipMemcpyAsync(paths, blk.p + o_path, n * G.nlevels * sizeof(int), hipMemcpyDeviceToHost, st));
   if (e == hipSuccess) {
     chk(hipMemcpyAsync(oct_count, blk.p + o_octn, n * G.nlevels * sizeof(int), hipMemcpyDeviceToHost, st));
     chk(hipMemcpyAsync(oct_out, blk.p + o_oct, n * G.oct_total * 4, hipMemcpyDeviceToHost, st));
   }
   chk(hipStreamSynchronize(st));  // before blk is freed
   return hip_status(e);
+}
+
+extern "C" orbx_status orbx_debug_octree_candidates(orbx_extractor* h, int n_img, const int32_t* cell_counts,
+                                                    const uint32_t* candidates, int32_t* oct_count,
+                                                    uint32_t* oct_out) {
+  return octree_candidates_run(h, n_img, cell_counts, candidates, oct_count, oct_out, nullptr, -1);
+}
+
+extern "C" orbx_status orbx_debug_octree_paths(orbx_extractor* h, int n_img, const int32_t* cell_counts,
+                                               const uint32_t* candidates, int depth_cap, int32_t* oct_count,
+                                               uint32_t* oct_out, int32_t* paths) {
+  if (!paths || depth_cap < -1) return ORBX_ERR_ARG;
+  return octree_candidates_run(h, n_img, cell_counts, candidates, oct_count, oct_out, paths, depth_cap);
 }
 
 extern "C" long long orbx_debug_launch_plan(const orbx_extractor_params* params, int width, int height, int what,
@@ -348,10 +367,22 @@ extern "C" long long orbx_debug_launch_plan(const orbx_extractor_params* params,
     case ORBX_LP_OCTREE: {
       auto row = [&](const OctGroup& g, long long max_batch) {
         out.insert(out.end(), {g.l0, g.l1, g.nt, g.node_cap, g.cell_cap, g.kcap,
-                               (long long)octree_smem_bytes(g.node_cap, g.cell_cap, g.kcap), max_batch});
+                               (long long)octree_group_smem(g), max_batch});
       };
       for (int g = 0; g < G.n_og; g++) row(G.og[g], -1);
       row(G.og_all, kOctOneLaunch);
+      break;
+    }
+    case ORBX_LP_OCT_PYRAMID: {
+      auto row = [&](const OctGroup& g) {
+        const long long n = g.depth > 0 ? oct_pyr_counters(g.nini, g.depth) : 0;
+        out.insert(out.end(), {g.depth, g.nini, n, (n + 1) / 2 * 4,
+                               g.depth > 0 ? (long long)oct_pyr_layout(g.node_cap, g.cell_cap, g.pcap, g.span, g.nini, g.depth).bytes : 0,
+                               (long long)octree_smem_bytes(g.node_cap, g.cell_cap, g.kcap),
+                               (long long)octree_group_smem(g), kOctMaxDepth});
+      };
+      for (int g = 0; g < G.n_og; g++) row(G.og[g]);
+      row(G.og_all);
       break;
     }
     case ORBX_LP_CELLS: {

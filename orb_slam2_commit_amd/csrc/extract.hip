@@ -1221,23 +1221,26 @@ __device__ __forceinline__ void oct_cands(int T, const OctCands& c, F f) {
 }
 
 // Phase probe (build with -DORBX_OCT_PROBE only; tools/oct_probe.py): per block, s_memtime ticks
-// of the candidate load, the roots, the phase-1 and phase-2 rounds (with their counts) and the
-// best-response pass, plus the level's candidate count; 8 words per block, indexed img * nlevels + l.
+// of the path that finished the block: [0] the candidate pass before the rounds (pyramid path: the
+// histogram and the sums above it; generic path: the load into LDS), [1] the roots, [2] / [3] the
+// phase-1 rounds and their count, [4] / [5] phase 2's, [6] the path's total, [7] the level's
+// candidate count, [8] the final pass (best response and output), [9] the path (1 pyramid, 2
+// generic), [10] ticks spent on the pyramid path before the block left it for the generic one;
+// kOctProbeWords words per block, indexed img * nlevels + l.
 #ifdef ORBX_OCT_PROBE
+constexpr int kOctProbeWords = 12;
 __device__ unsigned int* oct_probe_buf;
 #define OCT_TS(v) const unsigned long long v = __builtin_amdgcn_s_memtime()
 #else
 #define OCT_TS(v)
 #endif
 
+// The generic path: candidates held in LDS (or the global spill), every round walks them twice.  Any
+// depth, any candidate count.  Returns the block's path: 0 (empty level) or 2.
 template <int NT>
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(6))) void k_octree(const Geometry* __restrict__ G, const CellInfo* __restrict__ cells,
-                                               BatchPtrs B, OctGroup grp) {
-  extern __shared__ __align__(16) unsigned char smem_raw[];
-  // level-major grid (images fastest): every image's level-0 block (the longest) is dispatched
-  // first and the short top levels last, so the kernel's tail is short blocks (longest first;
-  // image-major order left one level-0 block per image until the end: 0.302 -> 0.232 ms per step)
-  const int img = blockIdx.x, l = grp.l0 + blockIdx.y, tid = threadIdx.x;
+__device__ int oct_generic(const Geometry* __restrict__ G, const CellInfo* __restrict__ cells, const BatchPtrs& B,
+                           const OctGroup& grp, unsigned char* smem_raw, int img, int l) {
+  const int tid = threadIdx.x;
   const LevelGeom& L = G->lv[l];
   const int NC = grp.node_cap;
   const int NP2 = next_pow2(NC);
@@ -1280,7 +1283,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(6))) void k_
   if (tid == 0) s.cpre[ncl] = T;
   if (T == 0) {
     if (tid == 0) *oct_cnt = 0;
-    return;
+    return 0;
   }
   const int nIni = L.nIni;
   const float hX = L.hX;
@@ -1563,6 +1566,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(6))) void k_
     }
   }
   __syncthreads();
+  OCT_TS(otf);
   // 3. best response per node: max score, then lowest candidate index
   for (int i = tid; i < S; i += NT) s.key[i] = 0;
   __syncthreads();
@@ -1582,7 +1586,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(6))) void k_
 #ifdef ORBX_OCT_PROBE
   if (tid == 0 && oct_probe_buf) {
     const unsigned long long ot3 = __builtin_amdgcn_s_memtime();
-    unsigned int* o = oct_probe_buf + ((size_t)img * G->nlevels + l) * 8;
+    unsigned int* o = oct_probe_buf + ((size_t)img * G->nlevels + l) * kOctProbeWords;
     o[0] = (unsigned int)(ot1 - ot0);
     o[1] = (unsigned int)(ot2 - ot1);
     o[2] = (unsigned int)ot_p1;
@@ -1591,8 +1595,452 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(6))) void k_
     o[5] = (unsigned int)n_p2;
     o[6] = (unsigned int)(ot3 - ot0);
     o[7] = (unsigned int)T;
+    o[8] = (unsigned int)(ot3 - otf);
+    o[9] = 2;
   }
 #endif
+  return 2;
+}
+
+// ------------------------------------------------------ octree: the count-pyramid path
+// DivideNode splits a box at x0 + ceil((x1 - x0) / 2), y0 + ceil((y1 - y0) / 2): the whole tree's
+// geometry is fixed by the level's roots, and a candidate's child digits down to any depth are a
+// function of its position and its root.  Everything the rounds decide (which nodes split, the
+// children kept, nexp, the switch to phase 2, phase 2's (size, sequence) order, the stop conditions)
+// depends on the candidates only through how many lie in each box.  So: ONE pass over the candidates
+// counts them into the boxes of depth D, the counts of depths D - 1 .. 0 are summed from those, the
+// rounds run on the node list alone (a node's children's counts are two dword reads), and one more
+// pass hands each candidate to its final node for the best-response pick.  Two candidate passes,
+// where the generic path takes two per round and three around them.
+//
+// A block leaves this path for the generic one (from the start; nothing has been written to global
+// memory by then) when a round selects a node of depth D with more than one candidate for
+// splitting, or when the level holds more candidates than a 16-bit counter counts.
+// f(k, v) for candidate k = 0 .. T-1 of the level in vToDistributeKeys order (cells row-major), v its
+// FAST slot; cpre: exclusive prefix of the level's cell counts, cpre[ncl] = T
+template <int NT, class F>
+__device__ __forceinline__ void oct_walk(const LevelGeom& L, const CellInfo* __restrict__ cells,
+                                         const uint32_t* __restrict__ cand, const int* cpre, int T, F f) {
+  const int tid = threadIdx.x, ncl = L.cell_end - L.cell_begin;
+  if (ncl >= NT / 2) {
+    // many cells: one thread per cell walks its survivors, four loads in flight at a time
+    for (int c = tid; c < ncl; c += NT) {
+      const int k0 = cpre[c], n = cpre[c + 1] - k0;
+      const CellInfo& ci = cells[L.cell_begin + c];
+      const int kin = ci.kin, off = ci.cand_off, ovf = ci.ovf_off - kin;  // slot i: i < kin ? off + i : ovf + i
+      int i = 0;
+      for (; i + 4 <= n; i += 4) {
+        const uint32_t v0 = cand[(i < kin ? off : ovf) + i], v1 = cand[(i + 1 < kin ? off : ovf) + i + 1],
+                       v2 = cand[(i + 2 < kin ? off : ovf) + i + 2], v3 = cand[(i + 3 < kin ? off : ovf) + i + 3];
+        f(k0 + i, v0);
+        f(k0 + i + 1, v1);
+        f(k0 + i + 2, v2);
+        f(k0 + i + 3, v3);
+      }
+      for (; i < n; i++) f(k0 + i, cand[(i < kin ? off : ovf) + i]);
+    }
+  } else {
+    // few cells with many survivors each: one thread per candidate, its cell by binary search
+    for (int k = tid; k < T; k += NT) {
+      int lo = 0, hi = ncl - 1;  // last c with cpre[c] <= k
+      while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (cpre[mid] <= k) lo = mid; else hi = mid - 1;
+      }
+      f(k, cand[cell_slot(cells[L.cell_begin + lo], k - cpre[lo])]);
+    }
+  }
+}
+
+// Returns the block's path: 0 (empty level), 1 (done), 2 (nothing written: run the generic path).
+template <int NT>
+__device__ int oct_pyramid(const Geometry* __restrict__ G, const CellInfo* __restrict__ cells, const BatchPtrs& B,
+                           const OctGroup& grp, int D, unsigned char* smem_raw, int img, int l) {
+  const int tid = threadIdx.x;
+  const LevelGeom& L = G->lv[l];
+  const int NC = grp.node_cap;
+  const int nIni = L.nIni;
+  const OctPyrLayout lay = oct_pyr_layout(NC, grp.cell_cap, grp.pcap, grp.span, nIni, D);
+  uint64_t* key = (uint64_t*)(smem_raw + lay.key);
+  uint64_t* tmp = (uint64_t*)(smem_raw + lay.tmp);
+  uint32_t* cell = (uint32_t*)(smem_raw + lay.cell);
+  int* cnt = (int*)(smem_raw + lay.cnt);
+  int* seq = (int*)(smem_raw + lay.seq);
+  int* sa = (int*)(smem_raw + lay.sa);
+  int* sb = (int*)(smem_raw + lay.sb);
+  int* cpre = (int*)(smem_raw + lay.cpre);
+  int* ctrl = (int*)(smem_raw + lay.ctrl);
+  int16_t* nidx = (int16_t*)(smem_raw + lay.nidx);
+  uint32_t* kp = (uint32_t*)(smem_raw + lay.kp);
+  uint16_t* xtab = (uint16_t*)(smem_raw + lay.tab);
+  uint32_t* pyrw = (uint32_t*)(smem_raw + lay.pyr);  // the counters as dwords (a pair each)
+  uint16_t* pyr = (uint16_t*)(smem_raw + lay.pyr);
+  uint32_t* oct_out = B.oct + (size_t)img * G->oct_total + L.oct_off;
+  int* oct_cnt = B.oct_count + (size_t)img * G->nlevels + l;
+
+  OCT_TS(ot0);
+#ifdef ORBX_OCT_PROBE
+  unsigned long long ot_p1 = 0, ot_p2 = 0;
+  int n_p1 = 0, n_p2 = 0;
+#endif
+  // 1. the level's candidate count, and every box's
+  const int ncl = L.cell_end - L.cell_begin;
+  for (int c = tid; c < ncl; c += NT) cpre[c] = B.cell_count[(size_t)img * G->ncells + L.cell_begin + c];
+  __syncthreads();
+  const int T = block_exclusive_scan<NT>(cpre, ncl);
+  if (tid == 0) cpre[ncl] = T;
+  if (T == 0) {
+    if (tid == 0) *oct_cnt = 0;
+    return 0;
+  }
+  if (T > 0xFFFF) return 2;
+  const float hX = L.hX;
+  const int minBX = L.minBX, minBY = L.minBY, boxH = max(L.maxBY - minBY, 1);
+  const int npw = (oct_pyr_counters(nIni, D) + 1) / 2;
+  for (int i = tid; i < npw; i += NT) pyrw[i] = 0;
+  if (tid == 0) ctrl[0] = 0;  // 1: a round selected a node of depth D
+  const int boxW = max(L.maxBX - minBX, 1);
+  uint16_t* ytab = xtab + boxW;
+  for (int i = tid; i < boxW + boxH; i += NT) {
+    int lo, hi, g = 0;
+    const bool isx = i < boxW;
+    const float f = (float)(isx ? i : i - boxW);
+    if (isx) {
+      g = (int)(f / hX);
+      g = min(max(g, 0), nIni - 1);
+      lo = (int)(hX * (float)g);
+      hi = (int)(hX * (float)(g + 1));
+    } else {
+      lo = 0;
+      hi = boxH;
+    }
+    for (int d = 0; d < D; d++) {
+      const int h = (int)__builtin_ceilf((float)(hi - lo) / 2);
+      const int q = f < (float)(lo + h) ? 0 : 1;
+      if (q) lo += h; else hi = lo + h;
+      g = 2 * g + q;
+    }
+    xtab[i] = (uint16_t)g;
+  }
+  __syncthreads();
+  const uint32_t* cand = B.cand + (size_t)img * G->cand_total;
+  const int offD = oct_pyr_off(nIni, D);
+  // a candidate's box of depth D.  DivideNode halves x and y independently, and the root a candidate is
+  // filed under is a function of its x: gx at depth D depends on the column alone, gy on the row
+  // alone.  (xtab / ytab, filled above with the same arithmetic: the root as DistributeOctTree files
+  // it, then D halvings.)
+  auto leaf = [&](uint32_t v, int& gx, int& gy) {
+    const int xr = (int)(v & 0xFFF) - minBX, yr = (int)((v >> 12) & 0xFFF) - minBY;
+    gx = xtab[min(max(xr, 0), boxW - 1)];
+    gy = ytab[min(max(yr, 0), boxH - 1)];
+  };
+  const int kcap = grp.pcap;
+  oct_walk<NT>(L, cells, cand, cpre, T, [&](int k, uint32_t v) {
+    int gx, gy;
+    leaf(v, gx, gy);
+    const int idx = offD + gy * (nIni << D) + gx;
+    atomicAdd(&pyrw[idx >> 1], 1u << ((idx & 1) * 16));
+    if (k < kcap) kp[k] = v;  // kept for the final pass when the whole level fits
+  });
+  __syncthreads();
+  for (int d = D - 1; d >= 0; d--) {
+    const int W = nIni << d, n = W << d, o = oct_pyr_off(nIni, d), oc = oct_pyr_off(nIni, d + 1);
+    for (int c = tid; c < n; c += NT) {
+      const int gy = c / W, gx = c - gy * W;
+      const int ci = oc + 2 * gy * 2 * W + 2 * gx;  // children (2gx, 2gy), (2gx + 1, 2gy); the next row 2W on
+      const uint32_t w0 = pyrw[ci >> 1], w1 = pyrw[(ci + 2 * W) >> 1];
+      pyr[o + c] = (uint16_t)((w0 & 0xFFFF) + (w0 >> 16) + (w1 & 0xFFFF) + (w1 >> 16));
+    }
+    __syncthreads();
+  }
+  OCT_TS(ot1);
+  // a node's box (d, gx, gy) as one word; its counter; its children's counts by digit
+  auto slot = [&](uint32_t c) {
+    const int d = (int)(c >> 28);
+    return oct_pyr_off(nIni, d) + (int)((c >> 20) & 0xFF) * (nIni << d) + (int)(c & 0xFFFFF);
+  };
+  auto kids = [&](uint32_t c, int* cc) {
+    const int d = (int)(c >> 28) + 1, W = nIni << d;
+    const int ci = oct_pyr_off(nIni, d) + 2 * (int)((c >> 20) & 0xFF) * W + 2 * (int)(c & 0xFFFFF);
+    const uint32_t w0 = pyrw[ci >> 1], w1 = pyrw[(ci + W) >> 1];
+    cc[0] = (int)(w0 & 0xFFFF);
+    cc[1] = (int)(w0 >> 16);
+    cc[2] = (int)(w1 & 0xFFFF);
+    cc[3] = (int)(w1 >> 16);
+  };
+  auto child = [&](uint32_t c, int q) {
+    return (((c >> 28) + 1) << 28) | ((2 * ((c >> 20) & 0xFF) + (uint32_t)(q >> 1)) << 20) |
+           (2 * (c & 0xFFFFF) + (uint32_t)(q & 1));
+  };
+  constexpr uint16_t kSplit = 0xFFFF;  // a split node's own counter: descend (node indices are < 8192)
+  // 2. roots -> list (empty roots erased, src/ORBextractor.cc:604-615)
+  for (int i = tid; i < nIni; i += NT) sa[i] = pyr[i] > 0 ? 1 : 0;
+  __syncthreads();
+  int S = block_exclusive_scan<NT>(sa, nIni);
+  for (int i = tid; i < nIni; i += NT) {
+    if (pyr[i] > 0) {
+      const int ni = sa[i];
+      cell[ni] = (uint32_t)i;
+      cnt[ni] = pyr[i];
+      seq[ni] = i;
+    }
+  }
+  OCT_TS(ot2);
+  int cur = 0;
+  int seqBase = nIni;
+  int phase = 1;
+  const int N = L.nfeat;
+  for (int round = 0; round < 256; round++) {
+    __syncthreads();
+#ifdef ORBX_OCT_PROBE
+    const unsigned long long rt0 = __builtin_amdgcn_s_memtime();
+    const int rphase = phase;
+    struct RoundStamp {
+      unsigned long long t0;
+      int ph;
+      unsigned long long *p1, *p2;
+      int *n1, *n2;
+      __device__ ~RoundStamp() {
+        const unsigned long long d = __builtin_amdgcn_s_memtime() - t0;
+        if (ph == 1) { *p1 += d; ++*n1; } else { *p2 += d; ++*n2; }
+      }
+    } rstamp{rt0, rphase, &ot_p1, &ot_p2, &n_p1, &n_p2};
+#endif
+    const int nb = cur ^ 1;
+    const uint32_t* ccell = cell + cur * NC;
+    const int *ccnt = cnt + cur * NC, *cseq = seq + cur * NC;
+    uint32_t* ncell = cell + nb * NC;
+    int *ncnt = cnt + nb * NC, *nseq = seq + nb * NC;
+    int C, Snew;
+    if (phase == 1) {
+      // split every node with > 1 candidate, in list order.  One scan of packed
+      // (children | kept << 16 | expandable children << 32) gives each node its
+      // child and kept positions and the round's totals.
+      for (int i = tid; i < S; i += NT) {
+        uint64_t v = 1ull << 16;
+        if (ccnt[i] > 1) {
+          v = 0;
+          if ((int)(ccell[i] >> 28) >= D) {
+            ctrl[0] = 1;
+          } else {
+            int cc[4];
+            kids(ccell[i], cc);
+            for (int q = 0; q < 4; q++) v += (cc[q] > 0 ? 1ull : 0ull) + (cc[q] > 1 ? (1ull << 32) : 0ull);
+          }
+        }
+        key[i] = v;
+      }
+      __syncthreads();
+      if (ctrl[0]) return 2;
+      const uint64_t tot = block_scan_excl<NT, uint64_t>(key, S);
+      C = (int)(tot & 0xFFFF);
+      const int Sg = (int)((tot >> 16) & 0xFFFF);
+      const int nexp = (int)(tot >> 32);
+      for (int i = tid; i < S; i += NT) {
+        const uint64_t pre = key[i];
+        if (ccnt[i] > 1) {
+          const uint32_t c = ccell[i];
+          int cc[4];
+          kids(c, cc);
+          int rank = 0;
+          for (int q = 0; q < 4; q++) {
+            if (cc[q] == 0) continue;
+            const int p = (int)(pre & 0xFFFF) + rank++;
+            const int ni = C - 1 - p;
+            ncell[ni] = child(c, q);
+            ncnt[ni] = cc[q];
+            nseq[ni] = seqBase + p;
+          }
+          pyr[slot(c)] = kSplit;
+        } else {
+          const int ni = C + (int)((pre >> 16) & 0xFFFF);
+          ncell[ni] = ccell[i];
+          ncnt[ni] = ccnt[i];
+          nseq[ni] = cseq[i];
+        }
+      }
+      Snew = C + Sg;
+      seqBase += C;
+      const bool finish = Snew >= N || Snew == S;
+      S = Snew;
+      cur = nb;
+      if (finish) break;
+      if (Snew + 3 * nexp > N) phase = 2;
+    } else {
+      // phase 2: split the largest (size, seq) first until the list reaches N.  A node of depth D
+      // counts as one child here (its children's counts are not held): the walk's stop m is then
+      // either right or at or past that node, and a selected node of depth D ends this path.
+      auto nchild = [&](int n) {
+        if ((int)(ccell[n] >> 28) >= D) return 1;
+        int cc[4];
+        kids(ccell[n], cc);
+        return (cc[0] > 0) + (cc[1] > 0) + (cc[2] > 0) + (cc[3] > 0);
+      };
+      for (int i = tid; i < S; i += NT) sa[i] = ccnt[i] > 1 ? 1 : 0;
+      __syncthreads();
+      const int M = block_exclusive_scan<NT>(sa, S);
+      const int P2 = next_pow2(max(M, 2));
+      for (int i = tid; i < P2; i += NT) key[i] = 0;
+      __syncthreads();
+      for (int i = tid; i < S; i += NT)
+        if (ccnt[i] > 1) key[sa[i]] = ((uint64_t)ccnt[i] << 43) | ((uint64_t)cseq[i] << 13) | (uint64_t)i;
+      __syncthreads();
+      if (M <= kOctRankSortMax) {
+        // descending order by rank (keys are distinct: they carry the node index): key j goes to
+        // #{keys > key j}; one pass over the M keys per key instead of log2(P2)^2/2 barrier stages
+        for (int j = tid; j < M; j += NT) {
+          const uint64_t x = key[j];
+          int r = 0;
+#pragma unroll 4
+          for (int y = 0; y < M; y++) r += key[y] > x ? 1 : 0;
+          tmp[r] = x;
+        }
+        __syncthreads();
+        for (int j = tid; j < M; j += NT) key[j] = tmp[j];
+        __syncthreads();
+      } else {
+        bitonic_sort_desc<NT>(key, P2);
+      }
+      if (tid == 0) ctrl[1] = M - 1;
+      for (int j = tid; j < M; j += NT) sb[j] = nchild((int)(key[j] & 0x1FFF)) - 1;
+      __syncthreads();
+      // inclusive prefix of growth; first j reaching N
+      block_exclusive_scan<NT>(sb, M);  // exclusive
+      for (int j = tid; j < M; j += NT) {
+        const int nc = nchild((int)(key[j] & 0x1FFF));
+        if (S + sb[j] + (nc - 1) >= N) atomicMin(&ctrl[1], j);
+      }
+      __syncthreads();
+      const int m = ctrl[1];
+      // children positions in processing order j = 0..m
+      for (int j = tid; j < M; j += NT) {
+        int nc = 0;
+        if (j <= m) {
+          const int n = (int)(key[j] & 0x1FFF);
+          if ((int)(ccell[n] >> 28) >= D) ctrl[0] = 1;
+          nc = nchild(n);
+        }
+        sb[j] = nc;
+      }
+      for (int i = tid; i < S; i += NT) nidx[i] = -1;  // -2: split this round, set below
+      __syncthreads();
+      if (ctrl[0]) return 2;
+      C = block_exclusive_scan<NT>(sb, M);
+      for (int j = tid; j <= m; j += NT) nidx[(int)(key[j] & 0x1FFF)] = -2;
+      __syncthreads();
+      for (int i = tid; i < S; i += NT) sa[i] = nidx[i] == -2 ? 0 : 1;
+      __syncthreads();
+      const int rest = block_exclusive_scan<NT>(sa, S);
+      for (int j = tid; j <= m; j += NT) {
+        const int i = (int)(key[j] & 0x1FFF);
+        const uint32_t c = ccell[i];
+        int cc[4];
+        kids(c, cc);
+        int rank = 0;
+        for (int q = 0; q < 4; q++) {
+          if (cc[q] == 0) continue;
+          const int p = sb[j] + rank++;
+          const int ni = C - 1 - p;
+          ncell[ni] = child(c, q);
+          ncnt[ni] = cc[q];
+          nseq[ni] = seqBase + p;
+        }
+        pyr[slot(c)] = kSplit;
+      }
+      for (int i = tid; i < S; i += NT) {
+        if (nidx[i] == -2) continue;
+        const int ni = C + sa[i];
+        ncell[ni] = ccell[i];
+        ncnt[ni] = ccnt[i];
+        nseq[ni] = cseq[i];
+      }
+      Snew = C + rest;
+      seqBase += C;
+      const bool finish = Snew >= N || Snew == S;
+      S = Snew;
+      cur = nb;
+      if (finish) break;
+    }
+  }
+  __syncthreads();
+  OCT_TS(otf);
+  // 3. every final node's list index into its own counter, then each candidate descends from its
+  // root through the split boxes to the index; best response per node: max score, then lowest
+  // candidate index
+  for (int i = tid; i < S; i += NT) {
+    key[i] = 0;
+    pyr[slot((cell + cur * NC)[i])] = (uint16_t)i;
+  }
+  __syncthreads();
+  // the box of depth d above a box of depth D is its coordinates shifted: the D + 1 counters on a
+  // candidate's way down are read side by side, the first that is no split mark is its node
+  auto hand_over = [&](int k, uint32_t v) {
+    int gx, gy;
+    leaf(v, gx, gy);
+    uint32_t nd = kSplit;
+#pragma unroll
+    for (int d = kOctMaxDepth; d >= 0; d--) {
+      if (d > D) continue;
+      const uint32_t c = pyr[oct_pyr_off(nIni, d) + (gy >> (D - d)) * (nIni << d) + (gx >> (D - d))];
+      nd = c != kSplit ? c : nd;  // the shallowest wins: below a listed node the counters are stale counts
+    }
+    const uint64_t kv = ((uint64_t)(v >> 24) << 56) | ((uint64_t)(0xFFFFFFu - (uint32_t)k) << 24) | (uint64_t)(v & 0xFFFFFF);
+    if (nd < (uint32_t)S) atomicMax((unsigned long long*)&key[nd], (unsigned long long)kv);
+  };
+  if (T <= kcap) {
+    for (int k = tid; k < T; k += NT) hand_over(k, kp[k]);
+  } else {
+    oct_walk<NT>(L, cells, cand, cpre, T, hand_over);
+  }
+  __syncthreads();
+  const int nout = min(S, L.oct_cap);
+  for (int i = tid; i < nout; i += NT) {
+    const uint64_t kv = key[i];
+    oct_out[i] = ((uint32_t)(kv >> 56) << 24) | (uint32_t)(kv & 0xFFFFFF);
+  }
+  if (tid == 0) *oct_cnt = nout;
+#ifdef ORBX_OCT_PROBE
+  if (tid == 0 && oct_probe_buf) {
+    const unsigned long long ot3 = __builtin_amdgcn_s_memtime();
+    unsigned int* o = oct_probe_buf + ((size_t)img * G->nlevels + l) * kOctProbeWords;
+    o[0] = (unsigned int)(ot1 - ot0);
+    o[1] = (unsigned int)(ot2 - ot1);
+    o[2] = (unsigned int)ot_p1;
+    o[3] = (unsigned int)n_p1;
+    o[4] = (unsigned int)ot_p2;
+    o[5] = (unsigned int)n_p2;
+    o[6] = (unsigned int)(ot3 - ot0);
+    o[7] = (unsigned int)T;
+    o[8] = (unsigned int)(ot3 - otf);
+    o[9] = 1;
+  }
+#endif
+  return 1;
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(6))) void k_octree(const Geometry* __restrict__ G, const CellInfo* __restrict__ cells,
+                                               BatchPtrs B, OctGroup grp, int* __restrict__ path) {
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  // level-major grid (images fastest): every image's level-0 block (the longest) is dispatched
+  // first and the short top levels last, so the kernel's tail is short blocks (longest first;
+  // image-major order left one level-0 block per image until the end: 0.302 -> 0.232 ms per step)
+  const int img = blockIdx.x, l = grp.l0 + blockIdx.y;
+  OCT_TS(kt0);
+  int p = 2;
+  if (grp.depth > 0) p = oct_pyramid<NT>(G, cells, B, grp, grp.depth, smem_raw, img, l);
+  if (p == 2) {
+    __syncthreads();  // the two paths overlay the block's LDS
+#ifdef ORBX_OCT_PROBE
+    const unsigned long long kt1 = __builtin_amdgcn_s_memtime();
+#endif
+    p = oct_generic<NT>(G, cells, B, grp, smem_raw, img, l);
+#ifdef ORBX_OCT_PROBE
+    if (threadIdx.x == 0 && oct_probe_buf)
+      oct_probe_buf[((size_t)img * G->nlevels + l) * kOctProbeWords + 10] = grp.depth > 0 ? (unsigned int)(kt1 - kt0) : 0;
+#endif
+  }
+  if (path && threadIdx.x == 0) path[(size_t)img * G->nlevels + l] = p;
 }
 
 // --------------------------------------------------------------- describe
@@ -1935,15 +2383,16 @@ hipError_t launch_blur(const Geometry& Gh, const Geometry* Gd, const int* tile_l
 // (Launch order of the groups measured flat.)  One or two images: all levels in one launch (the groups'
 // launches would run one after the other with a few blocks each)
 hipError_t launch_octree(const Geometry& Gh, const Geometry* Gd, const CellInfo* cells, const BatchPtrs& B, int n_img,
-                         hipStream_t st) {
+                         hipStream_t st, int* path, int depth_cap) {
   const bool one = n_img <= kOctOneLaunch;
   for (int gi = 0; gi < (one ? 1 : Gh.n_og); gi++) {
-    const OctGroup& og = one ? Gh.og_all : Gh.og[gi];
-    const size_t smem = octree_smem_bytes(og.node_cap, og.cell_cap, og.kcap);
+    OctGroup og = one ? Gh.og_all : Gh.og[gi];
+    const size_t smem = octree_group_smem(og);  // the plan's, whatever the cap
+    if (depth_cap >= 0) og.depth = min(og.depth, depth_cap);
     if (og.nt == 512)
-      hipLaunchKernelGGL(k_octree<512>, dim3(n_img, og.l1 - og.l0), dim3(512), smem, st, Gd, cells, B, og);
+      hipLaunchKernelGGL(k_octree<512>, dim3(n_img, og.l1 - og.l0), dim3(512), smem, st, Gd, cells, B, og, path);
     else
-      hipLaunchKernelGGL(k_octree<256>, dim3(n_img, og.l1 - og.l0), dim3(256), smem, st, Gd, cells, B, og);
+      hipLaunchKernelGGL(k_octree<256>, dim3(n_img, og.l1 - og.l0), dim3(256), smem, st, Gd, cells, B, og, path);
   }
   return hipPeekAtLastError();
 }

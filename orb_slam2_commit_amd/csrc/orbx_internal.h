@@ -50,6 +50,11 @@ struct OctGroup {
   int node_cap;  // LDS node capacity (max over the group's levels, multiple of 64)
   int cell_cap;  // max cells of one level
   int kcap;      // candidates of a level kept in LDS (the rest in global scratch)
+  int depth;     // count-pyramid depth D of the group's blocks (0: the generic path only)
+  int nini;      // largest root count of the group's levels (sizes the pyramid)
+  int span;      // largest border-box width + height of the group's levels (the pyramid path's column
+                 // and row tables)
+  int pcap;      // candidates the pyramid path keeps in LDS: kcap plus what the group's LDS has left
 };
 
 // k_octree's dynamic LDS for a launch group (OctSmem in extract.hip carves it up in this order); the
@@ -75,6 +80,50 @@ __host__ __device__ inline size_t octree_smem_bytes(int NC, int cell_cap, int kc
   b += 8 * sizeof(int);
   b += (size_t)kcap * (sizeof(uint32_t) + sizeof(uint16_t));
   return b;
+}
+
+// k_octree's count pyramid: one 16-bit counter per box of the fixed split geometry, depth d = 0 (the
+// roots) .. D; box (d, gx, gy) has gx < nIni << d, gy < 1 << d and sits at oct_pyr_off(nIni, d) +
+// gy * (nIni << d) + gx.  Depth 0 is padded to an even count, so the two children (2gx, 2gx + 1) of a
+// row share one aligned dword.
+constexpr int kOctMaxDepth = 6;
+__host__ __device__ inline int oct_pyr_off(int nIni, int d) {
+  return d == 0 ? 0 : ((nIni + 1) & ~1) + nIni * (((1 << (2 * d)) - 4) / 3);
+}
+__host__ __device__ inline int oct_pyr_counters(int nIni, int D) { return oct_pyr_off(nIni, D + 1); }
+
+// LDS of k_octree's pyramid path (byte offsets into the block's dynamic LDS, which it shares with
+// the generic path's OctSmem: a block runs one path at a time)
+struct OctPyrLayout {
+  int key, tmp, cell, cnt, seq, sa, sb, cpre, ctrl, kp, nidx, tab, pyr, bytes;
+};
+__host__ __device__ inline OctPyrLayout oct_pyr_layout(int NC, int cell_cap, int pcap, int span, int nIni, int D) {
+  OctPyrLayout o;
+  int b = 0;
+  o.key = b;  b += next_pow2(NC) * 8;  // u64 [NP2]: packed scan words, sort keys, best responses
+  o.tmp = b;  b += NC * 8;             // u64 [NC]: the rank sort's output
+  o.cell = b; b += 2 * NC * 4;         // double-buffered node list: box d << 28 | gy << 20 | gx,
+  o.cnt = b;  b += 2 * NC * 4;         //   candidates,
+  o.seq = b;  b += 2 * NC * 4;         //   creation sequence
+  o.sa = b;   b += NC * 4;
+  o.sb = b;   b += NC * 4;
+  o.cpre = b; b += (cell_cap + 1) * 4;
+  o.ctrl = b; b += 8 * 4;
+  o.kp = b;   b += pcap * 4;           // the level's first pcap candidates as read (score << 24 | y << 12 | x)
+  o.pyr = b;  b += (oct_pyr_counters(nIni, D) + 1) / 2 * 4;
+  o.nidx = b; b += NC * 2;
+  o.tab = b;  b += span * 2;           // u16: column x -> gx at depth D, then row y -> gy
+  o.bytes = (b + 3) & ~3;
+  return o;
+}
+
+// dynamic LDS of a launch group's blocks.  The plan picks the group's depth so that the pyramid
+// path fits in what the generic path takes: a group's LDS per block, and with it the blocks per CU,
+// is what it was before the pyramid.
+__host__ __device__ inline size_t octree_group_smem(const OctGroup& g) {
+  const size_t a = octree_smem_bytes(g.node_cap, g.cell_cap, g.kcap);
+  const size_t b = g.depth > 0 ? (size_t)oct_pyr_layout(g.node_cap, g.cell_cap, g.pcap, g.span, g.nini, g.depth).bytes : 0;
+  return a > b ? a : b;
 }
 
 struct Geometry {
@@ -200,8 +249,10 @@ struct StageTimer;
 hipError_t upload_constants(const int* umax16, const int* gauss7);
 hipError_t launch_blur(const Geometry& Gh, const Geometry* Gd, const int* tile_level, const BatchPtrs& B, int n_img,
                        hipStream_t st);
+// path (device, n_img x nlevels, or null): the path each block took, 0 empty level, 1 pyramid, 2 generic;
+// depth_cap >= 0 lowers the groups' pyramid depth for this launch (the debug entry's; 0: generic only)
 hipError_t launch_octree(const Geometry& Gh, const Geometry* Gd, const CellInfo* cells, const BatchPtrs& B, int n_img,
-                         hipStream_t st);
+                         hipStream_t st, int* path = nullptr, int depth_cap = -1);
 hipError_t launch_extract_stages(const Geometry& Gh, const Geometry* Gd, const CellInfo* cells, const int* tile_level,
                                  const LaunchPlan& LP, const BatchPtrs& B, int n_img, orbx_keypoint* kps, uint8_t* desc,
                                  int32_t* counts, int kp_cap, hipStream_t st, StageTimer* T);

@@ -392,6 +392,24 @@ orbx_status build_plan(const orbx_extractor_params& p, const Tables& t, int W, i
       kc = std::min(kc, (long long)(mc + 63) / 64 * 64);
       while (kc > 64 && (long long)octree_smem_bytes(g.node_cap, g.cell_cap, (int)kc) > 160 * 1024 - 1024) kc -= 64;
       g.kcap = (int)kc;
+      // the count pyramid's depth: the deepest whose LDS, for the group's largest root count, fits in
+      // what the generic path takes anyway (the block's LDS, and the blocks per CU, stay as they were)
+      g.nini = 1;
+      g.span = 2;
+      for (int l = l0; l < l1; l++) {
+        g.nini = std::max(g.nini, G.lv[l].nIni);
+        g.span = std::max(g.span, std::max(G.lv[l].maxBX - G.lv[l].minBX, 0) + std::max(G.lv[l].maxBY - G.lv[l].minBY, 0) + 2);
+      }
+      g.depth = 0;
+      g.pcap = g.kcap;
+      const long long have = (long long)octree_smem_bytes(g.node_cap, g.cell_cap, g.kcap);
+      for (int d = kOctMaxDepth; d >= 1 && g.depth == 0; d--)
+        if (g.nini < (1 << 10) && oct_pyr_layout(g.node_cap, g.cell_cap, g.kcap, g.span, g.nini, d).bytes <= have) g.depth = d;
+      // what the chosen depth leaves of the group's LDS holds more candidates, up to a level's most
+      if (g.depth > 0) {
+        const long long left = have - oct_pyr_layout(g.node_cap, g.cell_cap, g.kcap, g.span, g.nini, g.depth).bytes;
+        g.pcap = (int)std::min((long long)g.kcap + left / 4 / 64 * 64, std::max((long long)g.kcap, (long long)(mc + 63) / 64 * 64));
+      }
     };
     G.n_og = 0;
     group(0, split, 512, 50 * 1024, G.og[G.n_og++]);
@@ -400,6 +418,11 @@ orbx_status build_plan(const orbx_extractor_params& p, const Tables& t, int W, i
     // the CU's LDS to spend -- a handful of blocks, so the groups' two launches would only run one
     // after the other
     group(0, p.nlevels, 512, 150 * 1024, G.og_all);
+    // ... on the generic path alone (depth 0).  This row's blocks each have a CU to themselves, where
+    // the generic path's candidate passes cost little and the pyramid's fixed work (tables, clear,
+    // sums) does not pay: the single stereo frame measured 0.252 ms (parent) against 0.265 (depth 5)
+    // and 0.282 (depth 6), five and three alternating pairs, profiles/r13/ab_single_frame.txt
+    G.og_all.depth = 0;
   }
   return ORBX_OK;
 }

@@ -229,6 +229,27 @@ def debug_octree_candidates(extractor, cell_counts, candidates):
     return oct_count, oct_out
 
 
+def debug_octree_paths(extractor, cell_counts, candidates, depth_cap=-1):
+    """debug_octree_candidates' launch through orbx_debug_octree_paths, which also reports the path each
+    (image, level) block took: 0 an empty level, 1 the count pyramid, 2 the generic path.  depth_cap >= 0
+    runs the launch groups at min(plan's D, depth_cap); 0 is the generic path alone.
+
+    Returns (oct_count int32[n_img, nlevels], oct_out uint32[n_img, oct_total], paths int32[n_img, nlevels])."""
+    counts = np.ascontiguousarray(cell_counts, np.int32)
+    cand = np.ascontiguousarray(candidates, np.uint32)
+    w, h = extractor._last_shape
+    cells = debug_launch_plan(extractor.params, w, h, 11).reshape(-1, 8)  # ORBX_LP_CELLS
+    levels = debug_launch_plan(extractor.params, w, h, 12).reshape(-1, 8)  # ORBX_LP_OCT_LEVELS
+    n_img = len(counts)
+    assert counts.shape == (n_img, len(cells)) and cand.shape == (n_img, int(cells[:, 6].sum()))
+    oct_count = np.zeros((n_img, extractor.nlevels), np.int32)
+    oct_out = np.zeros((n_img, int(levels[:, 7].sum())), np.uint32)
+    paths = np.zeros((n_img, extractor.nlevels), np.int32)
+    check(_lib.lib().orbx_debug_octree_paths(extractor._h, n_img, ptr(counts), ptr(cand), int(depth_cap),
+                                             ptr(oct_count), ptr(oct_out), ptr(paths)), "orbx_debug_octree_paths")
+    return oct_count, oct_out, paths
+
+
 def frame_stereo(extractor, image_left, image_right, bf, baseline):
     """The ORB part of Frame's stereo constructor (src/Frame.cc:62-123: ExtractORB(0/1) + ComputeStereoMatches)
     in one call through `extractor` (both images as one batch of two, one copy back).

@@ -83,6 +83,14 @@
  *                               src/LoopClosing.cc DetectLoop, and :145, :274 of KeyFrameDatabase.cc)
  *   orbx_kfdb_read_state        KeyFrame::mnRelocQuery, mnRelocWords, mRelocScore, mnLoopQuery, mnLoopWords,
  *                               mLoopScore                      include/KeyFrame.h:145-150
+ *   orbx_covis_set_keyframe / _erase_keyframe / _set_points_bad
+ *                               the observation table: KeyFrame::mvpMapPoints with MapPoint::mObservations,
+ *                               nObs (AddObservation / EraseObservation, src/MapPoint.cc:98-139) and mbBad
+ *   orbx_covis_update_connections  KeyFrame::UpdateConnections steps 1-2   src/KeyFrame.cc:367-467
+ *   orbx_covis_vote             Tracking::UpdateLocalKeyFrames, the vote   src/Tracking.cc:1523-1581
+ *   orbx_covis_local_points     Tracking::UpdateLocalPoints               src/Tracking.cc:1483-1515
+ *   orbx_covis_cull             LocalMapping::KeyFrameCulling             src/LocalMapping.cc:784-871, with the
+ *                               observation half of KeyFrame::SetBadFlag  src/KeyFrame.cc:585-587
  */
 #ifndef ORBX_H
 #define ORBX_H
@@ -364,6 +372,81 @@ orbx_status orbx_kfdb_read_state(orbx_kfdb* db, const int64_t* kf_ids, int n, ui
                                  float* loop_score);
 /* live keyframes and pool entries in use (dead ones included until the next compaction) */
 orbx_status orbx_kfdb_size(const orbx_kfdb* db, int* live, long long* pool_entries);
+
+/* The covisibility relation as a device-resident observation table: one row per live keyframe (its mnId,
+ * >= 0), a feature being the MapPoint's mnId (int32, -1: none, below 2^26), the keypoint's octave (0..63)
+ * and two flag bits; per point nObs, the reference's stereo-weighted MapPoint::Observations(), and bad.
+ * CONTRACT: a row holds a point id at most once, and mObservations agrees with mvpMapPoints -- keyframe j
+ * observes point p at idx exactly when row j holds p at idx.  The reference keeps both outside transients;
+ * under it no inverse index is needed and none is stored: every query scans the rows against a bitmap.
+ * nObs follows the rows: setting a row adds 2 per stereo and 1 per other feature to its points, replacing or
+ * erasing one takes the old contributions out.  These calls never turn a point bad; orbx_covis_cull does
+ * (nObs <= 2, src/MapPoint.cc:132) and orbx_covis_set_points_bad does.  A bad point stays bad, its nObs is
+ * frozen (its observations are gone, src/MapPoint.cc:161), it counts in no query, and a row entry that
+ * names it reads as -1, which is what EraseMapPointMatch leaves (src/MapPoint.cc:163-167).
+ * All pointers are host pointers and every call is synchronous.  Refused before any device call with
+ * ORBX_ERR_ARG: null pointers, negative sizes, a keyframe id that is negative or (where a live one is
+ * required) not live, an id twice in a keyframe list or a point twice in a row, a point id below -1 (below
+ * 0 where -1 has no meaning) or not below 2^26, an octave outside 0..63, flag bits beyond the two.
+ * orbx_covis_create without a usable device: ORBX_ERR_NODEV.  A handle is not thread-safe. */
+typedef struct orbx_covis orbx_covis;
+#define ORBX_COVIS_STEREO 1 /* mvuRight[i] >= 0                              */
+#define ORBX_COVIS_CLOSE 2  /* !(mvDepth[i] > mThDepth || mvDepth[i] < 0)    */
+orbx_status orbx_covis_create(int device, orbx_covis** out);
+orbx_status orbx_covis_destroy(orbx_covis* h);
+orbx_status orbx_covis_clear(orbx_covis* h); /* forgets every keyframe and every point */
+/* The check set_keyframe applies to a row, on its own (needs no handle and no device). */
+orbx_status orbx_covis_check_row(const int32_t* point_ids, const int32_t* octaves, const uint8_t* flags, int n);
+/* Inserts keyframe kf_id's whole row of n features, or replaces it: after ProcessNewKeyFrame, Fuse / Replace,
+ * AddMapPoint / EraseMapPointMatch.  The pool and the tables grow on demand. */
+orbx_status orbx_covis_set_keyframe(orbx_covis* h, int64_t kf_id, int n, const int32_t* point_ids,
+                                    const int32_t* octaves, const uint8_t* flags);
+/* The row leaves with its nObs contributions (a keyframe that is not live: ORBX_ERR_ARG).  The pool is
+ * compacted once more of it is dead than live. */
+orbx_status orbx_covis_erase_keyframe(orbx_covis* h, int64_t kf_id);
+/* MapPoint::SetBadFlag / Replace seen from the table: the points are bad from now on (repeats are fine). */
+orbx_status orbx_covis_set_points_bad(orbx_covis* h, const int32_t* ids, int n);
+/* live keyframes, pool entries in use (dead ones included until the next compaction), largest point id + 1 */
+orbx_status orbx_covis_size(const orbx_covis* h, int* live, long long* pool_entries, int* n_points);
+/* Read-back probes.  A live keyframe's row as set, except that a bad point shows as -1 (ORBX_ERR_CAPACITY
+ * with *n the needed size); nObs and bad of points (ids the handle has seen, else ORBX_ERR_ARG). */
+orbx_status orbx_covis_read_keyframe(orbx_covis* h, int64_t kf_id, int32_t* point_ids, int32_t* octaves,
+                                     uint8_t* flags, int cap, int* n);
+orbx_status orbx_covis_read_points(orbx_covis* h, const int32_t* ids, int n, int32_t* n_obs, uint8_t* bad);
+/* KeyFrame::UpdateConnections steps 1 and 2 (src/KeyFrame.cc:373-467) for live keyframe kf_id; th is the
+ * reference's 15.  counter_*: KFcounter, every other keyframe sharing a non-bad point with its count, ids
+ * ascending -- all of it, below th too, as :475 assigns it to mConnectedKeyFrameWeights.  ordered_*:
+ * mvpOrderedConnectedKeyFrames / mvOrderedWeights, the entries with count >= th, weight descending and equal
+ * weights in DESCENDING id (sort ascending, then push_front, :459-467; ascending id stands for pointer order);
+ * when none reaches th, the single (nmax, pKFmax), pKFmax the SMALLEST id among the maximal counts (the first
+ * strictly greater count of an ascending walk, :434-438).  An empty counter gives *n_counter = *n_ordered = 0
+ * (:414 returns and leaves the keyframe untouched).  Step 3 and the other keyframes' AddConnection stay with
+ * the caller.  ORBX_ERR_CAPACITY when a list does not fit; both sizes are then set. */
+orbx_status orbx_covis_update_connections(orbx_covis* h, int64_t kf_id, int th, int64_t* counter_kfs,
+                                          int32_t* counter_w, int cap, int* n_counter, int64_t* ordered_kfs,
+                                          int32_t* ordered_w, int cap_ordered, int* n_ordered);
+/* The vote of Tracking::UpdateLocalKeyFrames (src/Tracking.cc:1523-1581): point_ids = the frame's
+ * mvpMapPoints (-1: none).  was_bad[i] = 1 where the point is bad, for the caller to null as :1540 does; such
+ * points and -1 do not vote.  kfs / counts: keyframeCounter, ids ascending; *kf_max / *n_max: pKFmax (the
+ * smallest id among the maxima) and max, -1 / 0 when nobody was voted for.  No keyframe is excluded.  The
+ * neighbour / child / parent expansion (:1589-1643) stays with the caller. */
+orbx_status orbx_covis_vote(orbx_covis* h, const int32_t* point_ids, int n, uint8_t* was_bad, int64_t* kfs,
+                            int32_t* counts, int cap, int* n_kfs, int64_t* kf_max, int32_t* n_max);
+/* Tracking::UpdateLocalPoints (src/Tracking.cc:1483-1515): the distinct non-bad points of the listed live
+ * keyframes in the order of first occurrence by (position in kf_ids, feature index). */
+orbx_status orbx_covis_local_points(orbx_covis* h, const int64_t* kf_ids, int n_kfs, int32_t* point_ids, int cap,
+                                    int* n_points);
+/* LocalMapping::KeyFrameCulling (src/LocalMapping.cc:784-871): cand_ids =
+ * mpCurrentKeyFrame->GetVectorCovisibleKeyFrames() in order (live keyframes), not_erase[c] = mbNotErase,
+ * monocular = mbMonocular.  The candidates are judged one after the other as the reference does; verdict[c]:
+ * 0 kept, 1 culled, 2 to be erased (redundant, but mbNotErase holds it: src/KeyFrame.cc:573-577, its
+ * observations stay).  A culled keyframe's row is retired, its points lose 1 or 2 from nObs and those at
+ * nObs <= 2 turn bad, all before the next candidate is judged; bad_ids receives the points that went bad,
+ * ascending.  The table is left in that state.  The graph and spanning-tree half of SetBadFlag
+ * (src/KeyFrame.cc:581-677) and the mpRefKF reassignment stay with the caller.  ORBX_ERR_CAPACITY when
+ * bad_ids is too small (*n_bad the needed size; the table has been updated all the same). */
+orbx_status orbx_covis_cull(orbx_covis* h, const int64_t* cand_ids, int n_cand, const uint8_t* not_erase,
+                            int monocular, uint8_t* verdict, int32_t* bad_ids, int cap, int* n_bad);
 
 /* Optimizer::LocalBundleAdjustment on g2o semantics (BlockSolver_6_3 +
  * LinearSolverEigen + Levenberg, Huber kernels, two phases), FP64 on the GPU.

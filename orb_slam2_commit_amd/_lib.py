@@ -305,6 +305,22 @@ SIGNATURES = {
     "orbx_kfdb_score": ([P, P, P, C.c_int, P, C.c_int, P], C.c_int),
     "orbx_kfdb_read_state": ([P, P, C.c_int, P, P, P, P, P, P], C.c_int),
     "orbx_kfdb_size": ([P, C.POINTER(C.c_int), C.POINTER(C.c_longlong)], C.c_int),
+    "orbx_covis_create": ([C.c_int, C.POINTER(C.c_void_p)], C.c_int),
+    "orbx_covis_destroy": ([P], C.c_int),
+    "orbx_covis_clear": ([P], C.c_int),
+    "orbx_covis_check_row": ([P, P, P, C.c_int], C.c_int),
+    "orbx_covis_set_keyframe": ([P, C.c_int64, C.c_int, P, P, P], C.c_int),
+    "orbx_covis_erase_keyframe": ([P, C.c_int64], C.c_int),
+    "orbx_covis_set_points_bad": ([P, P, C.c_int], C.c_int),
+    "orbx_covis_size": ([P, C.POINTER(C.c_int), C.POINTER(C.c_longlong), C.POINTER(C.c_int)], C.c_int),
+    "orbx_covis_read_keyframe": ([P, C.c_int64, P, P, P, C.c_int, C.POINTER(C.c_int)], C.c_int),
+    "orbx_covis_read_points": ([P, P, C.c_int, P, P], C.c_int),
+    "orbx_covis_update_connections": ([P, C.c_int64, C.c_int, P, P, C.c_int, C.POINTER(C.c_int), P, P, C.c_int,
+                                       C.POINTER(C.c_int)], C.c_int),
+    "orbx_covis_vote": ([P, P, C.c_int, P, P, P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64),
+                         C.POINTER(C.c_int32)], C.c_int),
+    "orbx_covis_local_points": ([P, P, C.c_int, P, C.c_int, C.POINTER(C.c_int)], C.c_int),
+    "orbx_covis_cull": ([P, P, C.c_int, P, C.c_int, P, P, C.c_int, C.POINTER(C.c_int)], C.c_int),
     "orbx_track_gather_device": ([C.POINTER(TrackGather), C.c_int, P], C.c_int),
     "orbx_frame_points_device": ([C.POINTER(FramePoints), C.c_int, P], C.c_int),
     "orbx_track_step_device": ([C.POINTER(TrackStep), C.c_int, P], C.c_int),

@@ -1770,6 +1770,135 @@ class KeyFrameDatabase:
               "orbx_kfdb_loop_candidates_device")
 
 
+class CovisibilityMap:
+    """The covisibility relation on the GPU over orbx_covis_*: a device-resident observation table (one row
+    per keyframe: MapPoint ids, octaves, the stereo and close flags; nObs and bad per point) and the four
+    queries that read it -- KeyFrame::UpdateConnections steps 1-2 (src/KeyFrame.cc:367-467), the vote of
+    Tracking::UpdateLocalKeyFrames (src/Tracking.cc:1523-1581), Tracking::UpdateLocalPoints (:1483-1515)
+    and LocalMapping::KeyFrameCulling (src/LocalMapping.cc:784-871) -- with the reference's exact counts,
+    orders and verdicts.  Keyframes and points are their mnIds.  Raises OrbxError (code -4) without a GPU --
+    there is no CPU fallback."""
+
+    STEREO, CLOSE = 1, 2
+    KEPT, CULLED, TO_BE_ERASED = 0, 1, 2
+
+    def __init__(self, device=0):
+        h = C.c_void_p()
+        check(_lib.lib().orbx_covis_create(int(device), C.byref(h)), "orbx_covis_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.lib().orbx_covis_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def clear(self):
+        check(_lib.lib().orbx_covis_clear(self._h), "orbx_covis_clear")
+
+    @staticmethod
+    def flags(u_right, depth, th_depth):
+        """The two flag bits from mvuRight / mvDepth / mThDepth, as the reference tests them."""
+        u, d = np.asarray(u_right, np.float32), np.asarray(depth, np.float32)
+        return ((u >= 0).astype(np.uint8) * CovisibilityMap.STEREO |
+                (~((d > np.float32(th_depth)) | (d < 0))).astype(np.uint8) * CovisibilityMap.CLOSE)
+
+    def set_keyframe(self, kf_id, point_ids, octaves, flags):
+        """Inserts or replaces the keyframe's whole row (point id -1: no MapPoint)."""
+        p = np.ascontiguousarray(point_ids, np.int32).reshape(-1)
+        o = np.ascontiguousarray(octaves, np.int32).reshape(-1)
+        f = np.ascontiguousarray(flags, np.uint8).reshape(-1)
+        if not (len(p) == len(o) == len(f)):
+            raise ValueError("row arrays differ in length")
+        check(_lib.lib().orbx_covis_set_keyframe(self._h, int(kf_id), len(p), ptr(p), ptr(o), ptr(f)),
+              "orbx_covis_set_keyframe")
+
+    def erase_keyframe(self, kf_id):
+        check(_lib.lib().orbx_covis_erase_keyframe(self._h, int(kf_id)), "orbx_covis_erase_keyframe")
+
+    def set_points_bad(self, ids):
+        a = np.ascontiguousarray(list(ids), np.int32)
+        check(_lib.lib().orbx_covis_set_points_bad(self._h, ptr(a), len(a)), "orbx_covis_set_points_bad")
+
+    def size(self):
+        """(live keyframes, pool entries in use, largest point id + 1)."""
+        live, pool, npts = C.c_int(), C.c_longlong(), C.c_int()
+        check(_lib.lib().orbx_covis_size(self._h, C.byref(live), C.byref(pool), C.byref(npts)), "orbx_covis_size")
+        return live.value, pool.value, npts.value
+
+    def read_keyframe(self, kf_id):
+        """The row as set, a bad point shown as -1: (point_ids, octaves, flags)."""
+        n, L = C.c_int(), _lib.lib()
+        rc = L.orbx_covis_read_keyframe(self._h, int(kf_id), None, None, None, 0, C.byref(n))
+        if rc not in (_lib.ORBX_OK, _lib.ORBX_ERR_CAPACITY):
+            check(rc, "orbx_covis_read_keyframe")
+        m = max(n.value, 1)
+        p, o, f = np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.uint8)
+        check(L.orbx_covis_read_keyframe(self._h, int(kf_id), ptr(p), ptr(o), ptr(f), m, C.byref(n)),
+              "orbx_covis_read_keyframe")
+        return p[:n.value], o[:n.value], f[:n.value]
+
+    def read_points(self, ids):
+        """(nObs, bad) of the listed points."""
+        a = np.ascontiguousarray(list(ids), np.int32)
+        nobs, bad = np.zeros(max(len(a), 1), np.int32), np.zeros(max(len(a), 1), np.uint8)
+        check(_lib.lib().orbx_covis_read_points(self._h, ptr(a), len(a), ptr(nobs), ptr(bad)),
+              "orbx_covis_read_points")
+        return nobs[:len(a)], bad[:len(a)]
+
+    def update_connections(self, kf_id, th=15):
+        """UpdateConnections steps 1-2: (KFcounter as [(kf, count)] ids ascending, the ordered list as
+        [(kf, weight)] weight descending / id descending, or the single (pKFmax, nmax) when none reaches th)."""
+        cap = max(self.size()[0], 1)
+        ck, cw = np.zeros(cap, np.int64), np.zeros(cap, np.int32)
+        ok, ow = np.zeros(cap, np.int64), np.zeros(cap, np.int32)
+        nc, no = C.c_int(), C.c_int()
+        check(_lib.lib().orbx_covis_update_connections(self._h, int(kf_id), int(th), ptr(ck), ptr(cw), cap,
+                                                       C.byref(nc), ptr(ok), ptr(ow), cap, C.byref(no)),
+              "orbx_covis_update_connections")
+        return (list(zip(ck[:nc.value].tolist(), cw[:nc.value].tolist())),
+                list(zip(ok[:no.value].tolist(), ow[:no.value].tolist())))
+
+    def vote(self, point_ids):
+        """The vote of UpdateLocalKeyFrames: (was_bad bytes, keyframeCounter as [(kf, count)] ids ascending,
+        pKFmax or None, max)."""
+        p = np.ascontiguousarray(point_ids, np.int32).reshape(-1)
+        cap = max(self.size()[0], 1)
+        wb = np.zeros(max(len(p), 1), np.uint8)
+        k, c = np.zeros(cap, np.int64), np.zeros(cap, np.int32)
+        n, kmax, nmax = C.c_int(), C.c_int64(), C.c_int32()
+        check(_lib.lib().orbx_covis_vote(self._h, ptr(p), len(p), ptr(wb), ptr(k), ptr(c), cap, C.byref(n),
+                                         C.byref(kmax), C.byref(nmax)), "orbx_covis_vote")
+        return (wb[:len(p)], list(zip(k[:n.value].tolist(), c[:n.value].tolist())),
+                None if kmax.value < 0 else kmax.value, nmax.value)
+
+    def local_points(self, kf_ids, cap=None):
+        """UpdateLocalPoints: the distinct non-bad points of the listed keyframes, first occurrence first."""
+        ids = np.ascontiguousarray(list(kf_ids), np.int64)
+        cap = max(self.size()[1], 1) if cap is None else int(cap)
+        out, n = np.zeros(max(cap, 1), np.int32), C.c_int()
+        check(_lib.lib().orbx_covis_local_points(self._h, ptr(ids), len(ids), ptr(out), cap, C.byref(n)),
+              "orbx_covis_local_points")
+        return out[:n.value].tolist()
+
+    def cull(self, cand_ids, not_erase, monocular):
+        """KeyFrameCulling over the candidates in order: (verdict per candidate, points that went bad)."""
+        ids = np.ascontiguousarray(list(cand_ids), np.int64)
+        ne = np.ascontiguousarray([1 if x else 0 for x in not_erase], np.uint8)
+        if len(ne) != len(ids):
+            raise ValueError("not_erase and cand_ids differ in length")
+        cap = max(self.size()[1], 1)
+        v, bad, n = np.zeros(max(len(ids), 1), np.uint8), np.zeros(cap, np.int32), C.c_int()
+        check(_lib.lib().orbx_covis_cull(self._h, ptr(ids), len(ids), ptr(ne), 1 if monocular else 0, ptr(v),
+                                         ptr(bad), cap, C.byref(n)), "orbx_covis_cull")
+        return v[:len(ids)].tolist(), bad[:n.value].tolist()
+
+
 def new_points_problem(prob):
     """orbx_new_points_problem from a dict(current, neighbours, monocular, scale_factor); every keyframe
     is a dict(keys_un, desc, u_right, has_mp, node_id, node_off, feat, keys_xy, depth, mp_pos, Tcw, fx, fy,

@@ -7,9 +7,11 @@
 // AddObservation, both AddMapPoint, ComputeDistinctiveDescriptors, UpdateNormalAndDepth,
 // Map::AddMapPoint, push to mlpRecentAddedMapPoints.
 //
+// KeyFrameCulling() (:784-871) runs over the Map's device-resident covisibility table.
+//
 // CheckNewKeyFrames() between neighbours (:320) is the handle's device-readable flag: InsertKeyFrame
 // raises it, CreateNewMapPoints sets it from mlNewKeyFrames on entry.  The first neighbour always runs.
-// The thread loop (Run, ProcessNewKeyFrame, MapPointCulling, SearchInNeighbors, KeyFrameCulling) stays
+// The thread loop (Run, ProcessNewKeyFrame, MapPointCulling, SearchInNeighbors) stays
 // with the caller; the reference's protected members the caller of this step touches are public here.
 #pragma once
 #include <list>
@@ -30,6 +32,11 @@ class LocalMapping {
   void InsertKeyFrame(KeyFrame* pKF);  // src/LocalMapping.cc:141-146
   bool CheckNewKeyFrames();            // :149-153
   void CreateNewMapPoints();           // :281-558
+  // :784-871 over the Map's covisibility table: ONE orbx_covis_cull call judges
+  // mpCurrentKeyFrame->GetVectorCovisibleKeyFrames() in order on the MI355X (verdicts, cascades and the points
+  // that go bad included), then the object-graph half of KeyFrame::SetBadFlag (src/KeyFrame.cc:581-677) is
+  // applied here per verdict.  The table must hold the current rows (Map::UploadCovisibilityRow).
+  void KeyFrameCulling();
 
   Map* mpMap;
   bool mbMonocular;

@@ -17,6 +17,8 @@
 
 #include "opencv_min.hpp"
 
+struct orbx_covis;  // include/orbx.h: the device-resident covisibility table a Map owns
+
 namespace DBoW2 {
 typedef unsigned int NodeId;
 typedef unsigned int WordId;
@@ -227,6 +229,65 @@ class KeyFrame {
   }
   static bool weightComp(int a, int b) { return a > b; }  // include/KeyFrame.h:141-143
 
+  // Covisibility graph and spanning tree (include/KeyFrame.h:66-134, src/KeyFrame.cc:147-192, 367-565, 686-700).
+  // UpdateConnections takes steps 1-2 (KFcounter, the threshold, the order) from the Map's device-resident
+  // table (orbx_covis_update_connections) and applies step 3 and the other keyframes' AddConnection here; the
+  // table must hold the current rows (Map::UploadCovisibilityRow).  Throws without mpMap or without a device.
+  void UpdateConnections();
+  void AddConnection(KeyFrame* pKF, const int& weight) {  // src/KeyFrame.cc:147-162
+    {
+      std::unique_lock<std::mutex> lock(mMutexConnections);
+      if (!mConnectedKeyFrameWeights.count(pKF))
+        mConnectedKeyFrameWeights[pKF] = weight;
+      else if (mConnectedKeyFrameWeights[pKF] != weight)
+        mConnectedKeyFrameWeights[pKF] = weight;
+      else
+        return;
+    }
+    UpdateBestCovisibles();
+  }
+  void EraseConnection(KeyFrame* pKF) {  // src/KeyFrame.cc:686-700
+    bool bUpdate = false;
+    {
+      std::unique_lock<std::mutex> lock(mMutexConnections);
+      if (mConnectedKeyFrameWeights.count(pKF)) {
+        mConnectedKeyFrameWeights.erase(pKF);
+        bUpdate = true;
+      }
+    }
+    if (bUpdate) UpdateBestCovisibles();
+  }
+  void UpdateBestCovisibles();  // src/KeyFrame.cc:169-192 (pairs ordered by weight, then by mnId for pointer order)
+  void AddChild(KeyFrame* pKF) {  // src/KeyFrame.cc:495-499
+    std::unique_lock<std::mutex> lockCon(mMutexConnections);
+    mspChildrens.insert(pKF);
+  }
+  void EraseChild(KeyFrame* pKF) {  // src/KeyFrame.cc:501-505
+    std::unique_lock<std::mutex> lockCon(mMutexConnections);
+    mspChildrens.erase(pKF);
+  }
+  void ChangeParent(KeyFrame* pKF) {  // src/KeyFrame.cc:507-512
+    {
+      std::unique_lock<std::mutex> lockCon(mMutexConnections);
+      mpParent = pKF;
+    }
+    pKF->AddChild(this);
+  }
+  std::set<KeyFrame*> GetChilds() {  // src/KeyFrame.cc:514-518
+    std::unique_lock<std::mutex> lockCon(mMutexConnections);
+    return mspChildrens;
+  }
+  void SetNotErase() {  // src/KeyFrame.cc:545-549
+    std::unique_lock<std::mutex> lock(mMutexConnections);
+    mbNotErase = true;
+  }
+  // src/KeyFrame.cc:567-678.  SetBadFlag() also takes the keyframe's row out of the Map's table (when the Map has
+  // one and the row is there) and reports the points that went bad to it; SetBadFlagHost() is the object-graph
+  // half alone, for LocalMapping::KeyFrameCulling, whose device call has done the table's half already.  Returns
+  // false when nothing happened (mnId 0, or mbNotErase: mbToBeErased is set).
+  void SetBadFlag();
+  bool SetBadFlagHost();
+
   long unsigned int mnId = 0;
   long unsigned int mnBALocalForKF = 0, mnBAFixedForKF = 0;
   // written by Optimizer::BundleAdjustment with nLoopKF != 0 (include/KeyFrame.h:197-199)
@@ -262,13 +323,49 @@ class KeyFrame {
   std::vector<int> mvOrderedWeights;
   KeyFrame* mpParent = nullptr;
   std::set<KeyFrame*> mspChildrens, mspLoopEdges;
+  bool mbFirstConnection = true;                    // include/KeyFrame.h:280
+  bool mbNotErase = false, mbToBeErased = false;   // include/KeyFrame.h:290-291
   bool mbBad = false;
+  Map* mpMap = nullptr;                             // include/KeyFrame.h:296
   cv::Mat Tcw, Ow;
   std::mutex mMutexPose, mMutexConnections, mMutexFeatures;
 };
 
 class Map {
  public:
+  Map() = default;
+  ~Map();  // (shim.cc: destroys the covisibility table)
+  Map(const Map&) = delete;
+  Map& operator=(const Map&) = delete;
+  void AddKeyFrame(KeyFrame* pKF) {    // src/Map.cc:39-45
+    std::unique_lock<std::mutex> lock(mMutexMap);
+    mspKeyFrames.insert(pKF);
+    if (pKF->mnId > mnMaxKFid) mnMaxKFid = pKF->mnId;
+  }
+  void EraseKeyFrame(KeyFrame* pKF) {  // src/Map.cc:62-68
+    std::unique_lock<std::mutex> lock(mMutexMap);
+    mspKeyFrames.erase(pKF);
+  }
+  // The device-resident covisibility table (orbx_covis, include/orbx.h), created on first use; throws
+  // std::runtime_error without a device.  Not in the reference: it is what KeyFrame::UpdateConnections and
+  // LocalMapping::KeyFrameCulling scan instead of walking mObservations.
+  orbx_covis* Covisibility();
+  // Uploads pKF's whole row from mvpMapPoints / mvKeysUn[i].octave / mvuRight / mvDepth / mThDepth (a bad
+  // MapPoint goes up as "none"): after ProcessNewKeyFrame, Fuse / Replace, AddMapPoint / EraseMapPointMatch.
+  void UploadCovisibilityRow(KeyFrame* pKF);
+  // MapPoint::SetBadFlag / Replace seen from the table
+  void CovisibilityPointsBad(const std::vector<MapPoint*>& vpMP);
+  // the objects behind the table's ids (nullptr when the table has never seen the id)
+  KeyFrame* CovisibilityKeyFrame(long unsigned int id) {
+    auto it = mCovisKFs.find(id);
+    return it == mCovisKFs.end() ? nullptr : it->second;
+  }
+  MapPoint* CovisibilityMapPoint(long unsigned int id) {
+    auto it = mCovisMPs.find(id);
+    return it == mCovisMPs.end() ? nullptr : it->second;
+  }
+  std::map<long unsigned int, KeyFrame*> mCovisKFs;  // the rows the table holds
+  std::map<long unsigned int, MapPoint*> mCovisMPs;  // every point uploaded in a row
   void AddMapPoint(MapPoint* pMP) {    // src/Map.cc:48-52
     std::unique_lock<std::mutex> lock(mMutexMap);
     mspMapPoints.insert(pMP);
@@ -294,6 +391,9 @@ class Map {
   long unsigned int mnMaxKFid = 0;
   std::mutex mMutexMapUpdate;  // include/Map.h:65
   std::mutex mMutexMap;
+
+ private:
+  orbx_covis* mpCovis = nullptr;
 };
 
 // ---- the reference bodies (src/MapPoint.cc, src/KeyFrame.cc), restated for the stand-ins
@@ -409,6 +509,87 @@ inline void MapPoint::Replace(MapPoint* pMP) {
   pMP->IncreaseVisible(nvisible);
   pMP->ComputeDistinctiveDescriptors();
   if (mpMap) mpMap->EraseMapPoint(this);
+}
+
+inline void KeyFrame::UpdateBestCovisibles() {
+  std::unique_lock<std::mutex> lock(mMutexConnections);
+  std::vector<std::pair<std::pair<int, long unsigned int>, KeyFrame*>> vPairs;
+  vPairs.reserve(mConnectedKeyFrameWeights.size());
+  for (auto& m : mConnectedKeyFrameWeights) vPairs.push_back({{m.second, m.first->mnId}, m.first});
+  std::sort(vPairs.begin(), vPairs.end());  // :180 (ascending weight; ascending mnId stands for the pointer)
+  mvpOrderedConnectedKeyFrames.clear();
+  mvOrderedWeights.clear();
+  for (size_t i = vPairs.size(); i-- > 0;) {  // :183-187 push_front
+    mvpOrderedConnectedKeyFrames.push_back(vPairs[i].second);
+    mvOrderedWeights.push_back(vPairs[i].first.first);
+  }
+}
+
+inline bool KeyFrame::SetBadFlagHost() {
+  auto byId = [](KeyFrame* a, KeyFrame* b) { return a->mnId < b->mnId; };
+  {
+    std::unique_lock<std::mutex> lock(mMutexConnections);
+    if (mnId == 0) return false;  // :571
+    if (mbNotErase) {             // :573-577
+      mbToBeErased = true;
+      return false;
+    }
+  }
+  {
+    std::vector<KeyFrame*> conn;
+    for (auto& m : mConnectedKeyFrameWeights) conn.push_back(m.first);
+    for (KeyFrame* k : conn) k->EraseConnection(this);  // :581-582
+  }
+  for (size_t i = 0; i < mvpMapPoints.size(); i++)  // :585-587
+    if (mvpMapPoints[i]) mvpMapPoints[i]->EraseObservation(this);
+  KeyFrame* parent;
+  std::vector<KeyFrame*> children;
+  {
+    std::unique_lock<std::mutex> lock(mMutexConnections);
+    mConnectedKeyFrameWeights.clear();  // :593-594
+    mvpOrderedConnectedKeyFrames.clear();
+    parent = mpParent;
+    children.assign(mspChildrens.begin(), mspChildrens.end());
+  }
+  std::sort(children.begin(), children.end(), byId);
+  // Update Spanning Tree (:597-668): at each round the (child, candidate) pair of highest covisibility weight
+  std::vector<KeyFrame*> sParentCandidates;
+  if (parent) sParentCandidates.push_back(parent);
+  while (!children.empty()) {
+    bool bContinue = false;
+    int max = -1;
+    KeyFrame *pC = nullptr, *pP = nullptr;
+    for (KeyFrame* pKF : children) {  // :612
+      if (pKF->isBad()) continue;
+      const std::vector<KeyFrame*> vpConnected = pKF->GetVectorCovisibleKeyFrames();
+      for (size_t i = 0; i < vpConnected.size(); i++)
+        for (KeyFrame* cand : sParentCandidates)  // :623 (ascending mnId)
+          if (vpConnected[i]->mnId == cand->mnId) {
+            const int w = pKF->GetWeight(vpConnected[i]);
+            if (w > max) {
+              pC = pKF;
+              pP = vpConnected[i];
+              max = w;
+              bContinue = true;
+            }
+          }
+    }
+    if (!bContinue) break;
+    pC->ChangeParent(pP);  // :651-655
+    sParentCandidates.insert(std::upper_bound(sParentCandidates.begin(), sParentCandidates.end(), pC, byId), pC);
+    children.erase(std::find(children.begin(), children.end(), pC));
+  }
+  if (parent) {
+    for (KeyFrame* c : children) c->ChangeParent(parent);  // :663-668
+    parent->EraseChild(this);                              // :670 (a keyframe without a parent skips it)
+  }
+  {
+    std::unique_lock<std::mutex> lock(mMutexConnections);
+    mspChildrens = std::set<KeyFrame*>(children.begin(), children.end());  // (the re-parented ones left at :655)
+    mbBad = true;  // :672
+  }
+  if (mpMap) mpMap->EraseKeyFrame(this);  // :676
+  return true;
 }
 
 inline void KeyFrame::SetPose(const cv::Mat& Tcw_) {

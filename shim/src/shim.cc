@@ -1307,6 +1307,130 @@ void MapPoint::ComputeDistinctiveDescriptors() {
   mDescriptor = d;
 }
 
+// ------------------------------------------------------------------ the covisibility table of a Map
+Map::~Map() {
+  if (mpCovis) orbx_covis_destroy(mpCovis);
+}
+
+orbx_covis* Map::Covisibility() {
+  if (!mpCovis) check(orbx_covis_create(gOrbxDevice, &mpCovis), "orbx_covis_create");
+  return mpCovis;
+}
+
+void Map::UploadCovisibilityRow(KeyFrame* pKF) {
+  orbx_covis* h = Covisibility();
+  const std::vector<MapPoint*> vpMP = pKF->GetMapPointMatches();
+  const size_t n = vpMP.size();
+  if (pKF->mvKeysUn.size() < n || pKF->mvuRight.size() < n || pKF->mvDepth.size() < n)
+    throw std::runtime_error("Map::UploadCovisibilityRow: mvKeysUn / mvuRight / mvDepth shorter than mvpMapPoints");
+  std::vector<int32_t> pid(n), oct(n);
+  std::vector<uint8_t> flags(n);
+  for (size_t i = 0; i < n; i++) {
+    MapPoint* pMP = vpMP[i];
+    pid[i] = (pMP && !pMP->isBad()) ? (int32_t)pMP->mnId : -1;
+    if (pMP && pMP->mnId >= (1ul << 26)) throw std::runtime_error("Map::UploadCovisibilityRow: MapPoint id beyond 2^26");
+    if (pid[i] >= 0) mCovisMPs[pMP->mnId] = pMP;
+    oct[i] = pKF->mvKeysUn[i].octave;
+    flags[i] = (uint8_t)((pKF->mvuRight[i] >= 0 ? ORBX_COVIS_STEREO : 0) |
+                         (!(pKF->mvDepth[i] > pKF->mThDepth || pKF->mvDepth[i] < 0) ? ORBX_COVIS_CLOSE : 0));
+  }
+  check(orbx_covis_set_keyframe(h, (int64_t)pKF->mnId, (int)n, pid.data(), oct.data(), flags.data()),
+        "orbx_covis_set_keyframe");
+  mCovisKFs[pKF->mnId] = pKF;
+}
+
+void Map::CovisibilityPointsBad(const std::vector<MapPoint*>& vpMP) {
+  std::vector<int32_t> ids;
+  for (MapPoint* p : vpMP)
+    if (p && p->mnId < (1ul << 26)) ids.push_back((int32_t)p->mnId);
+  if (ids.empty()) return;
+  check(orbx_covis_set_points_bad(Covisibility(), ids.data(), (int)ids.size()), "orbx_covis_set_points_bad");
+}
+
+void KeyFrame::UpdateConnections() {
+  if (!mpMap) throw std::runtime_error("KeyFrame::UpdateConnections: the keyframe has no Map (mpMap)");
+  orbx_covis* h = mpMap->Covisibility();
+  const int cap = (int)std::max<size_t>(mpMap->mCovisKFs.size(), 1);
+  std::vector<int64_t> ck(cap), ok(cap);
+  std::vector<int32_t> cw(cap), ow(cap);
+  int nc = 0, no = 0;
+  // steps 1 and 2 (src/KeyFrame.cc:373-467) on the MI355X; th = 15 (:424)
+  check(orbx_covis_update_connections(h, (int64_t)mnId, 15, ck.data(), cw.data(), cap, &nc, ok.data(), ow.data(), cap,
+                                      &no),
+        "orbx_covis_update_connections");
+  if (nc == 0) return;  // :414
+  auto kf = [&](int64_t id) {
+    KeyFrame* p = mpMap->CovisibilityKeyFrame((long unsigned int)id);
+    if (!p) throw std::runtime_error("KeyFrame::UpdateConnections: the table names a keyframe the Map does not know");
+    return p;
+  };
+  std::map<KeyFrame*, int> KFcounter;
+  for (int i = 0; i < nc; i++) KFcounter[kf(ck[i])] = cw[i];
+  std::vector<KeyFrame*> vpOrdered(no);
+  for (int i = 0; i < no; i++) {
+    vpOrdered[i] = kf(ok[i]);
+    vpOrdered[i]->AddConnection(this, ow[i]);  // :445, :455
+  }
+  // step 3 (:470-492)
+  std::unique_lock<std::mutex> lockCon(mMutexConnections);
+  mConnectedKeyFrameWeights = KFcounter;
+  mvpOrderedConnectedKeyFrames = vpOrdered;
+  mvOrderedWeights.assign(ow.begin(), ow.begin() + no);
+  if (mbFirstConnection && mnId != 0) {
+    mpParent = mvpOrderedConnectedKeyFrames.front();
+    lockCon.unlock();
+    mpParent->AddChild(this);
+    mbFirstConnection = false;
+  }
+}
+
+void KeyFrame::SetBadFlag() {
+  std::vector<MapPoint*> before;
+  for (MapPoint* p : mvpMapPoints)
+    if (p && !p->isBad()) before.push_back(p);
+  if (!SetBadFlagHost()) return;
+  if (!mpMap || !mpMap->CovisibilityKeyFrame(mnId)) return;
+  check(orbx_covis_erase_keyframe(mpMap->Covisibility(), (int64_t)mnId), "orbx_covis_erase_keyframe");
+  mpMap->mCovisKFs.erase(mnId);
+  std::vector<MapPoint*> bad;
+  for (MapPoint* p : before)
+    if (p->isBad()) bad.push_back(p);  // nObs <= 2 after this keyframe's observation left (src/MapPoint.cc:132)
+  mpMap->CovisibilityPointsBad(bad);
+}
+
+void LocalMapping::KeyFrameCulling() {
+  const std::vector<KeyFrame*> vpLocalKeyFrames = mpCurrentKeyFrame->GetVectorCovisibleKeyFrames();  // :793
+  const int n = (int)vpLocalKeyFrames.size();
+  if (n == 0) return;
+  orbx_covis* h = mpMap->Covisibility();
+  std::vector<int64_t> ids(n);
+  std::vector<uint8_t> notErase(n), verdict(n);
+  size_t cap = 1;
+  for (int c = 0; c < n; c++) {
+    ids[c] = (int64_t)vpLocalKeyFrames[c]->mnId;
+    notErase[c] = vpLocalKeyFrames[c]->mbNotErase ? 1 : 0;
+    cap += vpLocalKeyFrames[c]->mvpMapPoints.size();
+  }
+  std::vector<int32_t> bad(cap);
+  int nBad = 0;
+  // :796-870, the candidates judged in order on the MI355X
+  check(orbx_covis_cull(h, ids.data(), n, notErase.data(), mbMonocular ? 1 : 0, verdict.data(), bad.data(), (int)cap,
+                        &nBad),
+        "orbx_covis_cull");
+  // :869 per verdict: the object-graph half of SetBadFlag (mbNotErase: mbToBeErased, src/KeyFrame.cc:573-577)
+  for (int c = 0; c < n; c++) {
+    if (verdict[c] == 0) continue;
+    KeyFrame* pKF = vpLocalKeyFrames[c];
+    if (pKF->SetBadFlagHost()) mpMap->mCovisKFs.erase(pKF->mnId);
+  }
+  // the points the table turned bad are the ones EraseObservation turned bad on the objects
+  for (int i = 0; i < nBad; i++) {
+    MapPoint* pMP = mpMap->CovisibilityMapPoint((long unsigned int)bad[i]);
+    if (!pMP) throw std::runtime_error("LocalMapping::KeyFrameCulling: the table names a MapPoint the Map does not know");
+    if (!pMP->isBad()) pMP->SetBadFlag();
+  }
+}
+
 ORBVocabulary::~ORBVocabulary() {
   if (mpScoreDb) orbx_kfdb_destroy(mpScoreDb);
   if (mpGpu) orbx_voc_destroy(mpGpu);
